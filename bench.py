@@ -11,6 +11,10 @@ A step = one batch of --batch rows per GPU (weak scaling): generate the batch
 on device, dedup its keys, pull weights (sharded table, sparse all-to-all over
 RCCL when N > 1), fused forward/backward, push gradients, per-coordinate FTRL
 update on the owners.  Nothing is skipped inside the timed region.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.
+--dump-outputs DIR also writes what the timed steps computed (.npy); --full
+adds the measurements that take a run of their own.
 """
 from __future__ import annotations
 
@@ -119,6 +123,17 @@ def parse():
                     help="generate batch t+1 on a side stream while step t runs (measured on "
                          "one MI355X: 2-4%% slower for the fused and the multi-rank step, the "
                          "generator competes with the step's kernels for CUs and LDS)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy "
+                         "(dump_outputs below): the trained weights of the last timed batch's "
+                         "leading rows, the model's predictions on that batch and the timed "
+                         "steps' loss sums.  Same arguments, same inputs: two builds compare "
+                         "output for output.  One process, the plain engine step only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: one more "
+                         "(untimed) step that counts the gradient reduction's records "
+                         "(reduction_records_per_step).  Off: set up, warm up, time the steps, "
+                         "print the result line")
     return ap.parse_args()
 
 
@@ -127,6 +142,40 @@ def _entropy(p: float) -> float:
     if p <= 0.0 or p >= 1.0:
         return 0.0
     return -(p * math.log(p) + (1.0 - p) * math.log(1.0 - p))
+
+
+DUMP_ROWS = 8192  # leading rows of the last timed batch whose keys' weights are written
+
+
+def dump_outputs(path, engine, gen, st):
+    """--dump-outputs: what the timed steps computed, as float .npy files.
+
+    A training step returns nothing to its caller: its results are the updated
+    table and the loss sums.  Written (a few MB in all):
+      weights.npy  float32 [n, params_per_key]: the trained weights of the
+                   distinct keys (ascending) in the first DUMP_ROWS rows of the
+                   last timed batch -- a fixed sample that holds every hot key
+      pctr.npy     float32 [rows]: the trained table's predictions on the
+                   last timed batch (forward only, nothing is inserted)
+      stats.npy    float64 [3]: ln-loss sum, rows, positives of the timed steps
+    The generator is counter-based, so the last batch is generated again from
+    (seed, step index) here: nothing extra is kept during the timed steps."""
+    import numpy as np
+
+    g = SyntheticCriteo(engine, gen.rows, gen.cfg, rank=gen.rank, slice_rows=gen.slice_rows)
+    g.step = gen.step - 1
+    batch = g.next(out=g.alloc_batch())
+    F, rows = g.cfg.fields, gen.rows
+    n = min(rows, DUMP_ROWS)
+    k = batch.keys.view(F, rows)[:, :n] if batch.field_major else batch.keys.view(rows, F)[:n]
+    keys = np.unique(k.contiguous().cpu().numpy().view(np.uint64))
+    weights = engine.pull(keys)
+    pctr = engine.eval_step(batch).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "weights.npy"), np.ascontiguousarray(weights, dtype=np.float32))
+    np.save(os.path.join(path, "pctr.npy"), np.ascontiguousarray(pctr, dtype=np.float32))
+    np.save(os.path.join(path, "stats.npy"),
+            np.array([st["ln_loss"], st["rows"], st["positives"]], dtype=np.float64))
 
 
 def run_async(a, world, rank, device, use_gpu, shared_gpu, synth, log2_cap, nnz):
@@ -254,6 +303,9 @@ def main():
     if world != a.gpus:
         if world == 1 and a.gpus > 1:
             raise SystemExit("--gpus > 1 must be launched with torch.distributed.run")
+    if a.dump_outputs and (world > 1 or a.async_ps or a.async_p2p or a.sharded or a.overlap == "on"):
+        raise SystemExit("--dump-outputs covers the plain engine step of one process "
+                         "(no --sharded, --async, --async-lockstep, --overlap on)")
     use_gpu = torch.cuda.is_available() and not a.cpu
     shared_gpu = False
     if use_gpu:
@@ -407,11 +459,13 @@ def main():
     elapsed = time.perf_counter() - t0
     st = engine.read_stats(reset=True)
     tbl = engine.table_size()
-    # one more (untimed) step with the reduction's records counted: how much
-    # gradient work a step of this model does (MVM: none for rows whose field
-    # product vanished)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, engine, gen, st)
+    # --full: one more (untimed) step with the reduction's records counted: how
+    # much gradient work a step of this model does (MVM: none for rows whose
+    # field product vanished)
     records = -1
-    if use_gpu:
+    if use_gpu and a.full:
         engine.count_records(True)
         step()
         sync()
@@ -480,7 +534,7 @@ def main():
             # rate's entropy): a model learns when logloss falls below it
             "constant_logloss": _entropy(vals[7] / max(rows, 1.0)),
             "table_keys": int(table_keys),
-            "reduction_records_per_step": int(records),
+            **({"reduction_records_per_step": int(records)} if a.full else {}),
             "table_load": table_keys / float(world * 2 ** log2_cap),
             "prefilled_keys": int(prefill_tot),
             "host_waits": int(sharded.host_waits) if sharded is not None else 0,

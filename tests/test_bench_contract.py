@@ -55,6 +55,31 @@ def test_bench_json_line(n, extra):
     assert 0.0 < d["logloss"] < 1.0 and d["table_keys"] > 0
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes what the timed steps computed as float .npy files,
+    identical from run to run (same arguments, same inputs); a plain run does
+    not take the extra record-counting step, --full reports it."""
+    import numpy as np
+
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = _run(1, ["--dump-outputs", str(tmp_path / name)] + extra)
+        assert ("reduction_records_per_step" in d) == bool(extra)
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        out = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert set(out) == {"weights", "pctr", "stats"}
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in out.values())
+        assert sum(v.nbytes for v in out.values()) <= 64 << 20
+        # the timed steps' sums are the result line's logloss
+        assert out["stats"][0] / out["stats"][1] == pytest.approx(d["logloss"], rel=1e-12)
+        assert out["stats"][1] == d["steps"] * d["config"]["rows_per_gpu"]
+        assert out["pctr"].shape == (d["config"]["rows_per_gpu"],)
+        assert ((out["pctr"] > 0) & (out["pctr"] < 1)).all() and np.count_nonzero(out["weights"]) > 0
+        runs.append(out)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--sharded"], ["--async"], ["--async-lockstep"], ["--slices", "8"],
                                    ["--model", "fm", "--v-dim", "8"], ["--model", "mvm", "--v-dim", "10"]])
@@ -67,6 +92,24 @@ def test_bench_json_line_on_gpu(gpu_device, extra):
     assert d["config"]["backend"].startswith("hip:gfx950")
     assert d["table_load"] > 0.4 and d["prefilled_keys"] > 0
     assert 0.0 < d["logloss"] < 1.0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_on_gpu(gpu_device, tmp_path):
+    """--dump-outputs on the HIP backend (small table, 16 384 rows): the three
+    arrays, finite, and the loss sums behind the result line's logloss."""
+    import numpy as np
+
+    d = _run(1, ["--batch", "16384", "--log2-cap", "24", "--clock-warmup-s", "0",
+                 "--dump-outputs", str(tmp_path)], cpu=False)
+    assert d["config"]["backend"].startswith("hip:gfx950")
+    out = {n: np.load(tmp_path / (n + ".npy")) for n in ("weights", "pctr", "stats")}
+    assert out["weights"].dtype == np.float32 and out["pctr"].dtype == np.float32
+    assert all(np.isfinite(v).all() for v in out.values())
+    assert out["pctr"].shape == (16384,) and ((out["pctr"] > 0) & (out["pctr"] < 1)).all()
+    assert out["weights"].shape[1] == 1 and np.count_nonzero(out["weights"]) > 0
+    assert out["stats"][1] == 2 * 16384
+    assert out["stats"][0] / out["stats"][1] == pytest.approx(d["logloss"], rel=1e-12)
 
 
 @pytest.mark.gpu
