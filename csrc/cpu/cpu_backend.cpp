@@ -158,11 +158,15 @@ class CpuBackend final : public Backend {
     int64_t n = count_of(a.n_dev, a.n_host, a.n_max);
     const TableView& t = a.table;
     const TableLayout& L = t.L;
+    // feature admission (AdmitView): look up only, then count, then insert
+    const bool admit = a.insert && a.admit.counters != nullptr;
+    std::vector<int64_t> absent;  // entries phase 1 found no slot for
     for (int64_t i = 0; i < n; ++i) {
       u64 key = sanitize_key(a.keys[i]);
       bool claimed = false;
-      u32 slot = probe(t, key, a.insert, claimed);
+      u32 slot = probe(t, key, a.insert && !admit, claimed);
       if (claimed) ++*t.size;
+      if (admit && slot == kNoSlot) absent.push_back(i);
       if (a.out_slot) a.out_slot[i] = slot;
       if (a.out_vals) {
         float* dst = a.out_vals + (size_t)(a.out_map ? a.out_map[i] : i) * a.pstride;
@@ -173,6 +177,25 @@ class CpuBackend final : public Backend {
           for (int p = 0; p < L.P; ++p) dst[p] = slot_weight(sp, key, p, L, a.opt);
         }
       }
+    }
+    if (!admit) return;
+    // phase 2: every absent entry counts a sighting in both of its counters
+    for (int64_t i : absent) {
+      const AdmitPos p = admit_pos(sanitize_key(a.keys[i]), a.admit.log2);
+      if (a.admit.counters[p.c0] != 255) ++a.admit.counters[p.c0];
+      if (a.admit.counters[p.c1] != 255) ++a.admit.counters[p.c1];
+    }
+    // phase 3: decide from the counters after all of the call's increments.
+    // The values written above stand: a fresh slot reads as an absent key.
+    for (int64_t i : absent) {
+      const u64 key = sanitize_key(a.keys[i]);
+      const AdmitPos p = admit_pos(key, a.admit.log2);
+      const int c0 = a.admit.counters[p.c0], c1 = a.admit.counters[p.c1];
+      if ((c0 < c1 ? c0 : c1) < a.admit.min_count) continue;
+      bool claimed = false;
+      const u32 slot = probe(t, key, true, claimed);
+      if (claimed) ++*t.size;
+      if (a.out_slot) a.out_slot[i] = slot;
     }
   }
 

@@ -88,6 +88,19 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   table_.overflow = overflow_ + 1;
   be.memset(mon_, 0, 4 * sizeof(u32));
   be.table_clear(table_);
+  // feature admission: the counting filter (EngineConfig::admit_min_count)
+  if (cfg_.admit_min_count < 1 || cfg_.admit_min_count > 255)
+    throw std::invalid_argument("admit_min_count must be in [1, 255]");
+  if (cfg_.admit_log2 != 0 && (cfg_.admit_log2 < kAdmitBlockLog2 || cfg_.admit_log2 > kAdmitMaxLog2))
+    throw std::invalid_argument("admit_log2 must be 0 (automatic) or in [6, 32]");
+  if (cfg_.admit_min_count > 1) {
+    const int top = cfg_.table_grow ? max_log2_cap_ : log2_cap_;
+    admit_.log2 = cfg_.admit_log2 ? cfg_.admit_log2 : (top + 1 < kAdmitMaxLog2 ? top + 1 : kAdmitMaxLog2);
+    if (admit_.log2 < kAdmitBlockLog2) admit_.log2 = kAdmitBlockLog2;
+    admit_.min_count = cfg_.admit_min_count;
+    admit_.counters = balloc<unsigned char>(be, (size_t)1 << admit_.log2);
+    be.memset(admit_.counters, 0, (size_t)1 << admit_.log2);
+  }
   snaps_ = static_cast<HostSnap*>(be.host_alloc(sizeof(HostSnap) * kSnaps));
   std::memset(snaps_, 0, sizeof(HostSnap) * kSnaps);
 
@@ -222,7 +235,7 @@ Engine::~Engine() {
   be.table_release(table_.words);
   be.free_stream(csr_roff_);
   be.free_stream(csr_long_);
-  void* ptrs[] = {mon_, scratch_.keys, scratch_.stamps,
+  void* ptrs[] = {admit_.counters, mon_, scratch_.keys, scratch_.stamps,
                   scratch_.claims, block_counts_, uniq_keys_, uniq_slot_, wpull_, grad_, tmask_,
                   stats_, bucket_ws_, slice_rows_, st_keys_, st_fgid_, st_rowptr_, st_labels_,
                   host_keys_dev_, host_vals_dev_,
@@ -650,6 +663,7 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   pa.n_dev = n_uniq_;
   pa.n_max = b.nnz;
   pa.insert = true;
+  pa.admit = admit_;
   pa.out_slot = uniq_slot_;
   pa.out_vals = wpull_;
   pa.pstride = pstride();
@@ -896,6 +910,7 @@ void Engine::train_step(const BatchView& b) {
   pa.n_dev = n_uniq_;
   pa.n_max = b.nnz;
   pa.insert = true;
+  pa.admit = admit_;
   pa.out_slot = uniq_slot_;
   pa.out_vals = wpull_;
   pa.out_map = upos ? nullptr : uniq_pos_;
@@ -1254,6 +1269,7 @@ void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool inser
   pa.n_host = n;
   pa.n_max = n;
   pa.insert = insert;
+  if (insert) pa.admit = admit_;
   pa.out_slot = sb.slots;
   pa.out_vals = out_vals;
   pa.pstride = pstride();
@@ -1767,6 +1783,38 @@ int64_t Engine::table_size() {
   known_size_ = (int64_t)n;
   known_adds_ = queued_adds_;
   return (int64_t)n;
+}
+
+std::vector<uint8_t> Engine::admit_counts(const std::vector<u64>& keys) {
+  std::vector<uint8_t> out(keys.size(), 0);
+  if (!admit_.counters) return out;
+  for (size_t i = 0; i < keys.size(); ++i) {
+    const AdmitPos p = admit_pos(sanitize_key(keys[i]), admit_.log2);
+    uint8_t c0 = 0, c1 = 0;
+    be_->copy_d2h(&c0, admit_.counters + p.c0, 1);  // (synchronising)
+    be_->copy_d2h(&c1, admit_.counters + p.c1, 1);
+    out[i] = c0 < c1 ? c0 : c1;
+  }
+  return out;
+}
+
+void Engine::admit_export(uint8_t* dst) {
+  if (admit_.counters) be_->copy_d2h(dst, admit_.counters, admit_bytes());
+}
+
+void Engine::admit_import(const uint8_t* src) {
+  if (!admit_.counters) throw std::runtime_error("admit_import: admission is off");
+  be_->synchronize();
+  be_->copy_h2d(admit_.counters, src, admit_bytes());
+  be_->synchronize();
+}
+
+std::vector<u32> Engine::server_slots(int buf) {
+  if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
+  const SrvBuf& sb = srv_[buf];
+  std::vector<u32> out((size_t)(sb.n > 0 ? sb.n : 0));
+  if (!out.empty()) be_->copy_d2h(out.data(), sb.slots, sizeof(u32) * out.size());
+  return out;
 }
 
 int64_t Engine::scratch_capacity() {

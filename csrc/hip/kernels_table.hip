@@ -950,9 +950,124 @@ static int packed_grid(int64_t n, int P) {
   return (int)(g < 1 ? 1 : (g < kGroupGridCap ? g : kGroupGridCap));
 }
 
+// ---------------------------------------------------------------------------
+// feature admission (AdmitView, backend.h): phases 2 and 3 of an inserting
+// pull, over the entries the probe-only pull before them left without a slot
+// ---------------------------------------------------------------------------
+// Each lane owns kAdmitItems entries one block apart and issues their
+// independent loads (slot, key, then the filter words) before it resolves
+// any: an absent key's filter block is one random 64-byte line, so as in
+// k_pull_lr16 memory-level parallelism is what matters.
+constexpr int kAdmitItems = 2;
+constexpr int kAdmitChunk = kBlock * kAdmitItems;
 
-void launch_table_pull(const PullArgs& a, hipStream_t st) {
-  if (a.n_max <= 0) return;
+// counter += 1, saturating at 255, by a CAS loop on its aligned 32-bit word
+// (`seen`: a value of the word loaded earlier).  Every adder that finds the
+// counter below 255 adds exactly 1 and one at 255 adds nothing, so the final
+// state is min(255, start + adders) whatever the order.
+__device__ __forceinline__ void admit_bump(u32* __restrict__ word, int shift, u32 seen) {
+  while (((seen >> shift) & 0xFFu) != 0xFFu) {
+    const u32 prev = atomicCAS(word, seen, seen + (1u << shift));
+    if (prev == seen) break;
+    seen = prev;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_admit_count(AdmitView av,
+                                                        const u64* __restrict__ keys,
+                                                        const int64_t* n_dev, int64_t n_host,
+                                                        int64_t n_max,
+                                                        const u32* __restrict__ slots) {
+  const int64_t n = dev_count(n_dev, n_host, n_max);
+  if ((int64_t)blockIdx.x * kAdmitChunk >= n) return;  // (grid sized by capacity)
+  u32* words = reinterpret_cast<u32*>(av.counters);
+  const int64_t base = (int64_t)blockIdx.x * kAdmitChunk + threadIdx.x;
+  bool on[kAdmitItems];
+  AdmitPos pos[kAdmitItems];
+  u32 w0[kAdmitItems], w1[kAdmitItems];
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    const int64_t i = base + (int64_t)j * kBlock;
+    on[j] = i < n && slots[i] == kNoSlot;
+    pos[j] = admit_pos(on[j] ? sanitize_key(keys[i]) : 0ull, av.log2);
+  }
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    if (!on[j]) continue;
+    w0[j] = words[pos[j].c0 >> 2];
+    w1[j] = words[pos[j].c1 >> 2];
+  }
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    if (!on[j]) continue;
+    admit_bump(words + (pos[j].c0 >> 2), (int)(pos[j].c0 & 3u) * 8, w0[j]);
+    // (the two counters may share a word: the second loop's first compare
+    // then fails once and continues from the word it finds)
+    admit_bump(words + (pos[j].c1 >> 2), (int)(pos[j].c1 & 3u) * 8, w1[j]);
+  }
+}
+
+// Phase 3.  Runs after every increment of the call (a launch of its own):
+// all entries of one key read the same two counters and decide alike.  An
+// admitted key is inserted by the table's CAS probe; entries of one key get
+// one slot.  The overflow flag is set only by an admitted key that finds no
+// slot within probe_limit (probe); an unadmitted entry keeps kNoSlot.
+__global__ void __launch_bounds__(kBlock) k_admit_insert(TableView t, AdmitView av,
+                                                         const u64* __restrict__ keys,
+                                                         const int64_t* n_dev, int64_t n_host,
+                                                         int64_t n_max, u32* __restrict__ slots) {
+  const int64_t n = dev_count(n_dev, n_host, n_max);
+  if ((int64_t)blockIdx.x * kAdmitChunk >= n) return;  // (grid sized by capacity)
+  const int64_t base = (int64_t)blockIdx.x * kAdmitChunk + threadIdx.x;
+  bool on[kAdmitItems];
+  u64 key[kAdmitItems];
+  AdmitPos pos[kAdmitItems];
+  unsigned int c0[kAdmitItems], c1[kAdmitItems];
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    const int64_t i = base + (int64_t)j * kBlock;
+    on[j] = i < n && slots[i] == kNoSlot;
+    key[j] = on[j] ? sanitize_key(keys[i]) : 0ull;
+    pos[j] = admit_pos(key[j], av.log2);
+  }
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    if (!on[j]) continue;
+    c0[j] = av.counters[pos[j].c0];
+    c1[j] = av.counters[pos[j].c1];
+  }
+  unsigned int claims = 0;
+#pragma unroll
+  for (int j = 0; j < kAdmitItems; ++j) {
+    if (!on[j]) continue;
+    if ((int)(c0[j] < c1[j] ? c0[j] : c1[j]) < av.min_count) continue;
+    bool claimed = false;
+    slots[base + (int64_t)j * kBlock] = probe(t, key[j], true, claimed);
+    claims += claimed;
+  }
+  block_count_add<kBlock>(t.size, claims);
+}
+
+static void launch_admit(const PullArgs& a, hipStream_t st) {
+  if (a.admit.log2 < kAdmitBlockLog2 || a.admit.log2 > kAdmitMaxLog2)
+    throw std::runtime_error("table_pull: admit log2");
+  const int64_t nm = a.n_dev ? a.n_max : a.n_host;
+  const int g = (int)((nm + kAdmitChunk - 1) / kAdmitChunk);
+  hipLaunchKernelGGL(k_admit_count, dim3(g > 0 ? g : 1), dim3(kBlock), 0, st, a.admit, a.keys,
+                     a.n_dev, a.n_host, a.n_max, a.out_slot);
+  hipLaunchKernelGGL(k_admit_insert, dim3(g > 0 ? g : 1), dim3(kBlock), 0, st, a.table, a.admit,
+                     a.keys, a.n_dev, a.n_host, a.n_max, a.out_slot);
+}
+
+void launch_table_pull(const PullArgs& a0, hipStream_t st) {
+  if (a0.n_max <= 0) return;
+  // admission: the kernels below only look up (present keys get their slot
+  // and values; an absent key's values are those of a fresh slot already),
+  // then the two admission kernels count and insert the absent entries
+  const bool admit = a0.insert && a0.admit.counters != nullptr;
+  PullArgs a = a0;
+  if (admit) a.insert = false;
+  if (admit && !a.out_slot) throw std::runtime_error("table_pull: admission needs out_slot");
   const TableLayout& L = a.table.L;
   int grid = grid_for(a.n_dev ? a.n_max : a.n_host);
   if (L.stride == 4 && L.P == 1 && L.opt == kFTRL && !L.has_flag) {
@@ -977,6 +1092,7 @@ void launch_table_pull(const PullArgs& a, hipStream_t st) {
     if (a.fm_vals || a.out_w) throw std::runtime_error("table_pull: fm_vals/out_w need the group path");
     hipLaunchKernelGGL(k_pull_generic, dim3(grid), dim3(kBlock), 0, st, a);
   }
+  if (admit) launch_admit(a0, st);
   XF_HIP_CHECK(hipGetLastError());
 }
 

@@ -341,8 +341,24 @@ constexpr int kFmGroupRows = 1024;  // rows per reference-FM workgroup on the re
 constexpr int kFmStdMinGroupRows = 128;
 constexpr int kMvmGroupRows = 512;  // rows per MVM forward workgroup on the reduction path (k_mvm2: T rows)
 
+// Feature admission: the engine's blocked counting filter of 8-bit saturating
+// counters (admit_pos, common.h).  With counters set, an inserting pull runs
+// in three phases, each complete before the next: (1) probe without insert
+// (present keys finish here and never touch the filter); (2) every absent
+// entry adds 1 to both of its counters, saturating at 255; (3) every absent
+// entry reads both counters -- their state after ALL of the call's increments
+// -- and inserts its key iff min(c0, c1) >= min_count, else its slot stays
+// "absent" and no overflow is flagged for it.  The decision depends only on
+// the set of entries, never on their order.  Null counters: a plain pull.
+struct AdmitView {
+  unsigned char* counters = nullptr;  // [2^log2]
+  int log2 = 0;
+  int min_count = 1;
+};
+
 struct PullArgs {
   TableView table;
+  AdmitView admit;                 // (ignored unless insert)
   OptSpec opt;
   const u64* keys = nullptr;
   const int64_t* n_dev = nullptr;  // count (device) or null => n_host

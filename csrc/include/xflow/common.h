@@ -53,6 +53,31 @@ XF_HD u32 owner_of(u64 key, u32 world) {
   return world <= 1 ? 0u : (u32)((fmix64(key) >> 32) % world);
 }
 
+// Feature admission (EngineConfig::admit_min_count, docs/DESIGN.md §2): where
+// a key counts its sightings in the blocked counting filter of 2^log2 bytes.
+// One fmix64 of the key, salted so that it is independent of the key's table
+// home and owner, gives from disjoint bits two distinct byte offsets inside
+// one 64-byte block (bits 0-5 and 6-11; equal offsets: the second is the
+// first ^ 1) and the block (bits 12 and up).  An absent key costs one random
+// line.  Mirrored in xflow_amd/testing/hashing.py.
+constexpr u64 kAdmitSalt = 0xa0761d6478bd642full;
+constexpr int kAdmitBlockLog2 = 6;
+constexpr int kAdmitMaxLog2 = 32;
+struct AdmitPos {
+  u64 c0, c1;  // byte indices of the key's two counters
+};
+XF_HD AdmitPos admit_pos(u64 key, int log2_bytes) {
+  const u64 h = fmix64(key ^ kAdmitSalt);
+  const u64 o0 = h & 63u;
+  u64 o1 = (h >> 6) & 63u;
+  if (o1 == o0) o1 = o0 ^ 1u;
+  const u64 block = (h >> 12) & ((1ull << (log2_bytes - kAdmitBlockLog2)) - 1);
+  AdmitPos p;
+  p.c0 = (block << kAdmitBlockLog2) | o0;
+  p.c1 = (block << kAdmitBlockLog2) | o1;
+  return p;
+}
+
 // Reference sigmoid: clamp at |x|>30, otherwise e^x/(1+e^x) evaluated in
 // double with the literal base 2.718281828 (base.h:54-63).
 XF_HD float sigmoid_ref(float x) {

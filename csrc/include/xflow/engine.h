@@ -64,6 +64,20 @@ struct EngineConfig {
   // (the same pushes, dense per-group buffers; also what a slice count the
   // CSR dests cannot address falls back to)
   bool csr = true;
+  // Feature admission (McMahan et al. 2013, §4 "probabilistic feature
+  // inclusion"; AdmitView, backend.h): a training pull inserts a key only
+  // once a blocked counting filter in front of the table has seen it
+  // admit_min_count times (1..255; 1 = off: every pull inserts, no filter
+  // exists).  A sighting is one entry of an inserting training pull
+  // (train_step: the step's unique keys; s_pull: every received entry) whose
+  // key is not in the table.  Until then the key reads its absent weight and
+  // its gradient is dropped.  Lookups (eval_step, pull_host, s_pull without
+  // insert) neither count nor consult the filter; push_host, import and
+  // prefill insert regardless of it.  admit_log2: log2 of the filter's bytes
+  // (6..32), 0 = min(32, the table's largest log2 capacity + 1).  The filter
+  // is allocated once and never grows.
+  int admit_min_count = 1;
+  int admit_log2 = 0;
 };
 
 // What the single-rank step's gradient layout depends on (Engine::step_inputs)
@@ -243,6 +257,17 @@ class Engine {
   // (tests / debugging; syncs)
   void csr_debug(std::vector<u32>& off, std::vector<u32>& cnt, std::vector<u32>& words);
   int64_t table_splits() const { return splits_; }
+  // feature admission: the filter's bytes (0: off) and log2 of them, the
+  // estimates min(c0, c1) of keys' sightings, the whole filter to / from
+  // host memory of admit_bytes() bytes (checkpoints), and the slots a server
+  // buffer's last s_pull recorded (tests / diagnostics).  All but the first
+  // two sync.
+  size_t admit_bytes() const { return admit_.counters ? (size_t)1 << admit_.log2 : 0; }
+  int admit_log2() const { return admit_.counters ? admit_.log2 : 0; }
+  std::vector<uint8_t> admit_counts(const std::vector<u64>& keys);
+  void admit_export(uint8_t* dst);
+  void admit_import(const uint8_t* src);
+  std::vector<u32> server_slots(int buf);
   // geometry: {segment slots log2, level, split, segments}
   std::vector<int64_t> table_geometry() const {
     return {table_.seg_log2, table_.level, (int64_t)table_.split,
@@ -387,6 +412,7 @@ class Engine {
   EngineConfig cfg_;
   std::unique_ptr<Backend> be_;
   TableView table_;
+  AdmitView admit_;              // counters == null: admission off
   size_t table_bytes_ = 0;
   ScratchView scratch_;
 

@@ -39,6 +39,8 @@ struct TrainerConfig {
   std::string pred_dir = ".";
   int device = -1;                 // -1 CPU backend, >=0 HIP device
   int table_log2_cap = 22;
+  int admit_min_count = 1;         // EngineConfig::admit_min_count / admit_log2
+  int admit_log2 = 0;
   ModelSpec model_spec;            // v_dim, math modes (kind is taken from `model`)
   OptSpec opt;
   bool sum_slices = false;

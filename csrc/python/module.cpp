@@ -388,8 +388,11 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def(py::init([](py::dict model, py::dict opt, int table_log2_cap, int64_t max_rows,
                        int64_t max_nnz, int max_slices, bool sum_slices, double scratch_factor,
                        int device, bool table_grow, double grow_load, int max_log2_cap,
-                       int monitor_lag, int owner_group, double grow_start, bool csr) {
+                       int monitor_lag, int owner_group, double grow_start, bool csr,
+                       int admit_min_count, int admit_log2) {
              EngineConfig c;
+             c.admit_min_count = admit_min_count;
+             c.admit_log2 = admit_log2;
              c.owner_group = owner_group;
              c.csr = csr;
              c.table_grow = table_grow;
@@ -414,7 +417,34 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("scratch_factor") = 2.5, py::arg("device") = -1,
            py::arg("table_grow") = true, py::arg("grow_load") = 0.8, py::arg("max_log2_cap") = 0,
            py::arg("monitor_lag") = 2, py::arg("owner_group") = 0, py::arg("grow_start") = 0.6,
-           py::arg("csr") = true)
+           py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0)
+      .def_property_readonly("admit_bytes", &Engine::admit_bytes)
+      .def_property_readonly("admit_log2", &Engine::admit_log2)
+      .def("admit_counts",
+           [](Engine& e, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> keys) {
+             std::vector<u64> k(keys.data(), keys.data() + keys.size());
+             return to_np(e.admit_counts(k));
+           })
+      .def("admit_export",
+           [](Engine& e) {
+             py::array_t<uint8_t> a((py::ssize_t)e.admit_bytes());
+             uint8_t* p = a.mutable_data();
+             {
+               py::gil_scoped_release nogil;
+               e.admit_export(p);
+             }
+             return a;
+           })
+      .def("admit_import",
+           [](Engine& e, py::array_t<uint8_t, py::array::c_style | py::array::forcecast> a) {
+             if ((size_t)a.size() != e.admit_bytes())
+               throw std::invalid_argument("admit_import: size mismatch");
+             const uint8_t* p = a.data();
+             py::gil_scoped_release nogil;
+             e.admit_import(p);
+           })
+      .def("server_slots", [](Engine& e, int buf) { return to_np(e.server_slots(buf)); },
+           py::arg("buf") = 0)
       .def_property_readonly("table_growths", &Engine::table_growths)
       .def_property_readonly("csr_steps", &Engine::csr_steps)
       .def("step_plan", [](const Engine& e, int S) { return plan_dict(e.plan(S)); })
@@ -746,6 +776,8 @@ PYBIND11_MODULE(_xflow_native, m) {
         if (d.contains("pred_dir")) c.pred_dir = d["pred_dir"].cast<std::string>();
         if (d.contains("device")) c.device = d["device"].cast<int>();
         if (d.contains("table_log2_cap")) c.table_log2_cap = d["table_log2_cap"].cast<int>();
+        if (d.contains("admit_min_count")) c.admit_min_count = d["admit_min_count"].cast<int>();
+        if (d.contains("admit_log2")) c.admit_log2 = d["admit_log2"].cast<int>();
         if (d.contains("sum_slices")) c.sum_slices = d["sum_slices"].cast<bool>();
         if (d.contains("verbose")) c.verbose = d["verbose"].cast<bool>();
         if (d.contains("model_spec")) c.model_spec = model_from(d["model_spec"].cast<py::dict>());

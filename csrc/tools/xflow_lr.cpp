@@ -8,7 +8,8 @@
 // (python -m xflow_amd.cli, scripts/local.sh), which maps workers to GPUs.
 // Optional flags after the positional args: --threads N --device D
 // --serial-slices --keep-remainder --sgd --fm-standard --mvm-fixed
-// --mvm-predict-compat --v-dim D --log2-cap N --save PATH --load PATH.
+// --mvm-predict-compat --v-dim D --log2-cap N --admit-min-count N
+// --admit-log2 N --save PATH --load PATH.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -59,6 +60,8 @@ int main(int argc, char* argv[]) {
     else if (a == "--mvm-predict-compat") cfg.mvm_predict_compat = true;
     else if (a == "--v-dim") cfg.model_spec.v_dim = std::atoi(next());
     else if (a == "--log2-cap") cfg.table_log2_cap = std::atoi(next());
+    else if (a == "--admit-min-count") cfg.admit_min_count = std::atoi(next());
+    else if (a == "--admit-log2") cfg.admit_log2 = std::atoi(next());
     else if (a == "--train-block-bytes") cfg.train_block_bytes = std::atoll(next());
     else if (a == "--save") save = next();
     else if (a == "--load") load = next();

@@ -6,6 +6,10 @@ Layout of ``<dir>/``:
   meta.json                      model/optimizer config, world size, epoch, step
   shard-<rank>-of-<world>.xftb   native binary shard (csrc/engine/engine.cpp
                                  Engine::save): header + keys + state words
+  admit-<rank>-of-<world>.xfad   only with feature admission on
+                                 (EngineConfig.admit_min_count > 1): the rank's
+                                 counting filter, its raw bytes; meta.json then
+                                 also records admit_min_count and admit_log2
 
 Resume is world-size agnostic: with the same world size each rank loads its
 own shard; otherwise every rank scans all shards and imports exactly the keys
@@ -22,6 +26,7 @@ from __future__ import annotations
 import dataclasses
 import glob
 import json
+import logging
 import os
 import shutil
 import struct
@@ -34,9 +39,15 @@ from xflow_amd.testing.hashing import owner_of
 
 MAGIC = b"XFLOWTB1"
 
+log = logging.getLogger(__name__)
+
 
 def shard_name(rank: int, world: int) -> str:
     return f"shard-{rank:05d}-of-{world:05d}.xftb"
+
+
+def admit_name(rank: int, world: int) -> str:
+    return f"admit-{rank:05d}-of-{world:05d}.xfad"
 
 
 def shard_keys(path: str) -> int:
@@ -98,11 +109,22 @@ def save(engine, ckpt_dir: str, rank: int, world: int, meta: Optional[dict] = No
     engine.save(tmp)
     _fsync_file(tmp)
     os.replace(tmp, path)
+    admit = engine.admit_bytes() > 0
+    if admit:  # the admission filter next to the shard
+        apath = os.path.join(ckpt_dir, admit_name(rank, world))
+        with open(apath + ".tmp", "wb") as f:
+            engine.admit_export().tofile(f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(apath + ".tmp", apath)
     (barrier or _default_barrier)()
     if rank == 0:
         m = dict(meta or {})
         m.update(world=world, model=dataclasses.asdict(engine.model),
                  optim=dataclasses.asdict(engine.optim))
+        if admit:
+            m.update(admit_min_count=int(engine.cfg.admit_min_count),
+                     admit_log2=int(engine.admit_log2))
         mtmp = os.path.join(ckpt_dir, "meta.json.tmp")
         with open(mtmp, "w") as f:
             json.dump(m, f, indent=1)
@@ -154,10 +176,28 @@ def load_meta(ckpt_dir: str) -> dict:
         return json.load(f)
 
 
+def _load_admit(engine, ckpt_dir: str, rank: int, world: int, meta: dict) -> None:
+    """Restore the admission filter when the checkpoint holds one of this
+    world size and filter size; otherwise the filter starts empty (a filter is
+    not resharded or resized) and the log says what that costs."""
+    if engine.admit_bytes() == 0:
+        return
+    path = os.path.join(ckpt_dir, admit_name(rank, world))
+    if (int(meta["world"]) == world and int(meta.get("admit_log2", 0)) == engine.admit_log2
+            and os.path.exists(path)):
+        engine.admit_import(np.fromfile(path, dtype=np.uint8))
+        return
+    log.warning("checkpoint %s: no admission filter for world %d / admit_log2 %d (saved: world "
+                "%s, admit_log2 %s); the filter starts empty, so keys not yet admitted need "
+                "their sightings again", ckpt_dir, world, engine.admit_log2, meta.get("world"),
+                meta.get("admit_log2"))
+
+
 def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
     meta = load_meta(ckpt_dir)
     check_compatible(engine, meta)
     saved_world = int(meta["world"])
+    _load_admit(engine, ckpt_dir, rank, world, meta)
     if saved_world == world:
         engine.load(os.path.join(ckpt_dir, shard_name(rank, world)))
         return meta

@@ -60,6 +60,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="growth limit 2^N slots per rank (0: 2^31, or what free HBM allows)")
     ap.add_argument("--no-table-grow", action="store_true",
                     help="fixed table capacity: an overflow raises within two steps")
+    ap.add_argument("--admit-min-count", type=int, default=1,
+                    help="feature admission: a key enters the table only after a counting filter "
+                         "has seen it N times in training pulls (1..255; 1: off)")
+    ap.add_argument("--admit-log2", type=int, default=0,
+                    help="admission filter bytes per rank = 2^N (6..32; 0: min(32, the table's "
+                         "largest log2 capacity + 1))")
     ap.add_argument("--train-block-bytes", type=int, default=2 << 20)
     ap.add_argument("--test-block-bytes", type=int, default=0)
     ap.add_argument("--gpu-parse", action="store_true",
@@ -109,7 +115,8 @@ def config_from_args(a) -> TrainConfig:
         optim=OptimConfig(kind=a.optimizer, alpha=a.alpha, beta=a.beta, lambda1=a.lambda1,
                           lambda2=a.lambda2, lr=a.lr),
         engine=EngineConfig(table_log2_cap=a.log2_cap, sum_slices=a.sum_slices,
-                            max_log2_cap=a.max_log2_cap, table_grow=not a.no_table_grow))
+                            max_log2_cap=a.max_log2_cap, table_grow=not a.no_table_grow,
+                            admit_min_count=a.admit_min_count, admit_log2=a.admit_log2))
 
 
 def main(argv=None) -> int:

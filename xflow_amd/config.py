@@ -104,6 +104,12 @@ class EngineConfig:
     # several slices on the GPU (LR-FTRL, reference FM): CSR gradients of the
     # touched (key, slice) pairs; False: slice groups of 32 (same pushes)
     csr: bool = True
+    # feature admission: a training pull inserts a key only after a counting
+    # filter has seen it admit_min_count times (1..255; 1: off, no filter).
+    # admit_log2: log2 of the filter's bytes, 0 = min(32, the table's largest
+    # log2 capacity + 1).  csrc/include/xflow/engine.h, docs/DESIGN.md §2
+    admit_min_count: int = 1
+    admit_log2: int = 0
 
 
 @dataclass

@@ -143,7 +143,9 @@ class Engine:
                            device=_device_index(self.device), table_grow=self.cfg.table_grow,
                            grow_load=self.cfg.grow_load, max_log2_cap=self.cfg.max_log2_cap,
                            monitor_lag=self.cfg.monitor_lag, owner_group=self.cfg.owner_group,
-                           grow_start=self.cfg.grow_start, csr=self.cfg.csr)
+                           grow_start=self.cfg.grow_start, csr=self.cfg.csr,
+                           admit_min_count=self.cfg.admit_min_count,
+                           admit_log2=self.cfg.admit_log2)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -237,6 +239,38 @@ class Engine:
         at the occupancy a long run reaches (untimed benchmark setup)."""
         self._sync_stream()
         self._e.prefill(int(n), int(seed))
+
+    # ---- feature admission (EngineConfig.admit_min_count) -------------------
+    def admit_bytes(self) -> int:
+        """Bytes of the admission filter (0: admission off)."""
+        return int(self._e.admit_bytes)
+
+    @property
+    def admit_log2(self) -> int:
+        """log2 of the filter's bytes as allocated (0: admission off)."""
+        return int(self._e.admit_log2)
+
+    def admit_counts(self, keys) -> np.ndarray:
+        """The filter's estimate of each key's sightings, min of its two
+        counters (uint8, saturating at 255; zeros with admission off).  A
+        small synchronising call for tests and diagnostics."""
+        self._sync_stream()
+        return self._e.admit_counts(np.ascontiguousarray(keys, dtype=np.uint64))
+
+    def admit_export(self) -> np.ndarray:
+        """A host copy of the whole filter (uint8 [admit_bytes()])."""
+        self._sync_stream()
+        return self._e.admit_export()
+
+    def admit_import(self, counters: np.ndarray) -> None:
+        self._sync_stream()
+        self._e.admit_import(np.ascontiguousarray(counters, dtype=np.uint8))
+
+    def server_slots(self, buf: int = 0) -> np.ndarray:
+        """Table slots the last s_pull into server buffer ``buf`` recorded
+        (0xFFFFFFFF: no slot); synchronising, for tests."""
+        self._sync_stream()
+        return self._e.server_slots(int(buf))
 
     def pull(self, keys) -> np.ndarray:
         k = np.asarray(keys, dtype=np.uint64)

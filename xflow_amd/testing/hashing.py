@@ -5,7 +5,7 @@ the test oracles so they do not depend on the code under test.
   ``_Hash_bytes(ptr, len, seed=0xc70f6907)``, MurmurHash64A-style.  The
   reference keys every feature with it (src/io/io.h:53,
   load_data_from_disk.cc:154).
-* ``fmix64`` / ``normal_init``: csrc/include/xflow/common.h.
+* ``fmix64`` / ``normal_init`` / ``admit_pos``: csrc/include/xflow/common.h.
 """
 from __future__ import annotations
 
@@ -83,3 +83,25 @@ def normal_init(keys: np.ndarray, dim: int, seed: int = 0x5EED) -> np.ndarray:
     u2 = (b >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
     r = np.sqrt(np.float32(-2.0) * np.log(u1))
     return (r * np.cos(np.float32(6.283185307179586) * u2)).astype(np.float32)
+
+
+ADMIT_SALT = 0xA0761D6478BD642F
+
+
+def sanitize_keys(keys: np.ndarray) -> np.ndarray:
+    k = np.asarray(keys, dtype=np.uint64).copy()
+    k[k == np.uint64(M64)] = np.uint64(M64 - 1)
+    return k
+
+
+def admit_pos(keys: np.ndarray, log2_bytes: int):
+    """Byte indices (c0, c1) of each key's two counters in the admission
+    filter of 2^log2_bytes bytes (common.h admit_pos): one 64-byte block, two
+    distinct offsets, from disjoint bits of one salted fmix64."""
+    h = fmix64(sanitize_keys(keys) ^ np.uint64(ADMIT_SALT))
+    o0 = h & np.uint64(63)
+    o1 = (h >> np.uint64(6)) & np.uint64(63)
+    o1 = np.where(o1 == o0, o0 ^ np.uint64(1), o1)
+    block = (h >> np.uint64(12)) & np.uint64((1 << (log2_bytes - 6)) - 1)
+    base = block << np.uint64(6)
+    return (base | o0).astype(np.int64), (base | o1).astype(np.int64)

@@ -357,6 +357,8 @@ class Trainer:
                        table_capacity=self.table.table_capacity,
                        table_growths=self.table.table_growths,
                        monitor_waits=self.table.monitor_waits)
+            if cfg.engine.admit_min_count > 1:
+                rec["admit_min_count"] = cfg.engine.admit_min_count
             if aps is not None:
                 rec["async_ps"] = {k: v for k, v in aps.stats().items()
                                    if k in ("max_staleness", "max_lead", "bytes_moved",
@@ -396,6 +398,8 @@ class Trainer:
         rate = ep_samples / max(time.perf_counter() - t0, 1e-9)
         rec = dict(event="progress", epoch=self.epoch, step=self.steps, samples_per_s=rate,
                    unique_keys=self.engine.n_unique())
+        if self.cfg.engine.admit_min_count > 1:
+            rec["admit_min_count"] = self.cfg.engine.admit_min_count
         if self.sharded is not None:
             rec["a2a_bytes"] = self.sharded.bytes_moved
         self.metrics.log(**rec)
