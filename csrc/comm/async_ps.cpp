@@ -131,13 +131,13 @@ AsyncPS::AsyncPS(Engine& worker, Engine& server, const Config& c)
   win_ = c_.device >= 0 ? make_ipc_window(win, W_, c_.rank, c_.device)
                         : make_shm_window(win, W_, c_.rank, c_.name);
   Backend& be = wk_.backend();
-  counts_d_ = static_cast<int64_t*>(be.alloc(sizeof(int64_t) * W_));
-  tot_d_ = static_cast<int64_t*>(be.alloc(sizeof(int64_t) * W_));
-  counts_h_ = static_cast<int64_t*>(be.host_alloc(sizeof(int64_t) * W_));
-  tot_h_ = static_cast<int64_t*>(be.host_alloc(sizeof(int64_t) * W_));
-  keys_d_ = static_cast<u64*>(be.alloc(sizeof(u64) * (size_t)nnz));
-  cnt_d_ = static_cast<u32*>(be.alloc(sizeof(u32) * (size_t)nnz));
-  pay_d_ = be.alloc(csr_ ? (size_t)eb_ * nnz : 4 * (size_t)S * gw_ * nnz);
+  counts_d_.alloc(be, W_);
+  tot_d_.alloc(be, W_);
+  counts_h_.alloc(be, W_);
+  tot_h_.alloc(be, W_);
+  keys_d_.alloc(be, (size_t)nnz);
+  cnt_d_.alloc(be, (size_t)nnz);
+  pay_d_.alloc(be, csr_ ? (size_t)eb_ * nnz : 4 * (size_t)S * gw_ * nnz);
   wev_ = be.event_create();
   srv_stream_ = sv_.backend().stream();
   served_.assign(W_, -1);
@@ -151,13 +151,6 @@ AsyncPS::~AsyncPS() {
   if (thr_.joinable()) thr_.join();
   Backend& be = wk_.backend();
   be.synchronize();
-  be.free(counts_d_);
-  be.free(tot_d_);
-  be.free(keys_d_);
-  be.free(cnt_d_);
-  be.free(pay_d_);
-  be.host_free(counts_h_);
-  be.host_free(tot_h_);
   be.event_destroy(wev_);
   delete ctl_;
 }
@@ -359,19 +352,19 @@ bool AsyncPS::step(const BatchView& b, float* pctr, bool train) {
     for (int o = 0; o < W_; ++o) {
       if (n[o]) be.copy_d2d(in_cnt(win_->peer(o), me, slot), cnt_d_ + off[o], sizeof(u32) * n[o]);
       if (e[o])
-        be.copy_d2d(in_pay(win_->peer(o), me, slot), static_cast<char*>(pay_d_) + (size_t)eb_ * eo,
+        be.copy_d2d(in_pay(win_->peer(o), me, slot), pay_d_ + (size_t)eb_ * eo,
                     (size_t)eb_ * e[o]);
       eo += e[o];
       moved += 4 * n[o] + (int64_t)eb_ * e[o];
     }
   } else {
     const int row = S * gw_;
-    wk_.w_forward_backward(b, pulled, n_send, static_cast<float*>(pay_d_), masks_ ? cnt_d_ : nullptr,
+    wk_.w_forward_backward(b, pulled, n_send, reinterpret_cast<float*>(pay_d_.get()), masks_ ? cnt_d_.get() : nullptr,
                            S, 0, 0);
     for (int o = 0; o < W_; ++o) {
       e[o] = n[o];
       if (!n[o]) continue;
-      be.copy_d2d(in_pay(win_->peer(o), me, slot), static_cast<float*>(pay_d_) + off[o] * row,
+      be.copy_d2d(in_pay(win_->peer(o), me, slot), reinterpret_cast<float*>(pay_d_.get()) + off[o] * row,
                   sizeof(float) * row * n[o]);
       if (masks_) be.copy_d2d(in_cnt(win_->peer(o), me, slot), cnt_d_ + off[o], sizeof(u32) * n[o]);
       moved += (4 * (int64_t)row + (masks_ ? 4 : 0)) * n[o];

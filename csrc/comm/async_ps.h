@@ -128,13 +128,11 @@ class AsyncPS {
   bool connected_ = false;
   // worker state
   int64_t seq_ = 0;  // next request number (training and eval steps)
-  int64_t* counts_d_ = nullptr;
-  int64_t* counts_h_ = nullptr;
-  int64_t* tot_d_ = nullptr;
-  int64_t* tot_h_ = nullptr;
-  u64* keys_d_ = nullptr;
-  u32* cnt_d_ = nullptr;
-  void* pay_d_ = nullptr;
+  DeviceBuffer<int64_t> counts_d_, tot_d_;
+  HostBuffer<int64_t> counts_h_, tot_h_;
+  DeviceBuffer<u64> keys_d_;
+  DeviceBuffer<u32> cnt_d_;
+  DeviceBuffer<char> pay_d_;  // gradient rows (float) or CSR entries
   void* wev_ = nullptr;
   // server state (kept across stop / start): per source the last step
   // whose pull was served / whose push was applied, and per (source, slot)

@@ -18,10 +18,10 @@ ShardedStep::ShardedStep(Engine& e, RcclComm* comm, int world, int rank, bool ea
     const int nbuf = staleness + 1;  // step t's buffers live until its apply at step t+k
     rk_.resize(nbuf);
     vals_k_.resize(nbuf);
-    gin_k_.assign(nbuf, std::vector<Buf>(1));
-    gout_k_.assign(nbuf, std::vector<Buf>(1));
-    min_k_.assign(nbuf, std::vector<Buf>(1));
-    mout_k_.assign(nbuf, std::vector<Buf>(1));
+    for (auto* vv : {&gin_k_, &gout_k_, &min_k_, &mout_k_}) {
+      vv->resize(nbuf);
+      for (auto& v : *vv) v.resize(1);
+    }
   }
   if (world < 1 || rank < 0 || rank >= world) throw std::invalid_argument("ShardedStep: bad world/rank");
   if (!comm && world != 1)
@@ -31,59 +31,25 @@ ShardedStep::ShardedStep(Engine& e, RcclComm* comm, int world, int rank, bool ea
   Backend& be = e_.backend();
   const int64_t nnz = e_.config().max_nnz > 0 ? e_.config().max_nnz : 1;
   for (int i = 0; i < 2; ++i) {
-    counts_both_[i] = static_cast<int64_t*>(be.alloc(sizeof(int64_t) * 2 * world_));
-    be.memset(counts_both_[i], 0, sizeof(int64_t) * 2 * world_);
-    send_keys_[i] = static_cast<u64*>(be.alloc(sizeof(u64) * (size_t)nnz));
-    counts_host_[i] = static_cast<int64_t*>(be.host_alloc(sizeof(int64_t) * 2 * world_));
+    counts_both_[i].alloc_zero(be, 2 * (size_t)world_);
+    send_keys_[i].alloc(be, (size_t)nnz);
+    counts_host_[i].alloc(be, 2 * (size_t)world_);
     counts_ready_[i] = be.event_create();
   }
   grads_out_.resize(1);
   grads_in_.resize(1);
   masks_out_.resize(1);
   masks_in_.resize(1);
-  csr_tot_ = static_cast<int64_t*>(be.alloc(sizeof(int64_t) * 2 * world_));
-  csr_tot_host_ = static_cast<int64_t*>(be.host_alloc(sizeof(int64_t) * 2 * world_));
+  csr_tot_.alloc(be, 2 * (size_t)world_);
+  csr_tot_host_.alloc(be, 2 * (size_t)world_);
   csr_tot_ready_ = be.event_create();
 }
 
 ShardedStep::~ShardedStep() {
   Backend& be = e_.backend();
   be.synchronize();
-  for (int i = 0; i < 2; ++i) {
-    be.free(counts_both_[i]);
-    be.free(send_keys_[i]);
-    be.host_free(counts_host_[i]);
-    be.event_destroy(counts_ready_[i]);
-  }
-  be.free(csr_tot_);
-  be.host_free(csr_tot_host_);
+  for (void* ev : counts_ready_) be.event_destroy(ev);
   be.event_destroy(csr_tot_ready_);
-  std::vector<Buf*> all = {&recv_keys_, &vals_, &pulled_, &ahead_keys_[0], &ahead_keys_[1],
-                           &csr_cnt_o_, &csr_cnt_i_, &csr_ent_o_, &csr_ent_i_};
-  for (auto* v : {&grads_out_, &grads_in_, &masks_out_, &masks_in_, &rk_, &vals_k_})
-    for (Buf& b : *v) all.push_back(&b);
-  for (auto* vv : {&gin_k_, &gout_k_, &min_k_, &mout_k_})
-    for (auto& v : *vv)
-      for (Buf& b : v) all.push_back(&b);
-  for (Buf* b : all)
-    if (b->p) be.free_stream(b->p);
-  be.synchronize();
-}
-
-void* ShardedStep::get(Buf& b, size_t bytes) {
-  if (bytes < 256) bytes = 256;
-  if (b.bytes < bytes) {
-    // Stream-ordered: the old buffer is released behind the queued work that
-    // still reads it, the new one is usable by the work queued next -- a
-    // buffer that grows mid-step costs no host wait (no device synchronize)
-    Backend& be = e_.backend();
-    if (b.p) be.free_stream(b.p);
-    const size_t n = bytes + bytes / 4 + 4096;
-    b.p = be.alloc_stream(n);
-    b.bytes = n;
-    ++buffer_growths;
-  }
-  return b.p;
 }
 
 uintptr_t ShardedStep::stream() const {
@@ -252,7 +218,7 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
   } else if (self_only()) {  // world 1: the owner reads the send buffer in place
     recv_keys = send_keys_[sp.wb];
   } else {
-    u64* rk = static_cast<u64*>(get(recv_keys_, sizeof(u64) * (size_t)n_recv));
+    u64* rk = get<u64>(recv_keys_, (size_t)n_recv);
     std::vector<RcclComm::A2AOp> ops(1);
     ops[0] = {send_keys_[sp.wb], sp.send, rk, sp.recv, (int)sizeof(u64)};
     a2a_group(ops);
@@ -260,7 +226,7 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
   }
   const std::vector<int64_t> offsets = offsets_of(sp.recv);
   const int ngroups = Engine::slice_groups(S);
-  float* vals = static_cast<float*>(get(vals_, sizeof(float) * (size_t)(n_recv * ps)));
+  float* vals = get<float>(vals_, (size_t)(n_recv * ps));
   // the CSR exchange applies source by source (s_apply_csr): no owner
   // grouping, and compact FM rows of a later source expand with the pulled
   // weights, not the table's (the earlier sources updated it)
@@ -271,7 +237,7 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
     e_.s_pull(recv_keys, n_recv, vals, true, 0, offsets, ngroups > 1);
   if (prefetch && !prefetched) prefetch();
   const bool alias = self_only();
-  float* pulled = alias ? vals : static_cast<float*>(get(pulled_, sizeof(float) * (size_t)(n_send * ps)));
+  float* pulled = alias ? vals : get<float>(pulled_, (size_t)(n_send * ps));
   std::vector<RcclComm::A2AOp> ops;
   if (!alias) ops.push_back({vals, sp.recv, pulled, sp.send, (int)sizeof(float) * ps});
   if (next) {
@@ -301,8 +267,8 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
     const int Sg = Engine::group_slices(S, k);
     const int Wd = Sg * gw;
     const bool om = ordered_masks && Sg > 1;
-    float* go = static_cast<float*>(get(grads_out_[k], sizeof(float) * (size_t)(n_send * Wd)));
-    u32* mo = om ? static_cast<u32*>(get(masks_out_[k], sizeof(u32) * (size_t)n_send)) : nullptr;
+    float* go = get<float>(grads_out_[k], (size_t)(n_send * Wd));
+    u32* mo = om ? get<u32>(masks_out_[k], (size_t)n_send) : nullptr;
     e_.w_forward_backward(b, pulled, n_send, go, mo, S, sp.wb, k);
     gS.push_back(Sg);
     if (alias) {
@@ -310,8 +276,8 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
       min_.push_back(mo);
       continue;
     }
-    float* gi = static_cast<float*>(get(grads_in_[k], sizeof(float) * (size_t)(n_recv * Wd)));
-    u32* mi = om ? static_cast<u32*>(get(masks_in_[k], sizeof(u32) * (size_t)n_recv)) : nullptr;
+    float* gi = get<float>(grads_in_[k], (size_t)(n_recv * Wd));
+    u32* mi = om ? get<u32>(masks_in_[k], (size_t)n_recv) : nullptr;
     gin.push_back(gi);
     min_.push_back(mi);
     ops.push_back({go, sp.send, gi, sp.recv, (int)sizeof(float) * Wd});
@@ -325,7 +291,7 @@ bool ShardedStep::train_step(const BatchView& b, int64_t id, int S, const BatchV
       Split s2 = take(*next, next_id, true);
       const int64_t n2s = last_send, n2r = last_recv;
       ahead_no_ ^= 1;
-      u64* rk2 = static_cast<u64*>(get(ahead_keys_[ahead_no_], sizeof(u64) * (size_t)n2r));
+      u64* rk2 = get<u64>(ahead_keys_[ahead_no_], (size_t)n2r);
       ops.push_back({send_keys_[s2.wb], s2.send, rk2, s2.recv, (int)sizeof(u64)});
       ahead_.valid = true;
       ahead_.id = next_id;
@@ -372,11 +338,11 @@ void ShardedStep::csr_gradients(const BatchView& b, int S, const Split& sp, cons
   const int eb = e_.csr_entry_bytes();
   // entries <= (key, slice) pairs <= occurrences
   const int64_t emax = std::min<int64_t>(b.nnz, n_send * (int64_t)S);
-  u32* cnt_o = static_cast<u32*>(get(csr_cnt_o_, sizeof(u32) * (size_t)n_send));
-  void* ent_o = get(csr_ent_o_, (size_t)eb * (size_t)(emax > 0 ? emax : 1));
+  u32* cnt_o = get<u32>(csr_cnt_o_, (size_t)n_send);
+  void* ent_o = get<char>(csr_ent_o_, (size_t)eb * (size_t)(emax > 0 ? emax : 1));
   e_.w_forward_backward_csr(b, pulled, n_send, S, sp.wb, true, cnt_o, ent_o, counts_both_[sp.wb],
                             W, W > 1, csr_tot_);
-  u32* cnt_i = static_cast<u32*>(get(csr_cnt_i_, sizeof(u32) * (size_t)n_recv));
+  u32* cnt_i = get<u32>(csr_cnt_i_, (size_t)n_recv);
   std::vector<RcclComm::A2AOp> ops;
   ops.push_back({cnt_o, sp.send, cnt_i, sp.recv, (int)sizeof(u32)});
   RcclComm::A2AOp tot;
@@ -392,7 +358,7 @@ void ShardedStep::csr_gradients(const BatchView& b, int S, const Split& sp, cons
     Split s2 = take(*next, next_id, true);
     const int64_t n2s = last_send, n2r = last_recv;
     ahead_no_ ^= 1;
-    u64* rk2 = static_cast<u64*>(get(ahead_keys_[ahead_no_], sizeof(u64) * (size_t)n2r));
+    u64* rk2 = get<u64>(ahead_keys_[ahead_no_], (size_t)n2r);
     ops.push_back({send_keys_[s2.wb], s2.send, rk2, s2.recv, (int)sizeof(u64)});
     ahead_.valid = true;
     ahead_.id = next_id;
@@ -424,7 +390,7 @@ void ShardedStep::csr_gradients(const BatchView& b, int S, const Split& sp, cons
     ein += er[r];
   }
   if (eout > emax) throw std::runtime_error("CSR exchange: more entries than (key, slice) pairs");
-  void* ent_i = get(csr_ent_i_, (size_t)eb * (size_t)(ein > 0 ? ein : 1));
+  void* ent_i = get<char>(csr_ent_i_, (size_t)eb * (size_t)(ein > 0 ? ein : 1));
   ops.clear();
   ops.push_back({ent_o, es, ent_i, er, eb});
   a2a_group(ops);
@@ -472,7 +438,7 @@ bool ShardedStep::train_step_async(const BatchView& b, int64_t id, int S, const 
   const int64_t n_send = last_send, n_recv = last_recv;
   const bool alias = self_only();
   // this step's received keys stay alive until its pushes are applied
-  u64* rk = static_cast<u64*>(get(rk_[buf], sizeof(u64) * (size_t)n_recv));
+  u64* rk = get<u64>(rk_[buf], (size_t)n_recv);
   std::vector<RcclComm::A2AOp> ops;
   ops.push_back({send_keys_[sp.wb], sp.send, rk, sp.recv, (int)sizeof(u64)});
   const bool due = (int)pending_.size() == staleness_;
@@ -480,11 +446,11 @@ bool ShardedStep::train_step_async(const BatchView& b, int64_t id, int S, const 
   a2a_group(ops);
   if (due) ++p2p_ops;
   const std::vector<int64_t> offsets = offsets_of(sp.recv);
-  float* vals = static_cast<float*>(get(vals_k_[buf], sizeof(float) * (size_t)(n_recv * ps)));
+  float* vals = get<float>(vals_k_[buf], (size_t)(n_recv * ps));
   // (applied after the next k pulls: keep the pulled weights)
   e_.s_pull(rk, n_recv, vals, true, buf, offsets, true);
   if (prefetch && !prefetched) prefetch();
-  float* pulled = alias ? vals : static_cast<float*>(get(pulled_, sizeof(float) * (size_t)(n_send * ps)));
+  float* pulled = alias ? vals : get<float>(pulled_, (size_t)(n_send * ps));
   ops.clear();
   if (!alias) ops.push_back({vals, sp.recv, pulled, sp.send, (int)sizeof(float) * ps});
   if (next) {
@@ -506,14 +472,14 @@ bool ShardedStep::train_step_async(const BatchView& b, int64_t id, int S, const 
     const int Sg = Engine::group_slices(S, k);
     const int Wd = Sg * gw;
     const bool om = ordered_masks && Sg > 1;
-    float* go = static_cast<float*>(get(gout_k_[buf][k], sizeof(float) * (size_t)(n_send * Wd)));
-    u32* mo = om ? static_cast<u32*>(get(mout_k_[buf][k], sizeof(u32) * (size_t)n_send)) : nullptr;
+    float* go = get<float>(gout_k_[buf][k], (size_t)(n_send * Wd));
+    u32* mo = om ? get<u32>(mout_k_[buf][k], (size_t)n_send) : nullptr;
     e_.w_forward_backward(b, pulled, n_send, go, mo, S, sp.wb, k);
     float* gi = go;
     u32* mi = mo;
     if (!alias) {  // (world 1: the owner reads the pushes in place)
-      gi = static_cast<float*>(get(gin_k_[buf][k], sizeof(float) * (size_t)(n_recv * Wd)));
-      mi = om ? static_cast<u32*>(get(min_k_[buf][k], sizeof(u32) * (size_t)n_recv)) : nullptr;
+      gi = get<float>(gin_k_[buf][k], (size_t)(n_recv * Wd));
+      mi = om ? get<u32>(min_k_[buf][k], (size_t)n_recv) : nullptr;
     }
     p.groups.push_back({gi, go, mi, mo, Sg});
   }
@@ -555,15 +521,15 @@ bool ShardedStep::eval_step(const BatchView& b, float* pctr) {
   if (self_only()) {
     recv_keys = send_keys_[sp.wb];
   } else {
-    u64* rk = static_cast<u64*>(get(recv_keys_, sizeof(u64) * (size_t)last_recv));
+    u64* rk = get<u64>(recv_keys_, (size_t)last_recv);
     std::vector<RcclComm::A2AOp> ops(1);
     ops[0] = {send_keys_[sp.wb], sp.send, rk, sp.recv, (int)sizeof(u64)};
     a2a_group(ops);
     recv_keys = rk;
   }
-  float* vals = static_cast<float*>(get(vals_, sizeof(float) * (size_t)(last_recv * ps)));
+  float* vals = get<float>(vals_, (size_t)(last_recv * ps));
   e_.s_pull(recv_keys, last_recv, vals, false, 0);
-  float* pulled = static_cast<float*>(get(pulled_, sizeof(float) * (size_t)(last_send * ps)));
+  float* pulled = get<float>(pulled_, (size_t)(last_send * ps));
   std::vector<RcclComm::A2AOp> ops(1);
   ops[0] = {vals, sp.recv, pulled, sp.send, (int)sizeof(float) * ps};
   a2a_group(ops);

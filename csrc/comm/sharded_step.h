@@ -73,10 +73,9 @@ class ShardedStep {
   double csr_wait_s = 0.0;
 
  private:
-  struct Buf {  // grow-only device buffer
-    void* p = nullptr;
-    size_t bytes = 0;
-  };
+  // grow-only exchange buffer (bytes): stream-ordered, so a buffer that grows
+  // in the middle of a step costs no host wait
+  using Buf = StreamBuffer<char>;
   struct Split {
     int wb = 0;
     std::vector<int64_t> send, recv;
@@ -103,7 +102,13 @@ class ShardedStep {
     u64* keys = nullptr;
   };
 
-  void* get(Buf& b, size_t bytes);
+  // b as an array of n T, grown (with slack) when it is too small
+  template <typename T>
+  T* get(Buf& b, size_t n) {
+    const size_t bytes = sizeof(T) * n < 256 ? 256 : sizeof(T) * n;
+    if (b.reserve(e_.backend(), bytes, bytes + bytes / 4 + 4096)) ++buffer_growths;
+    return reinterpret_cast<T*>(b.get());
+  }
   bool self_only() const { return comm_ == nullptr; }
   void prepare(const BatchView& b, int64_t id, bool exchange);
   RcclComm::A2AOp counts_op(int wb);
@@ -125,9 +130,9 @@ class ShardedStep {
   RcclComm* comm_;
   int world_, rank_;
   bool early_keys_;
-  int64_t* counts_both_[2] = {nullptr, nullptr};  // device [2*world]: send | recv counts
-  u64* send_keys_[2] = {nullptr, nullptr};        // device [max_nnz]
-  int64_t* counts_host_[2] = {nullptr, nullptr};  // pinned [2*world]
+  DeviceBuffer<int64_t> counts_both_[2];  // device [2*world]: send | recv counts
+  DeviceBuffer<u64> send_keys_[2];        // device [max_nnz]
+  HostBuffer<int64_t> counts_host_[2];    // pinned [2*world]
   void* counts_ready_[2] = {nullptr, nullptr};    // events behind the D2H copies
   Buf recv_keys_, vals_, pulled_, ahead_keys_[2];
   std::vector<Buf> grads_out_, grads_in_, masks_out_, masks_in_;
@@ -148,8 +153,8 @@ class ShardedStep {
   // CSR exchange: per-key entry counts out / in, packed entries out / in,
   // per-owner totals (device [2 * world]: send | recv) and their pinned copy
   Buf csr_cnt_o_, csr_cnt_i_, csr_ent_o_, csr_ent_i_;
-  int64_t* csr_tot_ = nullptr;
-  int64_t* csr_tot_host_ = nullptr;
+  DeviceBuffer<int64_t> csr_tot_;
+  HostBuffer<int64_t> csr_tot_host_;
   void* csr_tot_ready_ = nullptr;
   // the gradient half of a CSR step (forward/backward, the two exchanges,
   // the per-source applies); ops holds the early next-keys op, if any

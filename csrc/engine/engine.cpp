@@ -22,11 +22,6 @@ uint64_t next_pow2(uint64_t v) {
   return p;
 }
 
-template <typename T>
-T* balloc(Backend& be, size_t n) {
-  return static_cast<T*>(be.alloc(sizeof(T) * (n ? n : 1)));
-}
-
 constexpr char kMagic[8] = {'X', 'F', 'L', 'O', 'W', 'T', 'B', '1'};
 
 // XFLOW_NO_MONITOR=1: no per-step capacity snapshot (A/B of the monitor's
@@ -39,18 +34,29 @@ bool monitor_disabled() {
 
 }  // namespace
 
-Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
-  if (cfg_.table_log2_cap < 4 || cfg_.table_log2_cap > 31)
+// Every argument check, before anything is allocated.
+const EngineConfig& Engine::validated(const EngineConfig& cfg) {
+  if (cfg.table_log2_cap < 4 || cfg.table_log2_cap > 31)
     throw std::invalid_argument("table_log2_cap must be in [4, 31]");
-  if (!(cfg_.grow_load > 0.0 && cfg_.grow_load < 1.0))
+  if (!(cfg.grow_load > 0.0 && cfg.grow_load < 1.0))
     throw std::invalid_argument("grow_load must be in (0, 1)");
-  if (cfg_.monitor_lag < 0 || cfg_.monitor_lag >= kSnaps)
+  if (cfg.monitor_lag < 0 || cfg.monitor_lag >= kSnaps)
     throw std::invalid_argument("monitor_lag must be in [0, 63]");
-  if (cfg_.max_slices < 1) throw std::invalid_argument("max_slices must be >= 1");
+  if (cfg.max_slices < 1) throw std::invalid_argument("max_slices must be >= 1");
+  if (cfg.model.kind != kLR && (cfg.model.v_dim < 1 || cfg.model.v_dim > 32))
+    throw std::invalid_argument("v_dim must be in [1, 32]");
+  if (cfg.admit_min_count < 1 || cfg.admit_min_count > 255)
+    throw std::invalid_argument("admit_min_count must be in [1, 255]");
+  if (cfg.admit_log2 != 0 && (cfg.admit_log2 < kAdmitBlockLog2 || cfg.admit_log2 > kAdmitMaxLog2))
+    throw std::invalid_argument("admit_log2 must be 0 (automatic) or in [6, 32]");
+  if (next_pow2((uint64_t)((double)cfg.max_nnz * cfg.scratch_factor) + 1) > (1ull << 31))
+    throw std::invalid_argument("max_nnz too large");
+  return cfg;
+}
+
+Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   // buffers hold one slice group (more slices per step run group by group)
   slice_cap_ = cfg_.max_slices < kSliceGroup ? cfg_.max_slices : kSliceGroup;
-  if (cfg_.model.kind != kLR && (cfg_.model.v_dim < 1 || cfg_.model.v_dim > 32))
-    throw std::invalid_argument("v_dim must be in [1, 32]");
   be_ = cfg_.device >= 0 ? make_hip_backend(cfg_.device) : make_cpu_backend();
   Backend& be = *be_;
   // the device kernels' latent widths: any other v_dim runs padded (inert
@@ -76,78 +82,54 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   table_.probe_limit = seg < kMaxProbe ? seg : kMaxProbe;
   max_segs_ = cfg_.table_grow ? (1ull << max_log2_cap_) >> table_.seg_log2 : table_.cap >> table_.seg_log2;
   table_bytes_ = (size_t)table_.cap * table_.L.stride * sizeof(u32);
-  {
-    void* base = be.table_reserve((size_t)(max_segs_ << table_.seg_log2) * table_.L.stride * sizeof(u32),
-                                  max_segs_ > (table_.cap >> table_.seg_log2));
-    table_.words = static_cast<u32*>(be.table_commit(base, table_bytes_));
-  }
+  table_.words = static_cast<u32*>(
+      be.table_reserve((size_t)(max_segs_ << table_.seg_log2) * table_.L.stride * sizeof(u32),
+                       max_segs_ > (table_.cap >> table_.seg_log2)));
+  table_range_.e = this;  // (from here on the range is released on unwinding)
+  table_.words = static_cast<u32*>(be.table_commit(table_.words, table_bytes_));
   // one 16-byte block {size, overflow[2]}: a step's snapshot is one copy
-  mon_ = balloc<u32>(be, 4);
-  table_.size = reinterpret_cast<unsigned long long*>(mon_);
-  overflow_ = mon_ + 2;
+  overflow_ = mon_.alloc_zero(be, 4) + 2;
+  table_.size = reinterpret_cast<unsigned long long*>(mon_.get());
   table_.overflow = overflow_ + 1;
-  be.memset(mon_, 0, 4 * sizeof(u32));
   be.table_clear(table_);
   // feature admission: the counting filter (EngineConfig::admit_min_count)
-  if (cfg_.admit_min_count < 1 || cfg_.admit_min_count > 255)
-    throw std::invalid_argument("admit_min_count must be in [1, 255]");
-  if (cfg_.admit_log2 != 0 && (cfg_.admit_log2 < kAdmitBlockLog2 || cfg_.admit_log2 > kAdmitMaxLog2))
-    throw std::invalid_argument("admit_log2 must be 0 (automatic) or in [6, 32]");
   if (cfg_.admit_min_count > 1) {
     const int top = cfg_.table_grow ? max_log2_cap_ : log2_cap_;
     admit_.log2 = cfg_.admit_log2 ? cfg_.admit_log2 : (top + 1 < kAdmitMaxLog2 ? top + 1 : kAdmitMaxLog2);
     if (admit_.log2 < kAdmitBlockLog2) admit_.log2 = kAdmitBlockLog2;
     admit_.min_count = cfg_.admit_min_count;
-    admit_.counters = balloc<unsigned char>(be, (size_t)1 << admit_.log2);
-    be.memset(admit_.counters, 0, (size_t)1 << admit_.log2);
+    admit_.counters = admit_counters_.alloc_zero(be, (size_t)1 << admit_.log2);
   }
-  snaps_ = static_cast<HostSnap*>(be.host_alloc(sizeof(HostSnap) * kSnaps));
-  std::memset(snaps_, 0, sizeof(HostSnap) * kSnaps);
+  std::memset(snaps_.alloc(be, kSnaps), 0, sizeof(HostSnap) * kSnaps);
 
   // per-step dedup scratch
   const int64_t nnz = cfg_.max_nnz;
   scratch_.cap = next_pow2((uint64_t)((double)nnz * cfg_.scratch_factor) + 1);
-  if (scratch_.cap > (1ull << 31)) throw std::invalid_argument("max_nnz too large");
-  scratch_.keys = balloc<u64>(be, scratch_.cap);
+  scratch_.keys = scratch_keys_.alloc(be, scratch_.cap);
   be.fill_u64(scratch_.keys, kEmptyKey, scratch_.cap);
-  scratch_.stamps = balloc<unsigned char>(be, scratch_.cap);
-  be.memset(scratch_.stamps, 0, scratch_.cap);
-  scratch_.claims = balloc<unsigned long long>(be, 1);
-  be.memset(scratch_.claims, 0, sizeof(unsigned long long));
+  scratch_.stamps = scratch_stamps_.alloc_zero(be, scratch_.cap);
+  scratch_.claims = scratch_claims_.alloc_zero(be, 1);
   // Rebuild once half full: one more step adds at most max_nnz <= cap/factor
   // keys, so the load factor stays below 0.5 + 1/factor.
   scratch_.rebuild_at = scratch_.cap / 2;
   scratch_.epoch = 0;
   if (be.is_gpu()) {
     // adaptive active capacity (ScratchView::ctl): starts at the allocation
-    scratch_.ctl = balloc<unsigned long long>(be, 5);
+    scratch_.ctl = scratch_ctl_.alloc(be, 5);
     unsigned long long c0[5] = {scratch_.cap, 0ull, 0ull, 0ull, 0ull};
     be.copy_h2d(scratch_.ctl, c0, sizeof(c0));
   }
-  block_counts_ = balloc<u32>(be, scratch_.cap / 4096 + 1);
+  block_counts_.alloc(be, scratch_.cap / 4096 + 1);
 
   const int ps = cfg_.model.pstride();
-  pos_ = balloc<u32>(be, nnz);
-  uniq_keys_ = balloc<u64>(be, nnz);
-  uniq_pos_ = balloc<u32>(be, nnz);
-  uniq_slot_ = balloc<u32>(be, nnz);
-  send_pos_ = balloc<u32>(be, nnz);
-  n_uniq_ = balloc<int64_t>(be, 1);
-  be.memset(n_uniq_, 0, sizeof(int64_t));
-  wset_[0].pos = pos_;
-  wset_[0].uniq_pos = uniq_pos_;
-  wset_[0].n_uniq = n_uniq_;
-  wset_[0].send_pos = send_pos_;
-  bcap_ = balloc<unsigned long long>(be, 1);
-  be.memset(bcap_, 0, sizeof(unsigned long long));
-  wset_[0].bcap = bcap_;
+  uniq_keys_.alloc(be, nnz);
+  uniq_slot_.alloc(be, nnz);
+  use_worker_set(0);
   // slot-indexed buffers carry one extra row: the trash slot (index cap) that
   // a dedup probe overflow sends its occurrences to (flagged, never applied)
   const uint64_t rows1 = scratch_.cap + 1;
-  grad_ = balloc<float>(be, rows1 * slice_cap_ * ps);
-  be.memset(grad_, 0, sizeof(float) * rows1 * slice_cap_ * ps);
-  tmask_ = balloc<u32>(be, rows1);
-  be.memset(tmask_, 0, sizeof(u32) * rows1);
+  grad_.alloc_zero(be, rows1 * slice_cap_ * ps);
+  tmask_.alloc_zero(be, rows1);
   // atomic-free gradient reduction (FwdArgs::red_*): LR (1 value per key) and
   // reference-math FM (2 values per key, 16-byte records)
   const bool fm_ref = cfg_.model.kind == kFM && cfg_.model.fm_math == kFmReference;
@@ -187,111 +169,57 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     if (nb <= maxb && dests < (1ull << 32)) {
       const int64_t groups = (cfg_.max_rows + group_rows - 1) / group_rows;
       red_nb_ = nb;
-      red_pairs_ = balloc<u64>(be, (size_t)nnz * recw);
-      red_sorted_ = balloc<u64>(be, (size_t)nnz * recw);
-      red_sorted_words_ = (int64_t)nnz * recw;
-      red_hist_ = balloc<u32>(be, (size_t)nb * groups);
-      red_tot_ = balloc<u32>(be, 2 * (size_t)nb + 2);
-      red_count_ = balloc<u32>(be, groups);
+      red_pairs_.alloc(be, (size_t)nnz * recw);
+      red_sorted_.alloc(be, (size_t)nnz * recw);
+      red_hist_.alloc(be, (size_t)nb * groups);
+      red_tot_.alloc(be, 2 * (size_t)nb + 2);
+      red_count_.alloc(be, groups);
       red_groups_ = (int)groups;
       // MVM: T = loss*M per row; standard FM: (loss, loss*vs) per row (k_fm_std_fwd)
-      if (mvm || fm_std) red_rowv_ = balloc<float>(be, (size_t)cfg_.max_rows * ps);
+      if (mvm || fm_std) red_rowv_.alloc(be, (size_t)cfg_.max_rows * ps);
       if (mvm) {
         // (vmax, dup flag, dup |c| max, dup record count: two alternating words each)
-        red_vmax_ = balloc<u32>(be, 8);
-        be.memset(red_vmax_, 0, 8 * sizeof(u32));
+        red_vmax_.alloc_zero(be, 8);
         // repeated-field rows' records and fixed-point sums (MvmDup, backend.h)
         const int D = cfg_.model.kernel_dim();
         mdup_ew_ = csr_row_words(D);
-        mdup_rec_ = balloc<float>(be, (size_t)nnz * mdup_ew_);
-        mdup_acc_ = balloc<long long>(be, (size_t)nnz * D);
-        mdup_claim_ = balloc<u32>(be, (size_t)nnz);
-        mdup_cap_ = nnz;
+        mdup_rec_.alloc(be, (size_t)nnz * mdup_ew_);
+        mdup_acc_.alloc(be, (size_t)nnz * D);
+        mdup_claim_.alloc(be, (size_t)nnz);
       }
     }
   }
   // reference-math FM with the GPU reduction: compact (w, Σv, Σv^2, 0) value rows
   fm_vals_ = red_pairs_ && fm_ref;
   vstride_ = fm_vals_ ? 4 : ps;
-  wpull_ = balloc<float>(be, rows1 * vstride_);
+  wpull_.alloc(be, rows1 * vstride_);
   be.memset(wpull_ + scratch_.cap * vstride_, 0, sizeof(float) * vstride_);
-  stats_ = balloc<LossStats>(be, 2);
-  be.memset(stats_, 0, 2 * sizeof(LossStats));
-  bucket_ws_ = balloc<int64_t>(be, 512);
-  slice_rows_cap_ = kSliceGroup;
-  slice_rows_ = balloc<int32_t>(be, slice_rows_cap_);
+  stats_.alloc_zero(be, 2);
+  bucket_ws_.alloc(be, 512);
+  slice_rows_.alloc(be, kSliceGroup);
 
-  st_keys_ = balloc<u64>(be, nnz);
-  st_fgid_ = balloc<int32_t>(be, nnz);
-  st_rowptr_ = balloc<int32_t>(be, cfg_.max_rows + 1);
-  st_labels_ = balloc<float>(be, cfg_.max_rows);
+  st_keys_.alloc(be, nnz);
+  st_fgid_.alloc(be, nnz);
+  st_rowptr_.alloc(be, cfg_.max_rows + 1);
+  st_labels_.alloc(be, cfg_.max_rows);
   be.synchronize();
 }
 
-Engine::~Engine() {
-  Backend& be = *be_;
-  be.synchronize();
-  use_worker_set(cur_wb_);  // (records the current set)
-  be.table_release(table_.words);
-  be.free_stream(csr_roff_);
-  be.free_stream(csr_long_);
-  void* ptrs[] = {admit_.counters, mon_, scratch_.keys, scratch_.stamps,
-                  scratch_.claims, block_counts_, uniq_keys_, uniq_slot_, wpull_, grad_, tmask_,
-                  stats_, bucket_ws_, slice_rows_, st_keys_, st_fgid_, st_rowptr_, st_labels_,
-                  host_keys_dev_, host_vals_dev_,
-                  host_slots_dev_, scratch_.ctl, red_pairs_, red_sorted_, red_hist_,
-                  red_tot_, red_count_, red_rowv_, lr_grad_, lr_nz_, grp_nz_, own_keys_, fm_grad_,
-                  row_grad_,
-                  lr_mask_, fm_w_, rec_count_, red_vmax_, text_ws_, text_counts_, csr_off_, csr_vent_,
-                  csr_cnt_, csr_doff_, mdup_rec_, mdup_acc_, mdup_claim_};
-  for (void* p : ptrs) be.free(p);
-  for (void* p : stage_io_) be.staging_free(p);
-  for (SrvBuf& b : srv_) {
-    void* bp[] = {b.slots, b.nz, b.w, b.own_pos, b.own_idx};
-    for (void* p : bp) be.free(p);
-  }
-  be.host_free(snaps_);
-  for (StageSet& a : aset_) {
-    void* ap[] = {a.keys, a.rowptr, a.fgid, a.labels};
-    for (void* p : ap) be.free(p);
-  }
-  for (WorkerSet& w : wset_) {
-    void* wp[] = {w.pos, w.uniq_pos, w.inv, w.n_uniq, w.send_pos, w.bcap};
-    for (void* p : wp) be.free(p);
-  }
-}
+Engine::~Engine() { be_->synchronize(); }  // (the members release the table range and the buffers)
 
 void Engine::use_worker_set(int wb) {
   if (wb < 0 || wb > 1) throw std::invalid_argument("worker buffer set must be 0 or 1");
-  WorkerSet& c = wset_[cur_wb_];
-  c.pos = pos_;
-  c.uniq_pos = uniq_pos_;
-  c.inv = inv_;
-  c.n_uniq = n_uniq_;
-  c.send_pos = send_pos_;
-  c.send_map = send_map_;
-  c.inv_valid = inv_valid_;
-  c.bcap = bcap_;
-  WorkerSet& w = wset_[wb];
-  if (!w.pos) {  // second set: allocated on first use (pipelined sharded step)
-    const int64_t nnz = cfg_.max_nnz;
-    w.pos = balloc<u32>(*be_, nnz);
-    w.uniq_pos = balloc<u32>(*be_, nnz);
-    w.send_pos = balloc<u32>(*be_, nnz);
-    w.n_uniq = balloc<int64_t>(*be_, 1);
-    be_->memset(w.n_uniq, 0, sizeof(int64_t));
-    w.bcap = balloc<unsigned long long>(*be_, 1);
-    be_->memset(w.bcap, 0, sizeof(unsigned long long));
-  }
-  pos_ = w.pos;
-  uniq_pos_ = w.uniq_pos;
-  inv_ = w.inv;
-  n_uniq_ = w.n_uniq;
-  send_pos_ = w.send_pos;
-  send_map_ = w.send_map;
-  inv_valid_ = w.inv_valid;
-  bcap_ = w.bcap;
-  cur_wb_ = wb;
+  ws_ = &wset_[wb];
+  if (ws_->pos) return;
+  // first use: set 0 by the constructor, set 1 by the pipelined sharded step
+  // (pos last: a set whose allocation threw half way is allocated again)
+  Backend& be = *be_;
+  const int64_t nnz = cfg_.max_nnz;
+  ws_->uniq_pos.alloc(be, nnz);
+  ws_->send_pos.alloc(be, nnz);
+  ws_->n_uniq.alloc_zero(be, 1);
+  ws_->bcap.alloc_zero(be, 1);
+  ws_->pos.alloc(be, nnz);
 }
 
 // The GPU reduction path sees every (key, slice) that occurs (a record per
@@ -310,13 +238,8 @@ std::vector<int64_t> Engine::parse_text(const char* text, int64_t n, u64* keys, 
                                         int32_t* row_ptr, float* labels, int64_t max_rows,
                                         int64_t max_nnz, int64_t row_mod) {
   const int64_t need = text_ws_words(n);
-  if (need > text_ws_words_) {
-    be_->synchronize();
-    be_->free(text_ws_);
-    text_ws_words_ = need + need / 4;
-    text_ws_ = balloc<u32>(*be_, (size_t)text_ws_words_);
-  }
-  if (!text_counts_) text_counts_ = balloc<long long>(*be_, 8);
+  text_ws_.reserve(*be_, (size_t)need, (size_t)(need + need / 4));
+  text_counts_.ensure(*be_, 8);
   TextParseArgs a;
   a.text = text;
   a.n = n;
@@ -328,7 +251,7 @@ std::vector<int64_t> Engine::parse_text(const char* text, int64_t n, u64* keys, 
   a.max_nnz = max_nnz;
   a.max_lines = text_max_lines(n);
   a.ws = text_ws_;
-  a.ws_words = text_ws_words_;
+  a.ws_words = (int64_t)text_ws_.capacity();
   a.row_mod = row_mod;
   a.counts = text_counts_;
   be_->parse_text(a);
@@ -341,10 +264,7 @@ std::vector<int64_t> Engine::parse_text(const char* text, int64_t n, u64* keys, 
 }
 
 void Engine::count_records(bool on) {
-  if (on && !rec_count_) {
-    rec_count_ = balloc<unsigned long long>(*be_, 1);
-    be_->memset(rec_count_, 0, sizeof(unsigned long long));
-  }
+  if (on && !rec_count_) rec_count_.alloc_zero(*be_, 1);
   rec_on_ = on;
 }
 
@@ -371,17 +291,17 @@ void Engine::set_reduction(FwdArgs& fa) const {
       fa.mdup.n = red_vmax_ + 6;
       fa.mdup.acc = mdup_acc_;
       fa.mdup.claim = mdup_claim_;
-      fa.mdup.cap = mdup_cap_;
+      fa.mdup.cap = (int64_t)mdup_claim_.capacity();
       fa.mdup.ew = mdup_ew_;
     }
     vmax_parity_ ^= 1;
   }
-  fa.red_bcap = bcap_;
+  fa.red_bcap = ws_->bcap;
   fa.red_cap = scratch_.cap;
   fa.red_nsub = red_nsub_;
   fa.red_pairs = red_pairs_;
   fa.red_sorted = red_sorted_;
-  fa.red_sorted_words = red_sorted_words_;
+  fa.red_sorted_words = (int64_t)red_sorted_.capacity();
   fa.red_hist = red_hist_;
   fa.red_tot = red_tot_;
   fa.red_count = red_count_;
@@ -400,12 +320,8 @@ const int32_t* Engine::slice_rows_dev(const BatchView& b, int S) {
   if (b.rows == cached_rows_ && b.slice_rows == cached_slice_rows_ && S == cached_S_)
     return slice_rows_;
   const int ng = slice_groups(S);
-  if ((int64_t)ng * kSliceGroup > slice_rows_cap_) {
-    be_->synchronize();  // (the old normalisers may still be read)
-    be_->free(slice_rows_);
-    slice_rows_cap_ = (int64_t)ng * kSliceGroup;
-    slice_rows_ = balloc<int32_t>(*be_, slice_rows_cap_);
-  }
+  // (a growth waits for the stream: the old normalisers may still be read)
+  slice_rows_.reserve(*be_, (size_t)ng * kSliceGroup, (size_t)ng * kSliceGroup);
   const int64_t sr = b.slice_rows > 0 ? b.slice_rows : b.rows;
   for (int g = 0; g < ng; ++g) {
     int32_t h[kSliceGroup];
@@ -451,11 +367,11 @@ BatchView Engine::group_view(const BatchView& b, int S, int k, const u32*& pos) 
 }
 
 void Engine::ensure_inv() {
-  if (inv_) return;
+  if (ws_->inv) return;
   // + the trash slot's entry (and padding to a 16-slot compaction group): no
   // unique index, so reductions skip it
-  inv_ = balloc<u32>(*be_, scratch_.cap + 16);
-  be_->memset(inv_ + scratch_.cap, 0xFF, 16 * sizeof(u32));
+  ws_->inv.alloc(*be_, scratch_.cap + 16);
+  be_->memset(ws_->inv + scratch_.cap, 0xFF, 16 * sizeof(u32));
 }
 
 void Engine::dedup_(const BatchView& b, int parts, u64* uniq_keys_out, bool want_inv,
@@ -491,15 +407,15 @@ void Engine::dedup_(const BatchView& b, int parts, u64* uniq_keys_out, bool want
     scratch_.grow = (float)((double)b.nnz / (double)nnz_seen_);
   if (b.nnz > nnz_seen_) nnz_seen_ = b.nnz;
   DedupOut o;
-  o.pos = pos_;
+  o.pos = ws_->pos;
   o.uniq_keys = uniq_keys_out ? uniq_keys_out : uniq_keys_;
-  o.uniq_pos = uniq_pos_;
-  o.n_uniq = n_uniq_;
+  o.uniq_pos = ws_->uniq_pos;
+  o.n_uniq = ws_->n_uniq;
   o.overflow = overflow_;
   o.block_counts = block_counts_;
-  o.inv = want_inv ? inv_ : nullptr;
+  o.inv = want_inv ? ws_->inv.get() : nullptr;
   o.n_uniq_copy = n_copy;
-  o.cap_out = bcap_;
+  o.cap_out = ws_->bcap;
   be_->dedup(b.keys, b.nnz, scratch_, o);
 }
 
@@ -638,29 +554,19 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   // standard FM / MVM: full-row entries (k_red_csr_vec), applied by the packed CSR apply
   const bool rows = csr_full_rows();
   ensure_inv();
-  if (!csr_off_) {
-    csr_off_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz);
-    csr_cnt_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz);
-  }
   const int ew = rows ? csr_row_words(table_.L.P) : 0;
-  float* stash;
-  if (fm || rows) {
-    if (!grp_nz_) grp_nz_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P);
-    stash = grp_nz_;
-  } else {
-    if (!lr_nz_) lr_nz_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz);
-    stash = lr_nz_;
-  }
+  float* stash = fm || rows ? grp_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P)
+                            : lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
   dedup_(b, 1, nullptr, true);
-  inv_valid_ = false;
-  be_->remap_pos(pos_, b.nnz, inv_, (u32)scratch_.cap);
+  ws_->inv_valid = false;
+  be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
   guard_inserts(b.nnz);
 
   PullArgs pa;
   pa.table = table_;
   pa.opt = cfg_.opt;
   pa.keys = uniq_keys_;
-  pa.n_dev = n_uniq_;
+  pa.n_dev = ws_->n_uniq;
   pa.n_max = b.nnz;
   pa.insert = true;
   pa.admit = admit_;
@@ -680,7 +586,7 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   aa.opt = cfg_.opt;
   aa.keys = uniq_keys_;
   aa.slots = uniq_slot_;
-  aa.n_dev = n_uniq_;
+  aa.n_dev = ws_->n_uniq;
   aa.n_max = b.nnz;
   aa.S = S;
   aa.pstride = pstride();
@@ -690,11 +596,11 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   aa.nz_stash = stash;
   aa.csr_off = csr_off_;
   aa.csr_cnt = csr_cnt_;
-  aa.csr_ent = rows ? static_cast<const void*>(csr_vent_) : red_pairs_;
+  aa.csr_ent = rows ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get();
   aa.csr_ew = ew;
   // (a chain has at most S entries: with S <= 16 nothing is ever deferred)
   aa.csr_long = S > 16 ? csr_long_list(b.nnz) : nullptr;
-  aa.csr_long_cap = csr_long_cap_;
+  aa.csr_long_cap = (int64_t)csr_long_.capacity();
   attach_snapshot(aa);
   be_->table_apply(aa);
   end_step();
@@ -702,13 +608,11 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
 
 void Engine::csr_forward_backward(const BatchView& b, int slog2, const int32_t* srows,
                                   bool normalise) {
-  if (!csr_off_) {
-    csr_off_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz);
-    csr_cnt_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz);
-  }
+  csr_off_.ensure(*be_, (size_t)cfg_.max_nnz);  // (the CSR arrays' one allocation site)
+  csr_cnt_.ensure(*be_, (size_t)cfg_.max_nnz);
   FwdArgs fa;
   fa.batch = b;
-  fa.pos = pos_;
+  fa.pos = ws_->pos;
   fa.wpull = wpull_;
   fa.grad = grad_;
   fa.stats = stats_;
@@ -717,7 +621,7 @@ void Engine::csr_forward_backward(const BatchView& b, int slog2, const int32_t* 
   fa.agg_ok = true;  // (dests below max_nnz * 2^slog2 < 2^32: csr_slog2)
   fa.fx_bad = overflow_;
   set_reduction(fa);
-  fa.red_nuq = n_uniq_;
+  fa.red_nuq = ws_->n_uniq;
   fa.fm_compact = fm_vals_;
   fa.fm_vals = fm_vals_;
   fa.red_csr.off = csr_off_;
@@ -727,8 +631,7 @@ void Engine::csr_forward_backward(const BatchView& b, int slog2, const int32_t* 
   fa.red_csr.rows = normalise ? srows : nullptr;
   if (csr_full_rows()) {  // full-row entries
     const int ew = csr_row_words(table_.L.P);
-    if (!csr_vent_) csr_vent_ = balloc<float>(*be_, (size_t)cfg_.max_nnz * ew);
-    fa.red_csr.ent = csr_vent_;
+    fa.red_csr.ent = csr_vent_.ensure(*be_, (size_t)cfg_.max_nnz * ew);
     fa.red_csr.P = table_.L.P;
     fa.red_csr.ew = ew;
   }
@@ -742,11 +645,7 @@ u32* Engine::csr_long_list(int64_t n) {
   // <= 8192 x 4 waves x 64, and the per-wave counts)
   // (+ the dense list of n, the offsets and the scan tiles)
   const int64_t need = 2 * n + (int64_t)(2u << 20) + 4 * 65536;
-  if (need > csr_long_cap_) {
-    be_->free_stream(csr_long_);
-    csr_long_cap_ = need + n / 4;
-    csr_long_ = static_cast<u32*>(be_->alloc_stream(sizeof(u32) * (size_t)csr_long_cap_));
-  }
+  csr_long_.reserve(*be_, (size_t)need, (size_t)(need + n / 4));
   return csr_long_;
 }
 
@@ -761,20 +660,20 @@ void Engine::w_forward_backward_csr(const BatchView& b, const float* pulled, int
     throw std::invalid_argument("w_forward_backward_csr: S_global off the CSR path");
   // (a rank out of data -- a batch of 0 rows -- still takes part: no keys,
   // zero entries per owner)
-  if (b.nnz > 0 && !inv_valid_)
+  if (b.nnz > 0 && !ws_->inv_valid)
     throw std::logic_error("w_forward_backward_csr: needs the partitioned dedup's inv");
   // unique-index (= send-order) positions, and the pulled rows (send order)
   // as the forward's value rows; the trash slot's row stays zero
-  be_->remap_pos(pos_, b.nnz, inv_, (u32)scratch_.cap);
+  be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
   be_->scatter_rows(pulled, wpull_, nullptr, nullptr, n_send, vstride_);
   // (rows per slice: the worker normalises, the owner does not know them)
   csr_forward_backward(b, sl, slice_rows_dev(b, St), true);
   last_nsend_ = n_send;
   if (!pack) return;
-  if (!csr_doff_) csr_doff_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz + 1);
-  be_->scan_u32(csr_cnt_, csr_doff_, n_uniq_, cfg_.max_nnz);
-  be_->csr_pack(csr_off_, csr_cnt_, csr_full_rows() ? static_cast<const void*>(csr_vent_) : red_pairs_,
-                csr_doff_, n_uniq_, cfg_.max_nnz, ent_out, csr_entry_bytes());
+  csr_doff_.ensure(*be_, (size_t)cfg_.max_nnz + 1);
+  be_->scan_u32(csr_cnt_, csr_doff_, ws_->n_uniq, cfg_.max_nnz);
+  be_->csr_pack(csr_off_, csr_cnt_, csr_full_rows() ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get(),
+                csr_doff_, ws_->n_uniq, cfg_.max_nnz, ent_out, csr_entry_bytes());
   be_->copy_d2d(cnt_out, csr_cnt_, sizeof(u32) * (size_t)n_send);
   be_->csr_totals(counts, world, encoded, csr_doff_, totals_out);
 }
@@ -788,15 +687,11 @@ void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* 
   stale_stashes();
   const u32* off = csr_off_;
   const u32* cnt = csr_cnt_;
-  const void* ent = csr_full_rows() ? static_cast<const void*>(csr_vent_) : red_pairs_;
+  const void* ent = csr_full_rows() ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get();
   const int64_t n = src_offsets.empty() ? 0 : src_offsets.back();
   if (n > sb.n) throw std::invalid_argument("s_apply_csr: offsets beyond pull");
   if (recv_cnt) {  // received entries: offsets by a scan of the counts
-    if (n + 1 > csr_roff_cap_) {
-      be_->free_stream(csr_roff_);
-      csr_roff_cap_ = n + n / 4 + 1024;
-      csr_roff_ = static_cast<u32*>(be_->alloc_stream(sizeof(u32) * (size_t)csr_roff_cap_));
-    }
+    csr_roff_.reserve(*be_, (size_t)n + 1, (size_t)(n + n / 4 + 1024));
     be_->scan_u32(recv_cnt, csr_roff_, nullptr, n);
     off = csr_roff_;
     cnt = recv_cnt;
@@ -831,7 +726,7 @@ void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* 
     aa.csr_cnt = cnt + o;
     aa.csr_ent = ent;
     aa.csr_long = S > 16 ? csr_long_list(c) : nullptr;
-    aa.csr_long_cap = csr_long_cap_;
+    aa.csr_long_cap = (int64_t)csr_long_.capacity();
     if (stash) aa.nz_stash = sb.nz ? sb.nz + 2 * o : nullptr;
     stash = false;
     attach_snapshot(aa);
@@ -854,7 +749,7 @@ void Engine::csr_debug(std::vector<u32>& off, std::vector<u32>& cnt, std::vector
   const bool rows = csr_vent_ && cfg_.model.kind == kFM && cfg_.model.fm_math == kFmStandard;
   const int w = rows ? csr_row_words(table_.L.P) : csr_entry_bytes() / 4;
   words.resize((size_t)end * w);
-  if (end) be_->copy_d2h(words.data(), rows ? static_cast<const void*>(csr_vent_) : red_pairs_,
+  if (end) be_->copy_d2h(words.data(), rows ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get(),
                          sizeof(u32) * (size_t)end * w);
 }
 
@@ -879,41 +774,41 @@ void Engine::train_step(const BatchView& b) {
   const bool rowu = P.rowu, fsu = P.fsu, grpst = P.grpst, uq = P.uq, upos = P.upos;
   // (dest * ps in 32 bits over unique indices or scratch slots, see plan_step)
   const double key_bound = upos ? (double)cfg_.max_nnz : (double)scratch_.cap;
-  if (lr16s && !lr_nz_) lr_nz_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz);
+  if (lr16s) lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
   if (lr16) {
     ensure_inv();
-    if (!lr_grad_) lr_grad_ = balloc<float>(*be_, (size_t)cfg_.max_nnz * slice_cap_);
-    if (!lr_nz_) lr_nz_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz);
+    lr_grad_.ensure(*be_, (size_t)cfg_.max_nnz * slice_cap_);
+    lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
   }
   if (fmu) {
     ensure_inv();
-    if (!fm_grad_) fm_grad_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz * slice_cap_);
+    fm_grad_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * slice_cap_);
   }
-  if (fm_keep_w && !fm_w_) fm_w_ = balloc<float>(*be_, (size_t)cfg_.max_nnz * ps);
+  if (fm_keep_w) fm_w_.ensure(*be_, (size_t)cfg_.max_nnz * ps);
   if (rowu) {
     ensure_inv();
     const int rs = fsu ? slice_cap_ : 1;
-    if (!row_grad_) row_grad_ = balloc<float>(*be_, (size_t)cfg_.max_nnz * ps * rs);
+    row_grad_.ensure(*be_, (size_t)cfg_.max_nnz * ps * rs);
   }
-  if (grpst && !grp_nz_) grp_nz_ = balloc<float>(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P);
-  if (uq && !lr_mask_) lr_mask_ = balloc<u32>(*be_, (size_t)cfg_.max_nnz);
+  if (grpst) grp_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P);
+  if (uq) lr_mask_.ensure(*be_, (size_t)cfg_.max_nnz);
   if (upos) ensure_inv();
   dedup_(b, 1, nullptr, upos || lr16 || fmu || rowu);
-  inv_valid_ = false;  // (the sharded step's send order is not this one)
-  if (upos) be_->remap_pos(pos_, b.nnz, inv_, (u32)scratch_.cap);
+  ws_->inv_valid = false;  // (the sharded step's send order is not this one)
+  if (upos) be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
   guard_inserts(b.nnz);  // (<= nnz new keys; may grow the table first)
 
   PullArgs pa;
   pa.table = table_;
   pa.opt = cfg_.opt;
   pa.keys = uniq_keys_;
-  pa.n_dev = n_uniq_;
+  pa.n_dev = ws_->n_uniq;
   pa.n_max = b.nnz;
   pa.insert = true;
   pa.admit = admit_;
   pa.out_slot = uniq_slot_;
   pa.out_vals = wpull_;
-  pa.out_map = upos ? nullptr : uniq_pos_;
+  pa.out_map = upos ? nullptr : ws_->uniq_pos.get();
   pa.pstride = ps;
   pa.fm_vals = fm_vals_;
   if (fm_keep_w) pa.out_w = fm_w_;
@@ -935,13 +830,13 @@ void Engine::train_step(const BatchView& b) {
     pa.zero_width = ps;
   }
   if (uq) {  // S > 1: only a key's present slices are read, so only its bits need clearing
-    pa.zero_out = reinterpret_cast<float*>(lr_mask_);
+    pa.zero_out = reinterpret_cast<float*>(lr_mask_.get());
     pa.zero_width = 1;
   }
   be_->table_pull(pa);
 
   for (int k = 0; k < ng; ++k) {
-    const u32* posk = pos_;
+    const u32* posk = ws_->pos;
     const BatchView bk = group_view(b, S, k, posk);
     const int Sg = group_slices(S, k);
     const int32_t* srk = srows + (int64_t)k * kSliceGroup;
@@ -962,7 +857,7 @@ void Engine::train_step(const BatchView& b) {
     fa.agg_ok = key_bound * Sg * ps < 4294967295.0;  // (32-bit dest * ps, see rows_ok)
     fa.fx_bad = overflow_;
     set_reduction(fa);
-    if (upos) fa.red_nuq = n_uniq_;
+    if (upos) fa.red_nuq = ws_->n_uniq;
     // slice bits from the reduction (unique order with the outputs, else
     // slot-indexed), else per occurrence
     if (uq) fa.red_masks = lr_mask_;
@@ -974,7 +869,7 @@ void Engine::train_step(const BatchView& b) {
     fa.fm_vals = fm_vals_;
     if (fm_vals_ && !fa.fm_compact) throw std::logic_error("train_step: compact FM rows need the reduction");
     // (unique-index positions: the outputs' rows are the dests' own)
-    const u32* oinv = upos ? nullptr : inv_;
+    const u32* oinv = upos ? nullptr : ws_->inv.get();
     if (lr16) {
       fa.red_out = lr_grad_;
       fa.red_inv = oinv;
@@ -996,12 +891,12 @@ void Engine::train_step(const BatchView& b) {
     aa.opt = cfg_.opt;
     aa.keys = uniq_keys_;
     aa.slots = uniq_slot_;
-    aa.n_dev = n_uniq_;
+    aa.n_dev = ws_->n_uniq;
     aa.n_max = b.nnz;
     aa.grads = grad_;
-    aa.grad_map = upos ? nullptr : uniq_pos_;  // (slot- or unique-indexed rows)
-    aa.masks = masks ? tmask_ : nullptr;
-    aa.masks_rw = masks ? tmask_ : nullptr;
+    aa.grad_map = upos ? nullptr : ws_->uniq_pos.get();  // (slot- or unique-indexed rows)
+    aa.masks = masks ? tmask_.get() : nullptr;
+    aa.masks_rw = masks ? tmask_.get() : nullptr;
     aa.zero_after = true;
     aa.S = Sg;
     aa.pstride = ps;
@@ -1016,7 +911,7 @@ void Engine::train_step(const BatchView& b) {
       aa.grad_map = nullptr;
       aa.zero_after = false;
       aa.slice_rows = nullptr;
-      aa.nz_stash = stash ? lr_nz_ : nullptr;
+      aa.nz_stash = stash ? lr_nz_.get() : nullptr;
     }
     if (lr16s && stash) aa.nz_stash = lr_nz_;  // (unique order, as the apply's entries)
     if (grpst && stash) aa.nz_stash = grp_nz_;
@@ -1051,19 +946,19 @@ void Engine::eval_step(const BatchView& b, float* pctr) {
   pa.table = table_;
   pa.opt = cfg_.opt;
   pa.keys = uniq_keys_;
-  pa.n_dev = n_uniq_;
+  pa.n_dev = ws_->n_uniq;
   pa.n_max = b.nnz;
   pa.insert = false;
   pa.out_slot = uniq_slot_;
   pa.out_vals = wpull_;
-  pa.out_map = uniq_pos_;
+  pa.out_map = ws_->uniq_pos;
   pa.pstride = pstride();
   pa.fm_vals = fm_vals_;
   be_->table_pull(pa);
 
   FwdArgs fa;
   fa.batch = b;
-  fa.pos = pos_;
+  fa.pos = ws_->pos;
   fa.wpull = wpull_;
   fa.grad = nullptr;
   fa.pctr = pctr;
@@ -1074,6 +969,13 @@ void Engine::eval_step(const BatchView& b, float* pctr) {
   be_->forward_backward(fa);
 }
 
+// the device arrays of push_host / pull_host: exactly n keys when they grow
+void Engine::ensure_host_staging(int64_t n) {
+  if (!host_keys_dev_.reserve(*be_, (size_t)n, (size_t)n)) return;  // (waited for the stream)
+  host_vals_dev_.alloc(*be_, (size_t)n * cfg_.model.P());
+  host_slots_dev_.alloc(*be_, (size_t)n);
+}
+
 void Engine::push_host(const std::vector<u64>& keys, const std::vector<float>& grads) {
   stale_stashes();  // the table changes: server stashes are stale
   const int64_t n = (int64_t)keys.size();
@@ -1081,16 +983,7 @@ void Engine::push_host(const std::vector<u64>& keys, const std::vector<float>& g
   if ((int64_t)grads.size() != n * P) throw std::invalid_argument("push_host: grads != keys*P");
   if (n == 0) return;
   guard_inserts(n);
-  if (n > host_cap_) {
-    be_->synchronize();
-    be_->free(host_keys_dev_);
-    be_->free(host_vals_dev_);
-    be_->free(host_slots_dev_);
-    host_cap_ = n;
-    host_keys_dev_ = balloc<u64>(*be_, n);
-    host_vals_dev_ = balloc<float>(*be_, n * P);
-    host_slots_dev_ = balloc<u32>(*be_, n);
-  }
+  ensure_host_staging(n);
   be_->copy_h2d(host_keys_dev_, keys.data(), sizeof(u64) * n);
   be_->copy_h2d(host_vals_dev_, grads.data(), sizeof(float) * n * P);
   PullArgs pa;
@@ -1136,16 +1029,7 @@ std::vector<float> Engine::pull_host(const std::vector<u64>& keys) {
   const int P = cfg_.model.P();
   std::vector<float> out((size_t)n * P);
   if (n == 0) return out;
-  if (n > host_cap_) {
-    be_->synchronize();
-    be_->free(host_keys_dev_);
-    be_->free(host_vals_dev_);
-    be_->free(host_slots_dev_);
-    host_cap_ = n;
-    host_keys_dev_ = balloc<u64>(*be_, n);
-    host_vals_dev_ = balloc<float>(*be_, n * P);
-    host_slots_dev_ = balloc<u32>(*be_, n);
-  }
+  ensure_host_staging(n);
   be_->copy_h2d(host_keys_dev_, keys.data(), sizeof(u64) * n);
   PullArgs pa;
   pa.table = table_;
@@ -1178,51 +1062,46 @@ void Engine::w_prepare(const BatchView& b, int world, int64_t* counts_out, u64* 
     const int64_t c = b.rows == 0 ? -1 : 0;
     be_->fill_u64(reinterpret_cast<u64*>(counts_out), (u64)(seq >= 0 ? encode_count(c, seq) : c),
                   (size_t)(world > 0 ? world : 1));
-    be_->memset(n_uniq_, 0, sizeof(int64_t));
-    inv_valid_ = false;
-    send_map_ = uniq_pos_;
+    be_->memset(ws_->n_uniq, 0, sizeof(int64_t));
+    ws_->inv_valid = false;
+    ws_->send_map = ws_->uniq_pos;
     return;
   }
   if (world >= 1 && world <= kMaxParts && be_->partitioned_dedup()) {
     // owner-partitioned scratch: the slot-ordered unique list is the send
-    // order already; counts are range counts (one range at world 1).  inv_
+    // order already; counts are range counts (one range at world 1).  ws_->inv
     // (slot -> send index) lets the LR backward write the send buffer directly.
     if (red_pairs_ && (cfg_.model.kind == kLR || fm_vals_ || csr_full_rows())) ensure_inv();
     dedup_(b, world, send_keys_out, true, world == 1 ? counts_out : nullptr);
-    inv_valid_ = inv_ != nullptr;
-    if (world > 1) be_->partition_counts(scratch_, block_counts_, n_uniq_, counts_out, seq);
-    send_map_ = uniq_pos_;
+    ws_->inv_valid = ws_->inv != nullptr;
+    if (world > 1) be_->partition_counts(scratch_, block_counts_, ws_->n_uniq, counts_out, seq);
+    ws_->send_map = ws_->uniq_pos;
     return;
   }
   dedup_(b);
-  inv_valid_ = false;
+  ws_->inv_valid = false;
   BucketArgs ba;
   ba.uniq_keys = uniq_keys_;
-  ba.uniq_pos = uniq_pos_;
-  ba.n_dev = n_uniq_;
+  ba.uniq_pos = ws_->uniq_pos;
+  ba.n_dev = ws_->n_uniq;
   ba.n_max = b.nnz;
   ba.world = world;
   ba.counts = counts_out;
   ba.send_keys = send_keys_out;
-  ba.send_pos = send_pos_;
+  ba.send_pos = ws_->send_pos;
   ba.scratch = bucket_ws_;
   ba.seq = seq;
   be_->bucket(ba);
-  send_map_ = send_pos_;
+  ws_->send_map = ws_->send_pos;
   // (slice masks are built in w_forward_backward with the step's global S)
 }
 
 void Engine::ensure_server_capacity(int64_t n, int buf) {
   if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
   SrvBuf& sb = srv_[buf];
-  if (n <= sb.cap) return;
-  be_->synchronize();
-  be_->free(sb.slots);
-  be_->free(sb.nz);
-  sb.nz = nullptr;
-  sb.cap = n + n / 4 + 1024;
-  sb.slots = balloc<u32>(*be_, sb.cap);
-  if (lr16_layout()) sb.nz = balloc<float>(*be_, 2 * (size_t)sb.cap);
+  const size_t cap = (size_t)(n + n / 4 + 1024);
+  if (n <= 0 || !sb.slots.reserve(*be_, (size_t)n, cap)) return;  // (waited for the stream)
+  if (lr16_layout()) sb.nz.alloc(*be_, 2 * cap);
 }
 
 bool Engine::lr16_layout() const {
@@ -1233,10 +1112,10 @@ bool Engine::lr16_layout() const {
 void Engine::w_forward(const BatchView& b, const float* pulled, int64_t n_send, float* pctr,
                        int wb) {
   use_worker_set(wb);
-  be_->scatter_rows(pulled, wpull_, send_map_, nullptr, n_send, vstride_);
+  be_->scatter_rows(pulled, wpull_, ws_->send_map, nullptr, n_send, vstride_);
   FwdArgs fa;
   fa.batch = b;
-  fa.pos = pos_;
+  fa.pos = ws_->pos;
   fa.wpull = wpull_;
   fa.grad = nullptr;
   fa.pctr = pctr;
@@ -1283,12 +1162,7 @@ void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool inser
   int active = 0;
   for (int s2 = 0; s2 < nsrc; ++s2) active += src_offsets[s2 + 1] > src_offsets[s2];
   if (fm_vals_ && insert && (keep_weights || (!sb.grp.oidx && active > 1))) {
-    if (sb.w_cap < n) {
-      be_->synchronize();
-      be_->free(sb.w);
-      sb.w_cap = n + n / 4 + 1024;
-      sb.w = balloc<float>(*be_, (size_t)sb.w_cap * pstride());
-    }
+    sb.w.reserve(*be_, (size_t)n * pstride(), (size_t)(n + n / 4 + 1024) * pstride());
     pa.out_w = sb.w;
     sb.w_valid = true;
   }
@@ -1318,36 +1192,26 @@ bool Engine::group_entries(const u64* recv_keys, int64_t n, int buf,
   if (active < 2) return false;  // one source: the per-source apply is one launch already
   const u64 want = next_pow2((uint64_t)n * 4);
   if (want > (1ull << 32)) throw std::invalid_argument("s_pull: too many received keys to group");
-  if (want > own_cap_ || nsrc != own_nsrc_) {
+  if (want > own_keys_.capacity() || nsrc != own_nsrc_) {
     // (re)size: the other buffer's registrations are dropped with the arrays
     // (its apply then runs source by source)
     be_->synchronize();
-    const u64 cap = want > own_cap_ ? want : own_cap_;
-    be_->free(own_keys_);
+    const u64 cap = want > own_keys_.capacity() ? want : own_keys_.capacity();
     for (SrvBuf& b : srv_) {
-      be_->free(b.own_idx);
-      b.own_idx = nullptr;
+      b.own_idx.reset();
       b.grp = SrcGroups();
     }
-    own_cap_ = cap;
     own_nsrc_ = nsrc;
-    own_keys_ = balloc<u64>(*be_, cap);
+    own_keys_.alloc(*be_, cap);
     be_->fill_u64(own_keys_, kEmptyKey, cap);
     own_fill_ = 0;
   }
+  const u64 own_cap = own_keys_.capacity();
   SrvBuf& sb = srv_[buf];
-  if (!sb.own_idx) {
-    sb.own_idx = balloc<u64>(*be_, own_cap_ * (u64)own_nsrc_);
-    be_->memset(sb.own_idx, 0, sizeof(u64) * own_cap_ * own_nsrc_);  // epoch 0: never valid
-  }
-  if (n > sb.own_pos_cap) {
-    be_->synchronize();
-    be_->free(sb.own_pos);
-    sb.own_pos_cap = n + n / 4 + 1024;
-    sb.own_pos = balloc<u32>(*be_, sb.own_pos_cap);
-  }
-  if (own_fill_ + n > (int64_t)(own_cap_ / 2)) {
-    be_->fill_u64(own_keys_, kEmptyKey, own_cap_);
+  if (!sb.own_idx) sb.own_idx.alloc_zero(*be_, own_cap * (u64)own_nsrc_);  // epoch 0: never valid
+  sb.own_pos.reserve(*be_, (size_t)n, (size_t)(n + n / 4 + 1024));
+  if (own_fill_ + n > (int64_t)(own_cap / 2)) {
+    be_->fill_u64(own_keys_, kEmptyKey, own_cap);
     own_fill_ = 0;
   }
   own_fill_ += n;
@@ -1356,7 +1220,7 @@ bool Engine::group_entries(const u64* recv_keys, int64_t n, int buf,
   ga.keys = recv_keys;
   ga.n = n;
   ga.okeys = own_keys_;
-  ga.ocap = own_cap_;
+  ga.ocap = own_cap;
   ga.opos = sb.own_pos;
   ga.oidx = sb.own_idx;
   ga.g.nsrc = nsrc;
@@ -1385,19 +1249,19 @@ void Engine::w_forward_backward(const BatchView& b, const float* pulled, int64_t
   if (ng > 1 && cfg_.sum_slices)
     throw std::invalid_argument("sum_slices: at most 32 slices per step (ordered pushes: any count)");
   // slice group `group` of the step: its rows, its slices (>= 2 when grouped)
-  const u32* posk = pos_;
+  const u32* posk = ws_->pos;
   const BatchView bk = group_view(b, St, group, posk);
   const int S = group_slices(St, group);
   const int ps = pstride();
   const bool masks = S > 1 && !cfg_.sum_slices;
   const int32_t* srows = slice_rows_dev(b, St) + (int64_t)group * kSliceGroup;
-  const bool direct = inv_valid_ && red_pairs_ && S == 1 &&
+  const bool direct = ws_->inv_valid && red_pairs_ && S == 1 &&
                       (cfg_.model.kind == kLR || fm_vals_) &&
                       (double)scratch_.cap * S * ps < 4294967295.0;
   // the direct path's send buffer is zeroed by the scatter; the pulled rows
   // are placed once per step (every group reads the same ones)
   if (group == 0)
-    be_->scatter_rows(pulled, wpull_, send_map_, nullptr, n_send, vstride_,
+    be_->scatter_rows(pulled, wpull_, ws_->send_map, nullptr, n_send, vstride_,
                       direct ? grads_out : nullptr, grad_width());
   FwdArgs fa;
   fa.batch = bk;
@@ -1420,7 +1284,7 @@ void Engine::w_forward_backward(const BatchView& b, const float* pulled, int64_t
     if (!fa.red_pairs || !fa.agg_ok) throw std::logic_error("direct send path without reduction");
     // the bucket reduction writes the normalised send buffer (no gather)
     fa.red_out = grads_out;
-    fa.red_inv = inv_;
+    fa.red_inv = ws_->inv;
     fa.red_rows = srows;
     be_->forward_backward(fa);
     last_nsend_ = n_send;
@@ -1430,9 +1294,9 @@ void Engine::w_forward_backward(const BatchView& b, const float* pulled, int64_t
   GatherGradArgs ga;
   ga.grad = grad_;
   ga.grad_rw = grad_;
-  ga.tmask = masks ? tmask_ : nullptr;
-  ga.tmask_rw = masks ? tmask_ : nullptr;
-  ga.map = send_map_;
+  ga.tmask = masks ? tmask_.get() : nullptr;
+  ga.tmask_rw = masks ? tmask_.get() : nullptr;
+  ga.map = ws_->send_map;
   ga.n_max = n_send;
   ga.S = S;
   ga.pstride = ps;
@@ -1773,7 +1637,7 @@ LossStats Engine::read_stats(bool reset, int which) {
 
 int64_t Engine::n_unique() {
   int64_t n = 0;
-  be_->copy_d2h(&n, n_uniq_, sizeof(n));
+  be_->copy_d2h(&n, ws_->n_uniq, sizeof(n));
   return n;
 }
 
@@ -1839,7 +1703,7 @@ BatchView Engine::synth_batch(const SynthArgs& a0, int64_t slice_rows) {
   // caller-provided outputs (e.g. torch tensors) or the engine's staging buffers
   a.keys = a0.keys ? a0.keys : st_keys_;
   a.labels = a0.labels ? a0.labels : st_labels_;
-  if (!a0.fgid) a.fgid = cfg_.model.kind == kMVM ? st_fgid_ : nullptr;
+  if (!a0.fgid) a.fgid = cfg_.model.kind == kMVM ? st_fgid_.get() : nullptr;
   be_->synth_batch(a);
   BatchView b;
   b.keys = a.keys;
@@ -1879,10 +1743,10 @@ BatchView Engine::stage_host_batch_async(const BatchView& h) {
   astage_next_ ^= 1;
   StageSet& d = aset_[s];
   if (!d.keys) {
-    d.keys = balloc<u64>(*be_, cfg_.max_nnz);
-    d.rowptr = balloc<int32_t>(*be_, cfg_.max_rows + 1);
-    d.fgid = balloc<int32_t>(*be_, cfg_.max_nnz);
-    d.labels = balloc<float>(*be_, cfg_.max_rows);
+    d.keys.alloc(*be_, cfg_.max_nnz);
+    d.rowptr.alloc(*be_, cfg_.max_rows + 1);
+    d.fgid.alloc(*be_, cfg_.max_nnz);
+    d.labels.alloc(*be_, cfg_.max_rows);
   }
   auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t bk = sizeof(u64) * h.nnz, br = h.row_ptr ? sizeof(int32_t) * (h.rows + 1) : 0,
@@ -1902,8 +1766,8 @@ BatchView Engine::stage_host_batch_async(const BatchView& h) {
   astage_last_ = s;
   BatchView b = h;
   b.keys = d.keys;
-  b.row_ptr = h.row_ptr ? d.rowptr : nullptr;
-  b.fgid = h.fgid ? d.fgid : nullptr;
+  b.row_ptr = h.row_ptr ? d.rowptr.get() : nullptr;
+  b.fgid = h.fgid ? d.fgid.get() : nullptr;
   b.labels = d.labels;
   return b;
 }
@@ -1944,19 +1808,18 @@ static void par_copy(void* dst, const void* src, size_t bytes) {
 template <typename Sink>
 void Engine::d2h_stream(const void* src, size_t bytes, Sink sink) {
   if (bytes == 0) return;
-  for (void*& p : stage_io_)
-    if (!p) p = be_->staging_alloc(kStageChunk);
+  for (auto& p : stage_io_) p.ensure(*be_, kStageChunk);
   const char* s = static_cast<const char*>(src);
   int cur = 0;
-  be_->copy_d2h_async(stage_io_[0], s, bytes < kStageChunk ? bytes : kStageChunk);
+  be_->copy_d2h_async(stage_io_[0].get(), s, bytes < kStageChunk ? bytes : kStageChunk);
   be_->synchronize();
   for (size_t off = 0; off < bytes;) {
     const size_t len = bytes - off < kStageChunk ? bytes - off : kStageChunk;
     const size_t nxt = off + len;
     if (nxt < bytes)  // the next chunk's DMA runs while the host consumes this one
-      be_->copy_d2h_async(stage_io_[cur ^ 1], s + nxt,
+      be_->copy_d2h_async(stage_io_[cur ^ 1].get(), s + nxt,
                           bytes - nxt < kStageChunk ? bytes - nxt : kStageChunk);
-    sink(stage_io_[cur], off, len);
+    sink(stage_io_[cur].get(), off, len);
     be_->synchronize();
     off = nxt;
     cur ^= 1;
@@ -1966,15 +1829,14 @@ void Engine::d2h_stream(const void* src, size_t bytes, Sink sink) {
 template <typename Fill>
 void Engine::h2d_stream(void* dst, size_t bytes, Fill fill) {
   if (bytes == 0) return;
-  for (void*& p : stage_io_)
-    if (!p) p = be_->staging_alloc(kStageChunk);
+  for (auto& p : stage_io_) p.ensure(*be_, kStageChunk);
   char* d = static_cast<char*>(dst);
   int cur = 0;
   for (size_t off = 0; off < bytes;) {
     const size_t len = bytes - off < kStageChunk ? bytes - off : kStageChunk;
-    fill(stage_io_[cur], off, len);  // overlaps the previous chunk's DMA
+    fill(stage_io_[cur].get(), off, len);  // overlaps the previous chunk's DMA
     be_->synchronize();              // (that DMA read the other buffer)
-    be_->copy_h2d_async(d + off, stage_io_[cur], len);
+    be_->copy_h2d_async(d + off, stage_io_[cur].get(), len);
     off += len;
     cur ^= 1;
   }
@@ -1985,20 +1847,16 @@ void Engine::export_into(u64* keys, u32* words, int64_t n) {
   const int W = state_words();
   if (n != table_size()) throw std::invalid_argument("export_into: n must equal table_size()");
   if (n == 0) return;
-  u64* dk = balloc<u64>(*be_, n);
-  u32* dw = balloc<u32>(*be_, n * W);
-  const int64_t got = be_->table_export(table_, dk, dw, n);
-  if (got == n) {
-    d2h_stream(dk, sizeof(u64) * n, [&](const void* c, size_t o, size_t b) {
-      par_copy((char*)keys + o, c, b);
-    });
-    d2h_stream(dw, sizeof(u32) * n * W, [&](const void* c, size_t o, size_t b) {
-      par_copy((char*)words + o, c, b);
-    });
-  }
-  be_->free(dk);
-  be_->free(dw);
-  if (got != n) throw std::runtime_error("export_table: live slot count mismatch");
+  DeviceBuffer<u64> dk(*be_, n);
+  DeviceBuffer<u32> dw(*be_, n * W);
+  if (be_->table_export(table_, dk, dw, n) != n)
+    throw std::runtime_error("export_table: live slot count mismatch");
+  d2h_stream(dk, sizeof(u64) * n, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)keys + o, c, b);
+  });
+  d2h_stream(dw, sizeof(u32) * n * W, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)words + o, c, b);
+  });
 }
 
 void Engine::export_table(std::vector<u64>& keys, std::vector<u32>& words) {
@@ -2020,8 +1878,8 @@ void Engine::import_from(const u64* keys, const u32* words, int64_t n) {
   const int W = state_words();
   if (n <= 0) return;
   guard_inserts(n);
-  u64* dk = balloc<u64>(*be_, n);
-  u32* dw = balloc<u32>(*be_, n * W);
+  DeviceBuffer<u64> dk(*be_, n);
+  DeviceBuffer<u32> dw(*be_, n * W);
   h2d_stream(dk, sizeof(u64) * n, [&](void* c, size_t o, size_t b) {
     par_copy(c, (const char*)keys + o, b);
   });
@@ -2029,8 +1887,6 @@ void Engine::import_from(const u64* keys, const u32* words, int64_t n) {
     par_copy(c, (const char*)words + o, b);
   });
   table_from_device(dk, dw, n);
-  be_->free(dk);
-  be_->free(dw);
 }
 
 void Engine::import_table(const std::vector<u64>& keys, const std::vector<u32>& words) {
@@ -2055,22 +1911,17 @@ void Engine::save(const std::string& path) {
   ok = ok && std::fwrite(hdr, sizeof(hdr), 1, f) == 1;
   ok = ok && std::fwrite(&un, sizeof(un), 1, f) == 1;
   if (n > 0 && ok) {
-    u64* dk = balloc<u64>(*be_, n);
-    u32* dw = balloc<u32>(*be_, n * W);
-    const int64_t got = be_->table_export(table_, dk, dw, n);
-    if (got == n) {
-      auto put = [&](const void* c, size_t, size_t b) {
-        ok = ok && std::fwrite(c, 1, b, f) == b;
-      };
-      d2h_stream(dk, sizeof(u64) * n, put);
-      d2h_stream(dw, sizeof(u32) * n * W, put);
-    }
-    be_->free(dk);
-    be_->free(dw);
-    if (got != n) {
+    DeviceBuffer<u64> dk(*be_, n);
+    DeviceBuffer<u32> dw(*be_, n * W);
+    if (be_->table_export(table_, dk, dw, n) != n) {
       std::fclose(f);
       throw std::runtime_error("export_table: live slot count mismatch");
     }
+    auto put = [&](const void* c, size_t, size_t b) {
+      ok = ok && std::fwrite(c, 1, b, f) == b;
+    };
+    d2h_stream(dk, sizeof(u64) * n, put);
+    d2h_stream(dw, sizeof(u32) * n * W, put);
   }
   ok = (std::fclose(f) == 0) && ok;
   if (!ok) throw std::runtime_error("write failed: " + path);
@@ -2097,14 +1948,12 @@ void Engine::load(const std::string& path) {
   stale_stashes();
   if (n > 0) {
     guard_inserts((int64_t)n);
-    u64* dk = balloc<u64>(*be_, n);
-    u32* dw = balloc<u32>(*be_, n * W);
+    DeviceBuffer<u64> dk(*be_, n);
+    DeviceBuffer<u32> dw(*be_, n * W);
     auto get = [&](void* c, size_t, size_t b) { ok = ok && std::fread(c, 1, b, f) == b; };
     h2d_stream(dk, sizeof(u64) * n, get);
     h2d_stream(dw, sizeof(u32) * n * W, get);
     if (ok) table_from_device(dk, dw, (int64_t)n);
-    be_->free(dk);
-    be_->free(dw);
   }
   std::fclose(f);
   if (!ok) throw std::runtime_error("truncated checkpoint " + path);

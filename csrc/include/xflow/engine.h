@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "xflow/backend.h"
+#include "xflow/device_buffer.h"
 
 namespace xflow {
 
@@ -355,6 +356,29 @@ class Engine {
   void stage_release();
 
  private:
+  static const EngineConfig& validated(const EngineConfig& cfg);  // throws on a bad argument
+  EngineConfig cfg_;
+  std::unique_ptr<Backend> be_;  // first: every buffer below is destroyed before the backend
+  TableView table_;
+  // The table's address range (Backend::table_reserve; table_.words is its
+  // base, which moves when a backend re-allocates on commit): released when
+  // the engine -- or its constructor, throwing -- unwinds.
+  struct TableRange {
+    Engine* e = nullptr;
+    ~TableRange() {
+      if (e) e->be_->table_release(e->table_.words);
+    }
+  } table_range_;
+  // (table_.size / overflow, admit_.counters and scratch_'s arrays alias the
+  // owned buffers mon_, admit_counters_ and scratch_*_)
+  AdmitView admit_;              // counters == null: admission off
+  size_t table_bytes_ = 0;
+  ScratchView scratch_;
+  DeviceBuffer<unsigned char> admit_counters_;
+  DeviceBuffer<u64> scratch_keys_;
+  DeviceBuffer<unsigned char> scratch_stamps_;
+  DeviceBuffer<unsigned long long> scratch_claims_, scratch_ctl_;
+
   // chunked device<->host transfer through the staging pair (export / save,
   // import / load): sink(host chunk, byte offset, bytes) consumes each chunk
   // while the next one is in flight; fill(host chunk, offset, bytes)
@@ -364,26 +388,25 @@ class Engine {
   template <typename Fill>
   void h2d_stream(void* dst, size_t bytes, Fill fill);
   void table_from_device(const u64* dk, const u32* dw, int64_t n);
-  void* stage_io_[2] = {nullptr, nullptr};
+  DeviceBuffer<char, Mem::kStaging> stage_io_[2];
+  void ensure_host_staging(int64_t n);  // push_host / pull_host device arrays of n keys
   void ensure_server_capacity(int64_t n, int buf = 0);
-  // worker buffer sets (see w_prepare): the members pos_, uniq_pos_, inv_,
-  // n_uniq_, send_pos_, send_map_, inv_valid_ describe set cur_wb_
+  // worker buffer sets (see w_prepare); ws_ is the current one
   struct WorkerSet {
-    u32* pos = nullptr;
-    u32* uniq_pos = nullptr;
-    u32* inv = nullptr;
-    int64_t* n_uniq = nullptr;
-    u32* send_pos = nullptr;
-    const u32* send_map = nullptr;
-    bool inv_valid = false;
-    unsigned long long* bcap = nullptr;  // scratch capacity of the set's batch (device)
+    DeviceBuffer<u32> pos;        // [max_nnz]
+    DeviceBuffer<u32> uniq_pos;   // [max_nnz]
+    DeviceBuffer<u32> inv;        // [scratch cap] slot -> send index (partitioned dedup, LR)
+    DeviceBuffer<int64_t> n_uniq;  // [1]
+    DeviceBuffer<u32> send_pos;   // [max_nnz]
+    const u32* send_map = nullptr;  // send order -> scratch slot (send_pos or uniq_pos)
+    bool inv_valid = false;       // inv describes the batch of the last w_prepare
+    DeviceBuffer<unsigned long long> bcap;  // scratch capacity of the set's batch (device)
   };
   WorkerSet wset_[2];
-  int cur_wb_ = 0;
-  void use_worker_set(int wb);
+  WorkerSet* ws_ = &wset_[0];
+  void use_worker_set(int wb);  // switches ws_; a set is allocated on first use
   // owner grouping for the one-launch multi-source apply (Backend::owner_group)
-  u64* own_keys_ = nullptr;      // owner scratch [own_cap_]
-  u64 own_cap_ = 0;
+  DeviceBuffer<u64> own_keys_;   // owner scratch
   int64_t own_fill_ = 0;         // entries registered since the last clear (upper bound of keys)
   int own_nsrc_ = 0;             // row stride of SrvBuf::own_idx
   u32 own_epoch_ = 0;
@@ -400,7 +423,6 @@ class Engine {
   // redirects the unique-key list (the sharded step's send buffer)
   void dedup_(const BatchView& b, int parts = 1, u64* uniq_keys_out = nullptr,
               bool want_inv = false, int64_t* n_copy = nullptr);
-  const u32* send_map_ = nullptr;  // send order -> scratch slot (send_pos_ or uniq_pos_)
   bool sharded_fm_compact() const {
     return red_pairs_ && cfg_.model.kind == kFM && cfg_.model.fm_math == kFmReference &&
            (double)scratch_.cap * slice_cap_ * pstride() < 4294967295.0;
@@ -409,96 +431,77 @@ class Engine {
   int vstride_ = 1;
   const float* pulled_weights(int buf, int64_t off) const;
 
-  EngineConfig cfg_;
-  std::unique_ptr<Backend> be_;
-  TableView table_;
-  AdmitView admit_;              // counters == null: admission off
-  size_t table_bytes_ = 0;
-  ScratchView scratch_;
-
   // worker buffers (backend memory)
-  u32* pos_ = nullptr;          // [max_nnz]
-  u64* uniq_keys_ = nullptr;    // [max_nnz]
-  u32* uniq_pos_ = nullptr;     // [max_nnz]
-  u32* uniq_slot_ = nullptr;    // [max_nnz]
-  int64_t* n_uniq_ = nullptr;   // [1]
-  u32* block_counts_ = nullptr; // dedup compaction workspace
-  u32* mon_ = nullptr;          // [4]: table size (u64), overflow_ (below)
-  u32* overflow_ = nullptr;     // [2]: scratch, table (= mon_ + 2)
-  float* wpull_ = nullptr;      // [scratch_cap * pstride]
-  float* grad_ = nullptr;       // [scratch_cap * slice_cap * pstride]
-  u32* tmask_ = nullptr;        // [scratch_cap]
+  DeviceBuffer<u64> uniq_keys_;    // [max_nnz]
+  DeviceBuffer<u32> uniq_slot_;    // [max_nnz]
+  DeviceBuffer<u32> block_counts_; // dedup compaction workspace
+  DeviceBuffer<u32> mon_;          // [4]: table size (u64), overflow_ (below)
+  u32* overflow_ = nullptr;        // [2]: scratch, table (= mon_ + 2)
+  DeviceBuffer<float> wpull_;      // [scratch_cap * pstride]
+  DeviceBuffer<float> grad_;       // [scratch_cap * slice_cap * pstride]
+  DeviceBuffer<u32> tmask_;        // [scratch_cap]
   // HIP LR gradient reduction workspace (FwdArgs::red_*), null when unused
-  u64* red_pairs_ = nullptr;
-  u64* red_sorted_ = nullptr;
-  int64_t red_sorted_words_ = 0;  // u64 words of red_sorted_
-  u32* red_hist_ = nullptr;
-  u32* red_tot_ = nullptr;
-  u32* red_count_ = nullptr;
-  float* red_rowv_ = nullptr;    // MVM: per-row loss*M (FwdArgs::red_rowv)
-  float* lr_grad_ = nullptr;     // LR-FTRL fused step: unique-order gradients [max_nnz][slice_cap]
-  float* lr_nz_ = nullptr;       // LR-FTRL fused step: pulled (n, z) [max_nnz][2]
+  DeviceBuffer<u64> red_pairs_;
+  DeviceBuffer<u64> red_sorted_;
+  DeviceBuffer<u32> red_hist_;
+  DeviceBuffer<u32> red_tot_;
+  DeviceBuffer<u32> red_count_;
+  DeviceBuffer<float> red_rowv_;    // MVM: per-row loss*M (FwdArgs::red_rowv)
+  DeviceBuffer<float> lr_grad_;     // LR-FTRL fused step: unique-order gradients [max_nnz][slice_cap]
+  DeviceBuffer<float> lr_nz_;       // LR-FTRL fused step: pulled (n, z) [max_nnz][2]
   int64_t nnz_seen_ = 0;          // most occurrences in one batch (ScratchView::grow)
-  u32* lr_mask_ = nullptr;       // LR-FTRL fused step, S > 1: unique-order slice bits [max_nnz]
-  float* fm_grad_ = nullptr;     // reference FM fused step: unique-order (B, C) [max_nnz][2]
-  float* row_grad_ = nullptr;    // MVM / standard FM fused step (one slice): unique-order rows [max_nnz][pstride]
-  float* fm_w_ = nullptr;        // reference FM, grouped step: pulled per-parameter weights [max_nnz][pstride]
+  DeviceBuffer<u32> lr_mask_;       // LR-FTRL fused step, S > 1: unique-order slice bits [max_nnz]
+  DeviceBuffer<float> fm_grad_;     // reference FM fused step: unique-order (B, C) [max_nnz][2]
+  DeviceBuffer<float> row_grad_;    // MVM / standard FM fused step (one slice): unique-order rows [max_nnz][pstride]
+  DeviceBuffer<float> fm_w_;        // reference FM, grouped step: pulled per-parameter weights [max_nnz][pstride]
   int red_nb_ = 0;
   int red_nsub_ = 1;
   int red_maxb_ = 0;  // FwdArgs::red_maxb
   int red_groups_ = 0;  // FwdArgs::red_groups
-  unsigned long long* bcap_ = nullptr;  // current worker set's batch scratch capacity
-  u32* inv_ = nullptr;          // [scratch cap] slot -> send index (partitioned dedup, LR)
-  bool inv_valid_ = false;      // inv_ describes the batch of the last w_prepare
   void set_reduction(FwdArgs& fa) const;
   // CSR gradients (CsrOut): the single-rank step of several slices, LR-FTRL on
   // 16-byte slots or compact reference-FM rows -- one producer pass, one
   // reduction and one apply for any slice count
-  u32* csr_off_ = nullptr;      // [max_nnz]
-  u32* csr_cnt_ = nullptr;      // [max_nnz]
-  float* csr_vent_ = nullptr;   // standard FM / MVM: full-row entries [max_nnz][csr_row_words(P)]
+  DeviceBuffer<u32> csr_off_;      // [max_nnz]
+  DeviceBuffer<u32> csr_cnt_;      // [max_nnz]
+  DeviceBuffer<float> csr_vent_;   // standard FM / MVM: full-row entries [max_nnz][csr_row_words(P)]
   // MVM: repeated-field rows' records and fixed-point sums (MvmDup, backend.h)
-  float* mdup_rec_ = nullptr;
-  long long* mdup_acc_ = nullptr;
-  u32* mdup_claim_ = nullptr;
-  int64_t mdup_cap_ = 0;
+  DeviceBuffer<float> mdup_rec_;
+  DeviceBuffer<long long> mdup_acc_;
+  DeviceBuffer<u32> mdup_claim_;
   int mdup_ew_ = 0;
   int64_t csr_steps_ = 0;
   void train_step_csr(const BatchView& b, int S, int slog2);
-  u32* csr_doff_ = nullptr;     // [max_nnz + 1] dense offsets (worker pack)
-  u32* csr_long_ = nullptr;     // [1 + max keys] the applies' deferred long chains
-  int64_t csr_long_cap_ = 0;
+  DeviceBuffer<u32> csr_doff_;     // [max_nnz + 1] dense offsets (worker pack)
+  StreamBuffer<u32> csr_long_;     // [1 + max keys] the applies' deferred long chains
   u32* csr_long_list(int64_t n);
-  u32* csr_roff_ = nullptr;     // received entries' offsets (server)
-  int64_t csr_roff_cap_ = 0;
+  StreamBuffer<u32> csr_roff_;     // received entries' offsets (server)
   // the forward/backward both CSR entry points run: producer pass over every
   // slice with dests unique * 2^slog2 + slice, CSR reduction into csr_*_
   void csr_forward_backward(const BatchView& b, int slog2, const int32_t* srows, bool normalise);
   bool reduction_masks(bool unique_positions) const;
   void ensure_inv();
-  LossStats* stats_ = nullptr;  // [1]
-  u32* send_pos_ = nullptr;     // [max_nnz]
-  int64_t* bucket_ws_ = nullptr;  // [2*256]
-  int32_t* slice_rows_ = nullptr;  // [slice_rows_cap_]
-  int64_t slice_rows_cap_ = 0;
+  DeviceBuffer<LossStats> stats_;  // [1]
+  DeviceBuffer<int64_t> bucket_ws_;  // [2*256]
+  DeviceBuffer<int32_t> slice_rows_;  // [kSliceGroup per slice group]
   int64_t cached_rows_ = -1, cached_slice_rows_ = -1;
   int cached_S_ = -1;
   int64_t last_nsend_ = 0;
 
   // async staging sets (stage_host_batch_async)
   struct StageSet {
-    u64* keys = nullptr;
-    int32_t* rowptr = nullptr;
-    int32_t* fgid = nullptr;
-    float* labels = nullptr;
+    DeviceBuffer<u64> keys;
+    DeviceBuffer<int32_t> rowptr;
+    DeviceBuffer<int32_t> fgid;
+    DeviceBuffer<float> labels;
   };
   StageSet aset_[2];
   int astage_next_ = 0, astage_last_ = -1;
   // staging batch buffers (backend memory)
-  u64* st_keys_ = nullptr;
-  int32_t* st_rowptr_ = nullptr;
-  int32_t* st_fgid_ = nullptr;
-  float* st_labels_ = nullptr;
+  DeviceBuffer<u64> st_keys_;
+  DeviceBuffer<int32_t> st_rowptr_;
+  DeviceBuffer<int32_t> st_fgid_;
+  DeviceBuffer<float> st_labels_;
 
   // Server buffers: a pipelined step with staleness k applies a buffer's
   // pushes after the next k pulls (parallel/async_p2p.py), so k + 1 are live.
@@ -507,22 +510,19 @@ class Engine {
   static constexpr int kSrvBufs = 64;
  private:
   struct SrvBuf {
-    u32* slots = nullptr;        // table slot of each received key (s_pull)
-    int64_t cap = 0;
+    DeviceBuffer<u32> slots;     // table slot of each received key (s_pull)
     int64_t n = 0;
     const u64* keys = nullptr;   // the received keys (slots re-probed after a table growth)
     // LR-FTRL 16-byte slots: (n, z) as pulled, and whether no apply has
     // touched the table since that pull (then the first source's apply takes
     // its state from here instead of re-reading the table)
-    float* nz = nullptr;
+    DeviceBuffer<float> nz;
     bool nz_fresh = false;
     const float* vals = nullptr;  // s_pull outputs (fm_compact apply)
-    float* w = nullptr;           // s_pull(keep_weights) per-param weights
-    int64_t w_cap = 0;
+    DeviceBuffer<float> w;        // s_pull(keep_weights) per-param weights
     bool w_valid = false;
-    u32* own_pos = nullptr;       // owner grouping of the buffer's entries
-    int64_t own_pos_cap = 0;
-    u64* own_idx = nullptr;
+    DeviceBuffer<u32> own_pos;    // owner grouping of the buffer's entries
+    DeviceBuffer<u64> own_idx;
     SrcGroups grp;                // grp.oidx != null: s_pull grouped this buffer
   };
   SrvBuf srv_[kSrvBufs];
@@ -537,7 +537,7 @@ class Engine {
   // none) and polled by the host -- no event, no extra launch; each comes
   // with the cumulative insert bound queued before it
   static constexpr int kSnaps = 64;
-  HostSnap* snaps_ = nullptr;       // pinned host [kSnaps]
+  HostBuffer<HostSnap> snaps_;      // pinned host [kSnaps]
   int64_t snap_adds_[kSnaps] = {};
   bool snap_carried_ = false;       // an apply since the last inserts carries the next snapshot
   bool snap_ready(int64_t seq) const;
@@ -552,12 +552,11 @@ class Engine {
   double grow_s_ = 0.0;
   u64 max_segs_ = 0;                // segments of 2^max_log2_cap slots
   double monitor_wait_s_ = 0.0;
-  float* grp_nz_ = nullptr;                   // FM / MVM FTRL: the pull's (n, z) stash [unique][P]
-  unsigned long long* rec_count_ = nullptr;  // (count_records) device counter
-  u32* red_vmax_ = nullptr;                   // MVM: per-step scale words [2], dup words [2]
-  u32* text_ws_ = nullptr;                    // parse_text workspace
-  int64_t text_ws_words_ = 0;
-  long long* text_counts_ = nullptr;          // parse_text counts [7]
+  DeviceBuffer<float> grp_nz_;                   // FM / MVM FTRL: the pull's (n, z) stash [unique][P]
+  DeviceBuffer<unsigned long long> rec_count_;  // (count_records) device counter
+  DeviceBuffer<u32> red_vmax_;                   // MVM: per-step scale words [2], dup words [2]
+  DeviceBuffer<u32> text_ws_;                    // parse_text workspace
+  DeviceBuffer<long long> text_counts_;          // parse_text counts [7]
   mutable int vmax_parity_ = 0;
   bool rec_on_ = false;
   int log2_cap_ = 0, max_log2_cap_ = 31;
@@ -570,10 +569,9 @@ class Engine {
   static constexpr double kHardLoad = 0.9;
   void split_to(u64 nseg);              // split segments until there are nseg
 
-  u64* host_keys_dev_ = nullptr;   // push_host / pull_host staging
-  float* host_vals_dev_ = nullptr;
-  u32* host_slots_dev_ = nullptr;
-  int64_t host_cap_ = 0;
+  DeviceBuffer<u64> host_keys_dev_;   // push_host / pull_host staging
+  DeviceBuffer<float> host_vals_dev_;
+  DeviceBuffer<u32> host_slots_dev_;
 };
 
 }  // namespace xflow
