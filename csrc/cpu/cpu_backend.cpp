@@ -550,6 +550,50 @@ class CpuBackend final : public Backend {
       }
     }
   }
+  // The HIP prune kernel's algorithm (kernels_table.hip k_table_prune), one
+  // cluster after the other: the split's walk with slot_prunable as the "this
+  // key leaves" rule and nowhere to move a leaving key to.  A segment with no
+  // free slot has no cluster start and is left alone (impossible below load 1).
+  void table_prune(const TableView& t, const OptSpec& o, float max_n,
+                   unsigned long long* dropped) override {
+    const int W = t.L.stride;
+    const int g = t.seg_log2;
+    const u64 G = 1ull << g, m = G - 1, n = t.cap;
+    auto key_at = [&](u64 s) { return *reinterpret_cast<const u64*>(t.words + s * (u64)W); };
+    std::vector<u64> starts;
+    for (u64 i = 0; i < n; ++i) {
+      const u64 base = i & ~m, c = i & m;
+      if (key_at(base + c) != kEmptyKey && key_at(base + ((c - 1) & m)) == kEmptyKey)
+        starts.push_back(i);
+    }
+    auto free_slot = [&](u32* sp) {
+      sp[0] = sp[1] = 0xFFFFFFFFu;
+      for (int w = 2; w < W; ++w) sp[w] = 0u;
+    };
+    unsigned long long cnt = 0;
+    for (u64 i : starts) {
+      const u64 base = i & ~m, c = i & m;
+      auto at = [&](u64 off) { return base + ((c + off) & m); };
+      for (u64 d = 0; d < G; ++d) {
+        u32* sp = t.words + at(d) * (u64)W;
+        const u64 key = *reinterpret_cast<const u64*>(sp);
+        if (key == kEmptyKey) break;
+        if (slot_prunable(sp, key, t.L, o, max_n)) {
+          free_slot(sp);
+          ++cnt;
+        } else {
+          u64 off = ((fmix64(key) & m) - c) & m;
+          while (off < d && key_at(at(off)) != kEmptyKey) ++off;
+          if (off != d) {
+            std::memcpy(t.words + at(off) * (u64)W, sp, sizeof(u32) * W);
+            free_slot(sp);
+          }
+        }
+      }
+    }
+    *t.size -= cnt;
+    *dropped += cnt;
+  }
   // The table's range: address space reserved with mmap (pages get memory
   // when first touched), so growth never copies; a plain allocation that is
   // re-allocated on growth when the reservation fails.

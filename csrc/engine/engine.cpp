@@ -1649,6 +1649,29 @@ int64_t Engine::table_size() {
   return (int64_t)n;
 }
 
+// Drop every key that meets the pruning rule (slot_prunable, types.h).  Not
+// part of a step: call it between steps (epoch ends, before a model ships).
+// Slots of the staying keys change, so pulled-but-not-applied server buffers
+// are looked up again: an entry whose key was dropped gets the absent slot and
+// its push is skipped, like a not-admitted key's.  The admission filter is not
+// touched.  Capacity is not given back: the point is a lower load, shorter
+// chains and later growth.
+int64_t Engine::prune(float max_n) {
+  if (std::isnan(max_n)) throw std::invalid_argument("prune: max_n must not be NaN");
+  if (snap_carried_) close_snapshot();  // (as guard_inserts: it predates the prune)
+  poll_snapshots(snap_seq_);
+  if (!pruned_dev_) pruned_dev_.alloc_zero(*be_, 1);
+  be_->table_prune(table_, cfg_.opt, max_n, pruned_dev_);
+  unsigned long long total = 0;
+  be_->copy_d2h(&total, pruned_dev_, sizeof(total));  // (synchronising)
+  (void)table_size();  // (re-bases the capacity monitor)
+  stale_stashes();
+  remap_server_slots();
+  const int64_t dropped = (int64_t)total - pruned_keys_;
+  pruned_keys_ = (int64_t)total;
+  return dropped;
+}
+
 std::vector<uint8_t> Engine::admit_counts(const std::vector<u64>& keys) {
   std::vector<uint8_t> out(keys.size(), 0);
   if (!admit_.counters) return out;

@@ -182,6 +182,8 @@ void Trainer::train_epochs(int epochs) {
   for (int epoch = 0; epoch < epochs; ++epoch) {
     PrefetchReader reader(path, (size_t)cfg_.train_block_bytes);
     while (reader.next(blk)) train_block(blk);
+    if (cfg_.prune_every > 0 && (epoch + 1) % cfg_.prune_every == 0)
+      engine_->prune(cfg_.prune_max_n);
     if ((epoch + 1) % 30 == 0 && cfg_.verbose) out() << "epoch : " << epoch << std::endl;
   }
   engine_->synchronize();

@@ -271,14 +271,22 @@ class HipBackend final : public Backend {
     hip::launch_table_prefill(t, n, seed, stream_);
   }
   void table_split(const TableView& t, u64 s0, u64 k) override {
-    const size_t words = (size_t)(((k << t.seg_log2) + 63) / 64);
-    if (words > split_marks_words_) {
-      if (split_marks_) (void)hipFree(split_marks_);
-      split_marks_ = nullptr;
-      XF_HIP_CHECK(hipMalloc(&split_marks_, words * sizeof(u64)));
-      split_marks_words_ = words;
-    }
+    ensure_marks(t, k);
     hip::launch_table_split(t, s0, k, split_marks_, stream_);
+  }
+  // in launches of at most 2^28 slots over the split's marks workspace
+  void table_prune(const TableView& t, const OptSpec& o, float max_n,
+                   unsigned long long* dropped) override {
+    const int g = t.seg_log2;
+    const u64 nseg = t.cap >> g;
+    const u64 per_launch = g >= 28 ? 1 : (1ull << (28 - g));
+    XF_HIP_CHECK(hipMemsetAsync(counter_, 0, sizeof(unsigned long long), stream_));
+    for (u64 s0 = 0; s0 < nseg; s0 += per_launch) {
+      const u64 k = nseg - s0 < per_launch ? nseg - s0 : per_launch;
+      ensure_marks(t, k);
+      hip::launch_table_prune(t, o, max_n, s0, k, split_marks_, counter_, stream_);
+    }
+    hip::launch_table_prune_finish(t.size, dropped, counter_, stream_);
   }
 
   // ---- the table's address range (virtual memory management) ----
@@ -413,6 +421,16 @@ class HipBackend final : public Backend {
   bool waited_used_[2] = {false, false};
   u64* split_marks_ = nullptr;
   size_t split_marks_words_ = 0;
+  // the cluster-start bitmap of k segments (table_split, table_prune)
+  void ensure_marks(const TableView& t, u64 k) {
+    const size_t words = (size_t)(((k << t.seg_log2) + 63) / 64);
+    if (words > split_marks_words_) {
+      if (split_marks_) (void)hipFree(split_marks_);
+      split_marks_ = nullptr;
+      XF_HIP_CHECK(hipMalloc(&split_marks_, words * sizeof(u64)));
+      split_marks_words_ = words;
+    }
+  }
   struct VmChunk {
     size_t off, bytes;
     hipMemGenericAllocationHandle_t h;

@@ -49,6 +49,13 @@ void launch_table_import(const TableView& t, const u64* keys, const u32* words, 
 void launch_table_prefill(const TableView& t, int64_t n, u64 seed, hipStream_t st);
 // growth: split segments [s0, s0 + k) (marks: (k << seg_log2) / 64 words of scratch)
 void launch_table_split(const TableView& t, u64 s0, u64 k, u64* marks, hipStream_t st);
+// pruning: drop the slot_prunable keys of segments [s0, s0 + k), adding their
+// number to *count (marks as for the split); then *size -= *count,
+// *total += *count
+void launch_table_prune(const TableView& t, const OptSpec& o, float max_n, u64 s0, u64 k,
+                        u64* marks, unsigned long long* count, hipStream_t st);
+void launch_table_prune_finish(unsigned long long* size, unsigned long long* total,
+                               const unsigned long long* count, hipStream_t st);
 void launch_table_nonzero(const TableView& t, const OptSpec& o, unsigned long long* counter,
                           hipStream_t st);
 

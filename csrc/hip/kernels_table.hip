@@ -2431,6 +2431,115 @@ void launch_table_split(const TableView& t, u64 s0, u64 k, u64* marks, hipStream
   XF_HIP_CHECK(hipGetLastError());
 }
 
+// Pruning (Backend::table_prune): drop the keys of segments [s0, s0 + k) that
+// meet slot_prunable.  The split's walk with another "this key leaves" rule
+// and no buddy segment: k_table_split_marks marks the cluster starts before
+// any slot changes, then one lane per cluster walks it in order.  At walk
+// position d every slot before d is final: a leaving key's slot is freed; a
+// staying key goes to the first free slot from its home on -- a slot freed
+// earlier in the walk, or d itself.  Staying keys only move backwards inside
+// their own cluster, so lanes never meet and no insert can overflow.  A
+// segment with no free slot has no cluster start and is left alone; that
+// cannot happen below load 1 (inserts stop at probe_limit <= segment slots,
+// and the engine grows the table long before).
+// LR16: LR-FTRL 16-byte slots (key, n, z), each read and written as one
+// 16-byte access.
+template <bool LR16>
+__global__ void __launch_bounds__(kBlock) k_table_prune(TableView t, OptSpec o, float max_n,
+                                                        u64 s0, u64 k,
+                                                        const u64* __restrict__ marks,
+                                                        unsigned long long* dropped) {
+  const int g = t.seg_log2;
+  const u64 G = 1ull << g, m = G - 1;
+  const u64 n = k << g;
+  const int W = t.L.stride;
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  unsigned int drops = 0;
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (!((marks[i >> 6] >> (i & 63)) & 1ull)) continue;
+    const u64 base = (s0 << g) + (i & ~m), c = i & m;
+    auto slot_at = [&](u64 off) { return t.words + (base + ((c + off) & m)) * (u64)W; };
+    if constexpr (LR16) {
+      const uint4 kFree = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u);
+      for (u64 d = 0; d < G; ++d) {
+        uint4* sp = reinterpret_cast<uint4*>(slot_at(d));
+        const uint4 v = *sp;
+        const u64 key = (u64)v.x | ((u64)v.y << 32);
+        if (key == kEmptyKey) break;
+        const float fn = __uint_as_float(v.z), fz = __uint_as_float(v.w);
+        if (param_prunable(ftrl_weight(fz, fn, o.ftrl), fn, kFTRL, max_n)) {
+          *sp = kFree;
+          ++drops;
+        } else {
+          u64 off = ((fmix64(key) & m) - c) & m;  // home, in [0, d]
+          while (off < d && *reinterpret_cast<const u64*>(slot_at(off)) != kEmptyKey) ++off;
+          if (off != d) {
+            *reinterpret_cast<uint4*>(slot_at(off)) = v;
+            *sp = kFree;
+          }
+        }
+      }
+    } else {
+      auto free_slot = [&](u32* sp) {
+        sp[0] = 0xFFFFFFFFu;
+        sp[1] = 0xFFFFFFFFu;
+        for (int w = 2; w < W; ++w) sp[w] = 0u;
+      };
+      for (u64 d = 0; d < G; ++d) {
+        u32* sp = slot_at(d);
+        const u64 key = *reinterpret_cast<const u64*>(sp);
+        if (key == kEmptyKey) break;
+        if (slot_prunable(sp, key, t.L, o, max_n)) {
+          free_slot(sp);
+          ++drops;
+        } else {
+          u64 off = ((fmix64(key) & m) - c) & m;  // home, in [0, d]
+          while (off < d && *reinterpret_cast<const u64*>(slot_at(off)) != kEmptyKey) ++off;
+          if (off != d) {
+            u32* dp = slot_at(off);
+            for (int w = 0; w < W; ++w) dp[w] = sp[w];
+            free_slot(sp);
+          }
+        }
+      }
+    }
+  }
+  block_count_add<kBlock>(dropped, drops);
+}
+
+// *size -= *count, *total += *count (the prune's launches counted into *count)
+__global__ void k_table_prune_finish(unsigned long long* size, unsigned long long* total,
+                                     const unsigned long long* count) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned long long c = *count;
+    *size -= c;
+    *total += c;
+  }
+}
+
+void launch_table_prune(const TableView& t, const OptSpec& o, float max_n, u64 s0, u64 k,
+                        u64* marks, unsigned long long* count, hipStream_t st) {
+  const int64_t n = (int64_t)(k << t.seg_log2);
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_table_split_marks, dim3(grid_for(n, kBlock, 16384)), dim3(kBlock), 0, st,
+                     t, s0, k, marks);
+  XF_HIP_CHECK(hipGetLastError());
+  const bool lr16 = t.L.stride == 4 && t.L.P == 1 && t.L.opt == kFTRL && !t.L.has_flag;
+  if (lr16)
+    hipLaunchKernelGGL(k_table_prune<true>, dim3(grid_for(n, kBlock, 16384)), dim3(kBlock), 0, st,
+                       t, o, max_n, s0, k, (const u64*)marks, count);
+  else
+    hipLaunchKernelGGL(k_table_prune<false>, dim3(grid_for(n, kBlock, 16384)), dim3(kBlock), 0,
+                       st, t, o, max_n, s0, k, (const u64*)marks, count);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
+void launch_table_prune_finish(unsigned long long* size, unsigned long long* total,
+                               const unsigned long long* count, hipStream_t st) {
+  hipLaunchKernelGGL(k_table_prune_finish, dim3(1), dim3(64), 0, st, size, total, count);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
 __global__ void __launch_bounds__(kBlock) k_table_prefill(TableView t, int64_t n, u64 seed) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   unsigned int claims = 0;

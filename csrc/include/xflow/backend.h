@@ -770,6 +770,13 @@ class Backend {
   // that stay are re-packed inside their cluster (no tombstones).  Table size
   // is unchanged; slots of the split segments' keys change.
   virtual void table_split(const TableView& t, u64 s0, u64 k) = 0;
+  // Drop every key that meets the pruning rule (slot_prunable, types.h) from
+  // all segments of t; the keys that stay are re-packed inside their cluster
+  // as in table_split (no tombstones, no key leaves its segment).  Stream-
+  // ordered: the dropped count is subtracted from *t.size and added to
+  // *dropped (backend memory).  Slots of the staying keys change.
+  virtual void table_prune(const TableView& t, const OptSpec& o, float max_n,
+                           unsigned long long* dropped) = 0;
   // The slot array's address range: reserve the address space of max_bytes
   // once, commit memory as the table grows.  table_commit(base, bytes) makes
   // [base, base + bytes) usable and returns the (possibly moved) base: with

@@ -287,6 +287,13 @@ class Engine {
   void count_records(bool on);
   int64_t take_records();
   void grow_table(int log2_cap);
+  // Drop the keys whose weights are all exactly zero (slot_prunable, types.h:
+  // with FTRL also every n <= max_n; max_n < 0: no bound) and re-pack the
+  // keys that stay.  Returns the number dropped (syncs); pruned_keys() is the
+  // running total.  Only LR is prediction-neutral: a dropped FM / MVM key
+  // reads as never seen again (its latents take the lazy init).
+  int64_t prune(float max_n = -1.0f);
+  int64_t pruned_keys() const { return pruned_keys_; }
   // queue a snapshot of (table size, overflow flags) behind the step's
   // work; called at the end of every training step (fused or sharded)
   void end_step();
@@ -549,6 +556,8 @@ class Engine {
   int64_t known_adds_ = 0;          // cumulative insert bound queued before it
   int64_t queued_adds_ = 0;         // cumulative insert bound queued so far
   int64_t growths_ = 0, splits_ = 0, monitor_waits_ = 0;
+  DeviceBuffer<unsigned long long> pruned_dev_;  // [1] keys dropped by prune(), cumulative
+  int64_t pruned_keys_ = 0;
   double grow_s_ = 0.0;
   u64 max_segs_ = 0;                // segments of 2^max_log2_cap slots
   double monitor_wait_s_ = 0.0;

@@ -115,6 +115,28 @@ XF_HD float slot_weight(const u32* slot, u64 key, int p, const TableLayout& L,
                         : state_weight(key, pushed, st[p], 0.0f, p, L, o);
 }
 
+// Pruning rule (Backend::table_prune): the key in `slot` leaves the table when
+// every one of its P params has current weight exactly 0 and, with FTRL and
+// max_n >= 0, every param's n <= max_n (max_n < 0: no bound; max_n = 0: only
+// keys that were never pushed a non-zero gradient).  What follows from it: a
+// latent-param slot whose pushed flag is unset reads its (non-zero) lazy init
+// and stays; a prefilled key (zero state, flag set) leaves under every model
+// and optimiser.
+// (one param of current weight w; n: its FTRL n, unused with SGD)
+XF_HD bool param_prunable(float w, float n, int opt, float max_n) {
+  if (w != 0.0f) return false;
+  return !(opt == kFTRL && max_n >= 0.0f && !(n <= max_n));
+}
+XF_HD bool slot_prunable(const u32* slot, u64 key, const TableLayout& L, const OptSpec& o,
+                         float max_n) {
+  const float* st = reinterpret_cast<const float*>(slot + 2);
+  for (int p = 0; p < L.P; ++p) {
+    const float n = L.opt == kFTRL ? st[2 * p] : 0.0f;
+    if (!param_prunable(slot_weight(slot, key, p, L, o), n, L.opt, max_n)) return false;
+  }
+  return true;
+}
+
 // Weight of a key that is not in the table (lookup-only pulls at eval time).
 XF_HD float absent_weight(u64 key, int p, const TableLayout& L, const OptSpec& o) {
   if (p >= L.p_w) {

@@ -468,6 +468,9 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def("count_records", &Engine::count_records)
       .def("take_records", &Engine::take_records, py::call_guard<py::gil_scoped_release>())
       .def("grow_table", &Engine::grow_table, py::call_guard<py::gil_scoped_release>())
+      .def("prune", &Engine::prune, py::arg("max_n") = -1.0f,
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("pruned_keys", &Engine::pruned_keys)
       .def("end_step", &Engine::end_step, py::call_guard<py::gil_scoped_release>())
       .def_property_readonly("is_gpu", &Engine::is_gpu)
       .def_property_readonly("backend_name", [](Engine& e) { return e.backend().name(); })
@@ -778,6 +781,8 @@ PYBIND11_MODULE(_xflow_native, m) {
         if (d.contains("table_log2_cap")) c.table_log2_cap = d["table_log2_cap"].cast<int>();
         if (d.contains("admit_min_count")) c.admit_min_count = d["admit_min_count"].cast<int>();
         if (d.contains("admit_log2")) c.admit_log2 = d["admit_log2"].cast<int>();
+        if (d.contains("prune_every")) c.prune_every = d["prune_every"].cast<int>();
+        if (d.contains("prune_max_n")) c.prune_max_n = d["prune_max_n"].cast<float>();
         if (d.contains("sum_slices")) c.sum_slices = d["sum_slices"].cast<bool>();
         if (d.contains("verbose")) c.verbose = d["verbose"].cast<bool>();
         if (d.contains("model_spec")) c.model_spec = model_from(d["model_spec"].cast<py::dict>());

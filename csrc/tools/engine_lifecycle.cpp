@@ -111,6 +111,48 @@ void round_trip() {
   check(!keys.empty() && b.table_size() == a.table_size(), "table round trip");
 }
 
+// a prune round: prefilled (zero-state) keys leave, trained keys with a
+// non-zero weight stay and keep their values; a pulled-but-unapplied server
+// buffer is looked up again; the table keeps working afterwards
+void prune_round(EngineConfig c) {
+  // (MVM: latent values of order 1 keep the field products, and so the
+  // gradients and weights, away from exactly 0)
+  if (c.model.kind == kMVM) c.opt.v_init_scale = 1.0f;
+  Engine e(c);
+  e.prefill(300, 11);
+  for (uint64_t step = 0; step < 3; ++step) e.train_step(batch(e, 1, step));
+  std::vector<u64> keys;
+  std::vector<u32> words;
+  e.export_table(keys, words);
+  const std::vector<float> before = e.pull_host(keys);
+  const int64_t n0 = e.table_size();
+  const int64_t n = 64;
+  std::vector<u64> sk(n);
+  for (int64_t i = 0; i < n; ++i) sk[i] = (1ull << 20) + 5 * (u64)i;  // (no batch key: hash_space 2^16)
+  std::vector<float> vals(n * e.value_width()), grads(n * e.grad_width(), 0.25f);
+  e.s_pull(sk.data(), n, vals.data(), true, 0);  // (inserted with zero state: they leave too)
+  const int64_t dropped = e.prune(0.0f);
+  check(dropped >= 300 && e.table_size() == n0 + n - dropped, "prune count");
+  check(e.pruned_keys() == dropped && e.prune() >= 0, "prune total");
+  e.s_apply(sk.data(), grads.data(), nullptr, {0, n}, 1, 0);
+  check(!e.overflowed(), "prune overflowed");
+  const int P = e.config().model.P();
+  const std::vector<float> after = e.pull_host(keys);
+  std::vector<u64> k2;
+  e.export_table(k2, words);
+  size_t kept = 0;
+  for (size_t i = 0; i < keys.size(); ++i) {
+    bool zero = true;
+    for (int p = 0; p < P; ++p) zero = zero && before[i * P + p] == 0.0f;
+    if (zero) continue;  // (may have left)
+    ++kept;
+    for (int p = 0; p < P; ++p) check(after[i * P + p] == before[i * P + p], "prune moved a value");
+  }
+  check(kept > 0 && k2.size() >= kept, "prune kept nothing");
+  for (uint64_t step = 3; step < 5; ++step) e.train_step(batch(e, 8, step));
+  check(e.table_size() > 0 && !e.overflowed(), "training after a prune");
+}
+
 }  // namespace
 
 int main() {
@@ -127,6 +169,9 @@ int main() {
     growth();
     worker_sets();
     round_trip();
+    prune_round(config(kLR));
+    prune_round(config(kFM));
+    prune_round(config(kMVM));
   } catch (const std::exception& ex) {
     std::fprintf(stderr, "%s\n", ex.what());
     return 1;

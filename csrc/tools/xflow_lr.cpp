@@ -9,7 +9,7 @@
 // Optional flags after the positional args: --threads N --device D
 // --serial-slices --keep-remainder --sgd --fm-standard --mvm-fixed
 // --mvm-predict-compat --v-dim D --log2-cap N --admit-min-count N
-// --admit-log2 N --save PATH --load PATH.
+// --admit-log2 N --prune-every N --prune-max-n X --save PATH --load PATH.
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -62,6 +62,8 @@ int main(int argc, char* argv[]) {
     else if (a == "--log2-cap") cfg.table_log2_cap = std::atoi(next());
     else if (a == "--admit-min-count") cfg.admit_min_count = std::atoi(next());
     else if (a == "--admit-log2") cfg.admit_log2 = std::atoi(next());
+    else if (a == "--prune-every") cfg.prune_every = std::atoi(next());
+    else if (a == "--prune-max-n") cfg.prune_max_n = (float)std::atof(next());
     else if (a == "--train-block-bytes") cfg.train_block_bytes = std::atoll(next());
     else if (a == "--save") save = next();
     else if (a == "--load") load = next();

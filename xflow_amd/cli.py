@@ -66,6 +66,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--admit-log2", type=int, default=0,
                     help="admission filter bytes per rank = 2^N (6..32; 0: min(32, the table's "
                          "largest log2 capacity + 1))")
+    ap.add_argument("--prune-every", type=int, default=0,
+                    help="every N epochs drop the keys whose weights are all exactly zero "
+                         "(what L1 zeroed; 0: never)")
+    ap.add_argument("--prune-max-n", type=float, default=-1.0,
+                    help="--prune-every, FTRL: drop only keys with every n <= this (0: never "
+                         "pushed a non-zero gradient; negative: no bound)")
     ap.add_argument("--train-block-bytes", type=int, default=2 << 20)
     ap.add_argument("--test-block-bytes", type=int, default=0)
     ap.add_argument("--gpu-parse", action="store_true",
@@ -108,6 +114,7 @@ def config_from_args(a) -> TrainConfig:
         init_push=not a.no_init_push, pred_dir=a.pred_dir, write_pred=not a.no_pred_file,
         checkpoint_dir=a.save,
         save_every=a.save_every, resume_dir=a.resume,
+        prune_every=a.prune_every, prune_max_n=a.prune_max_n,
         metrics_file=a.metrics, async_p2p=a.async_p2p, async_ps=a.async_ps,
         staleness=a.staleness,
         model=ModelConfig(kind=kind, v_dim=a.v_dim, fm_math=a.fm_math, mvm_math=a.mvm_math,

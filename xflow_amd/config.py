@@ -134,6 +134,11 @@ class TrainConfig:
     checkpoint_dir: str = ""
     save_every: int = 0          # versioned checkpoint every N epochs (checkpoint.publish)
     resume_dir: str = ""         # versioned checkpoint root: resume from LATEST, save there
+    # prune the table (Engine.prune: drop keys whose weights are all exactly
+    # zero) at the end of every N-th epoch, 0: never; prune_max_n: with FTRL
+    # only keys with every n <= it (negative: no bound)
+    prune_every: int = 0
+    prune_max_n: float = -1.0
     metrics_file: str = ""
     async_p2p: bool = False      # lock-step staleness-k steps, pushes riding the next exchange
     # the asynchronous parameter server (parallel/async_ps.py): per-rank server

@@ -457,6 +457,22 @@ class Engine:
         self._sync_stream()
         self._e.grow_table(int(log2_cap))
 
+    def prune(self, max_n: float | None = None) -> int:
+        """Drop every key whose weights are all exactly zero -- with FTRL and
+        max_n given, only those with every n <= max_n (0: keys never pushed a
+        non-zero gradient) -- and re-pack the keys that stay; returns the number
+        dropped.  Call it between steps.  For LR a zero-weight key predicts
+        like an absent one, so no prediction changes; a dropped FM / MVM key
+        reads as never seen again (its latents take the lazy init).  Capacity
+        is not given back: the load falls and growth comes later."""
+        self._sync_stream()
+        return int(self._e.prune(-1.0 if max_n is None else float(max_n)))
+
+    @property
+    def pruned_keys(self) -> int:
+        """Keys dropped by prune() so far."""
+        return int(self._e.pruned_keys)
+
     def end_step(self) -> None:
         """Queue the step's capacity snapshot (the sharded steps call it via
         w_finish; raises if an earlier step overflowed)."""

@@ -349,6 +349,13 @@ class Trainer:
             if tot[3] > 0:
                 raise RuntimeError("table or dedup-scratch overflow during epoch %d: keys were "
                                    "dropped or isolated; grow --log2-cap / max_nnz" % self.epoch)
+            pruned = None
+            if cfg.prune_every > 0:
+                # every rank prunes its own table shard (nothing is pending
+                # after the flush / pause above; no communication needed)
+                if self.epoch % cfg.prune_every == 0:
+                    self.table.prune(cfg.prune_max_n)
+                pruned = int(xdist.all_sum([self.table.pruned_keys], self.device)[0])
             keys = self.table.table_size()
             rec = dict(event="epoch", epoch=self.epoch, steps=self.steps,
                        train_logloss=tot[0] / max(tot[1], 1.0),
@@ -359,6 +366,8 @@ class Trainer:
                        monitor_waits=self.table.monitor_waits)
             if cfg.engine.admit_min_count > 1:
                 rec["admit_min_count"] = cfg.engine.admit_min_count
+            if pruned is not None:
+                rec["pruned_keys"] = pruned  # (all ranks, since the run began)
             if aps is not None:
                 rec["async_ps"] = {k: v for k, v in aps.stats().items()
                                    if k in ("max_staleness", "max_lead", "bytes_moved",
