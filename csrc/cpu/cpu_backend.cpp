@@ -149,11 +149,6 @@ class CpuBackend final : public Backend {
     if (o.cap_out) *o.cap_out = s.cap;
   }
 
-  void scratch_reset(ScratchView s, const u32* pos, const int64_t* n_dev, int64_t n_max) override {
-    int64_t n = count_of(n_dev, n_max, n_max);
-    for (int64_t i = 0; i < n; ++i) s.keys[pos[i]] = kEmptyKey;
-  }
-
   void table_pull(const PullArgs& a) override {
     int64_t n = count_of(a.n_dev, a.n_host, a.n_max);
     const TableView& t = a.table;
@@ -235,7 +230,6 @@ class CpuBackend final : public Backend {
         for (int j = 0; j < S * ps; ++j) g[j] = 0.0f;
         if (a.masks_rw) a.masks_rw[row] = 0u;
       }
-      if (a.reset_pos) a.scratch.keys[a.reset_pos[i]] = kEmptyKey;
     }
   }
 
@@ -394,28 +388,6 @@ class CpuBackend final : public Backend {
       int64_t r = map ? map[i] : i;
       std::memcpy(dst + r * width, src + i * width, sizeof(float) * width);
     }
-  }
-  void gather_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
-                   int64_t n_max, int width, bool zero_src) override {
-    int64_t n = count_of(n_dev, n_max, n_max);
-    for (int64_t i = 0; i < n; ++i) {
-      float* s = const_cast<float*>(src) + (int64_t)map[i] * width;
-      std::memcpy(dst + i * width, s, sizeof(float) * width);
-      if (zero_src) std::memset(s, 0, sizeof(float) * width);
-    }
-  }
-  void gather_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev, int64_t n_max,
-                  bool zero_src) override {
-    int64_t n = count_of(n_dev, n_max, n_max);
-    for (int64_t i = 0; i < n; ++i) {
-      dst[i] = src[map[i]];
-      if (zero_src) const_cast<u32*>(src)[map[i]] = 0u;
-    }
-  }
-  void scatter_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                   int64_t n_max) override {
-    int64_t n = count_of(n_dev, n_max, n_max);
-    for (int64_t i = 0; i < n; ++i) dst[map[i]] = src[i];
   }
 
   void synth_batch(const SynthArgs& a) override {

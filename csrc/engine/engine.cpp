@@ -311,6 +311,64 @@ void Engine::set_reduction(FwdArgs& fa) const {
   fa.red_rowv = red_rowv_;
 }
 
+PullArgs Engine::pull_args(const u64* keys, const int64_t* n_dev, int64_t n, bool insert,
+                           u32* out_slot) const {
+  PullArgs pa;
+  pa.table = table_;
+  pa.opt = cfg_.opt;
+  pa.keys = keys;
+  pa.n_dev = n_dev;
+  pa.n_host = n_dev ? 0 : n;
+  pa.n_max = n;
+  pa.insert = insert;
+  pa.out_slot = out_slot;
+  return pa;
+}
+
+ApplyArgs Engine::apply_args(const u64* keys, const u32* slots, const int64_t* n_dev, int64_t n,
+                             int S) const {
+  ApplyArgs aa;
+  aa.table = table_;
+  aa.opt = cfg_.opt;
+  aa.keys = keys;
+  aa.slots = slots;
+  aa.n_dev = n_dev;
+  aa.n_host = n_dev ? 0 : n;
+  aa.n_max = n;
+  aa.S = S;
+  aa.pstride = pstride();
+  aa.P = cfg_.model.P();
+  aa.fm_D = cfg_.model.v_dim;
+  return aa;
+}
+
+FwdArgs Engine::train_fwd_args(const BatchView& b, const u32* pos, int S) const {
+  FwdArgs fa;
+  fa.batch = b;
+  fa.pos = pos;
+  fa.wpull = wpull_;
+  fa.grad = grad_;
+  fa.stats = stats_;
+  fa.model = cfg_.model;
+  fa.S = S;
+  fa.fx_bad = overflow_;
+  fa.fm_vals = fm_vals_;
+  set_reduction(fa);
+  return fa;
+}
+
+FwdArgs Engine::eval_fwd_args(const BatchView& b, float* pctr) const {
+  FwdArgs fa;
+  fa.batch = b;
+  fa.pos = ws_->pos;
+  fa.wpull = wpull_;
+  fa.pctr = pctr;
+  fa.stats = stats_ + 1;
+  fa.model = cfg_.model;
+  fa.fm_vals = fm_vals_;
+  return fa;
+}
+
 int Engine::slices_of(const BatchView& b) const {
   if (b.slice_rows <= 0 || b.rows <= 0) return 1;
   return (int)((b.rows + b.slice_rows - 1) / b.slice_rows);
@@ -553,27 +611,10 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   const bool fm = fm_vals_;
   // standard FM / MVM: full-row entries (k_red_csr_vec), applied by the packed CSR apply
   const bool rows = csr_full_rows();
-  ensure_inv();
   const int ew = rows ? csr_row_words(table_.L.P) : 0;
   float* stash = fm || rows ? grp_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P)
                             : lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
-  dedup_(b, 1, nullptr, true);
-  ws_->inv_valid = false;
-  be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
-  guard_inserts(b.nnz);
-
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = uniq_keys_;
-  pa.n_dev = ws_->n_uniq;
-  pa.n_max = b.nnz;
-  pa.insert = true;
-  pa.admit = admit_;
-  pa.out_slot = uniq_slot_;
-  pa.out_vals = wpull_;
-  pa.pstride = pstride();
-  pa.fm_vals = fm;
+  PullArgs pa = begin_fused_step(b, true, true);
   pa.out_nz = stash;
   be_->table_pull(pa);
 
@@ -581,18 +622,8 @@ void Engine::train_step_csr(const BatchView& b, int S, int slog2) {
   // expansion, as the slice-group path and the multi-rank send buffer do)
   csr_forward_backward(b, slog2, srows, true);
 
-  ApplyArgs aa;
-  aa.table = table_;
-  aa.opt = cfg_.opt;
-  aa.keys = uniq_keys_;
-  aa.slots = uniq_slot_;
-  aa.n_dev = ws_->n_uniq;
-  aa.n_max = b.nnz;
-  aa.S = S;
-  aa.pstride = pstride();
-  aa.P = cfg_.model.P();
+  ApplyArgs aa = apply_args(uniq_keys_, uniq_slot_, ws_->n_uniq, b.nnz, S);
   aa.fm_compact = fm;
-  aa.fm_D = cfg_.model.v_dim;
   aa.nz_stash = stash;
   aa.csr_off = csr_off_;
   aa.csr_cnt = csr_cnt_;
@@ -610,20 +641,10 @@ void Engine::csr_forward_backward(const BatchView& b, int slog2, const int32_t* 
                                   bool normalise) {
   csr_off_.ensure(*be_, (size_t)cfg_.max_nnz);  // (the CSR arrays' one allocation site)
   csr_cnt_.ensure(*be_, (size_t)cfg_.max_nnz);
-  FwdArgs fa;
-  fa.batch = b;
-  fa.pos = ws_->pos;
-  fa.wpull = wpull_;
-  fa.grad = grad_;
-  fa.stats = stats_;
-  fa.model = cfg_.model;
-  fa.S = 1 << slog2;
+  FwdArgs fa = train_fwd_args(b, ws_->pos, 1 << slog2);
   fa.agg_ok = true;  // (dests below max_nnz * 2^slog2 < 2^32: csr_slog2)
-  fa.fx_bad = overflow_;
-  set_reduction(fa);
   fa.red_nuq = ws_->n_uniq;
   fa.fm_compact = fm_vals_;
-  fa.fm_vals = fm_vals_;
   fa.red_csr.off = csr_off_;
   fa.red_csr.cnt = csr_cnt_;
   fa.red_csr.ent = red_pairs_;
@@ -678,6 +699,37 @@ void Engine::w_forward_backward_csr(const BatchView& b, const float* pulled, int
   be_->csr_totals(counts, world, encoded, csr_doff_, totals_out);
 }
 
+template <typename Source>
+void Engine::apply_by_source(const ApplyArgs& base, const std::vector<int64_t>& src_offsets,
+                             int buf, bool stash, const char* need_weights, Source source) {
+  const SrvBuf& sb = srv_[buf];
+  size_t first_src = 0;
+  while (first_src + 1 < src_offsets.size() && src_offsets[first_src + 1] <= src_offsets[first_src])
+    ++first_src;
+  for (size_t src = 0; src + 1 < src_offsets.size(); ++src) {
+    const int64_t o = src_offsets[src], c = src_offsets[src + 1] - o;
+    if (c <= 0) continue;
+    ApplyArgs aa = base;
+    aa.keys = base.keys + o;
+    aa.slots = base.slots + o;
+    aa.n_host = c;
+    aa.n_max = c;
+    source(aa, o, c);
+    if (aa.fm_compact) {
+      aa.pulled = pulled_weights(buf, o);
+      // compact value rows carry no per-parameter weights: a later source
+      // would expand its (B, C) with weights the earlier sources updated
+      if (!aa.pulled && src > first_src) throw std::logic_error(need_weights);
+    }
+    // the first source applied sees the state its pull saw; a key sent by
+    // several sources is updated by the earlier ones, so later sources re-read
+    if (stash) aa.nz_stash = sb.nz + 2 * o;  // (a fresh stash exists: s_pull)
+    stash = false;
+    attach_snapshot(aa);
+    be_->table_apply(aa);
+  }
+}
+
 void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* recv_ent,
                          const std::vector<int64_t>& src_offsets, int S, int buf) {
   if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
@@ -697,41 +749,19 @@ void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* 
     cnt = recv_cnt;
     ent = recv_ent;
   }
-  size_t first_src = 0;
-  while (first_src + 1 < src_offsets.size() && src_offsets[first_src + 1] <= src_offsets[first_src])
-    ++first_src;
-  for (size_t src = 0; src + 1 < src_offsets.size(); ++src) {
-    const int64_t o = src_offsets[src], c = src_offsets[src + 1] - o;
-    if (c <= 0) continue;
-    ApplyArgs aa;
-    aa.table = table_;
-    aa.opt = cfg_.opt;
-    aa.keys = recv_keys + o;
-    aa.slots = sb.slots + o;
-    aa.n_host = c;
-    aa.n_max = c;
-    aa.S = S;
-    aa.pstride = pstride();
-    aa.P = cfg_.model.P();
-    aa.fm_compact = fm_vals_;
-    aa.fm_D = cfg_.model.v_dim;
-    aa.csr_ew = csr_full_rows() ? csr_row_words(table_.L.P) : 0;
-    if (fm_vals_) {
-      aa.pulled = pulled_weights(buf, o);
-      if (!aa.pulled && src > first_src)
-        throw std::logic_error("s_apply_csr: compact FM rows of several sources need s_pull's weights");
-    }
-    // (entries normalised by the workers; entry indices are global)
-    aa.csr_off = off + o;
-    aa.csr_cnt = cnt + o;
-    aa.csr_ent = ent;
-    aa.csr_long = S > 16 ? csr_long_list(c) : nullptr;
-    aa.csr_long_cap = (int64_t)csr_long_.capacity();
-    if (stash) aa.nz_stash = sb.nz ? sb.nz + 2 * o : nullptr;
-    stash = false;
-    attach_snapshot(aa);
-    be_->table_apply(aa);
-  }
+  ApplyArgs base = apply_args(recv_keys, sb.slots, nullptr, 0, S);
+  base.fm_compact = fm_vals_;
+  base.csr_ew = csr_full_rows() ? csr_row_words(table_.L.P) : 0;
+  base.csr_ent = ent;
+  apply_by_source(base, src_offsets, buf, stash,
+                  "s_apply_csr: compact FM rows of several sources need s_pull's weights",
+                  [&](ApplyArgs& aa, int64_t o, int64_t c) {
+                    // (entries normalised by the workers; entry indices are global)
+                    aa.csr_off = off + o;
+                    aa.csr_cnt = cnt + o;
+                    aa.csr_long = S > 16 ? csr_long_list(c) : nullptr;
+                    aa.csr_long_cap = (int64_t)csr_long_.capacity();
+                  });
 }
 
 void Engine::csr_debug(std::vector<u32>& off, std::vector<u32>& cnt, std::vector<u32>& words) {
@@ -770,64 +800,44 @@ void Engine::train_step(const BatchView& b) {
   const int ps = pstride();
   const bool masks = P.masks;
   const int32_t* srows = slice_rows_dev(b, S);
-  const bool lr16 = P.lr16, lr16s = P.lr16s, uqm = P.uqm, fmu = P.fmu, fm_keep_w = P.fm_keep_w;
-  const bool rowu = P.rowu, fsu = P.fsu, grpst = P.grpst, uq = P.uq, upos = P.upos;
+  const bool uqm = P.uqm, fm_keep_w = P.fm_keep_w, uq = P.uq, upos = P.upos;
   // (dest * ps in 32 bits over unique indices or scratch slots, see plan_step)
   const double key_bound = upos ? (double)cfg_.max_nnz : (double)scratch_.cap;
-  if (lr16s) lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
-  if (lr16) {
-    ensure_inv();
-    lr_grad_.ensure(*be_, (size_t)cfg_.max_nnz * slice_cap_);
-    lr_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz);
+  // The unique-order gradient output, if the plan has one: the reduction
+  // writes it (through the slot -> unique map unless positions are unique
+  // indices already), the pull zeroes it, the apply reads it densely and
+  // neither maps nor clears it.
+  struct {
+    float* buf = nullptr;
+    int width = 0;            // floats per (key, slice)
+    bool normalised = false;  // the reduction divides by the slice's rows (else the apply does)
+    bool pull_zeroes = true;  // (the slice bits instead when several slices run: uq)
+  } uo;
+  const size_t un = (size_t)cfg_.max_nnz;
+  if (P.lr16) {
+    uo = {lr_grad_.ensure(*be_, un * slice_cap_), 1, true, true};
+  } else if (P.fmu) {  // (B, C) normalised before the expansion: 2 divisions a key, not P
+    uo = {fm_grad_.ensure(*be_, 2 * un * slice_cap_), 2, true, true};
+  } else if (P.rowu) {
+    // (one-slice standard FM: every unique key's row is written by the
+    // reduction -- each occurrence leaves a record, k_fm_std_red -- so the
+    // pull need not zero them)
+    uo = {row_grad_.ensure(*be_, un * ps * (P.fsu ? slice_cap_ : 1)), ps, false,
+          !(P.fsu && P.Sf == 1)};
   }
-  if (fmu) {
-    ensure_inv();
-    fm_grad_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * slice_cap_);
-  }
-  if (fm_keep_w) fm_w_.ensure(*be_, (size_t)cfg_.max_nnz * ps);
-  if (rowu) {
-    ensure_inv();
-    const int rs = fsu ? slice_cap_ : 1;
-    row_grad_.ensure(*be_, (size_t)cfg_.max_nnz * ps * rs);
-  }
-  if (grpst) grp_nz_.ensure(*be_, 2 * (size_t)cfg_.max_nnz * table_.L.P);
-  if (uq) lr_mask_.ensure(*be_, (size_t)cfg_.max_nnz);
-  if (upos) ensure_inv();
-  dedup_(b, 1, nullptr, upos || lr16 || fmu || rowu);
-  ws_->inv_valid = false;  // (the sharded step's send order is not this one)
-  if (upos) be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
-  guard_inserts(b.nnz);  // (<= nnz new keys; may grow the table first)
+  // the (n, z) the pull stashes in unique order for the first group's apply
+  float* nz = P.lr16 || P.lr16s ? lr_nz_.ensure(*be_, 2 * un)
+              : P.grpst         ? grp_nz_.ensure(*be_, 2 * un * table_.L.P)
+                                : nullptr;
+  if (fm_keep_w) fm_w_.ensure(*be_, un * ps);
+  if (uq) lr_mask_.ensure(*be_, un);
 
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = uniq_keys_;
-  pa.n_dev = ws_->n_uniq;
-  pa.n_max = b.nnz;
-  pa.insert = true;
-  pa.admit = admit_;
-  pa.out_slot = uniq_slot_;
-  pa.out_vals = wpull_;
-  pa.out_map = upos ? nullptr : ws_->uniq_pos.get();
-  pa.pstride = ps;
-  pa.fm_vals = fm_vals_;
+  PullArgs pa = begin_fused_step(b, upos || uo.buf, upos);
   if (fm_keep_w) pa.out_w = fm_w_;
-  if (lr16) {
-    pa.out_nz = lr_nz_;
-    pa.zero_out = lr_grad_;
-  }
-  if (lr16s) pa.out_nz = lr_nz_;
-  if (grpst) pa.out_nz = grp_nz_;
-  if (fmu) {
-    pa.zero_out = fm_grad_;
-    pa.zero_width = 2;
-  }
-  // (one-slice standard FM: every unique key's row is written by the
-  // reduction -- each occurrence leaves a record, k_fm_std_red -- so the
-  // pull need not zero them)
-  if (rowu && !(fsu && P.Sf == 1)) {
-    pa.zero_out = row_grad_;
-    pa.zero_width = ps;
+  pa.out_nz = nz;
+  if (uo.buf && uo.pull_zeroes) {
+    pa.zero_out = uo.buf;
+    pa.zero_width = uo.width;
   }
   if (uq) {  // S > 1: only a key's present slices are read, so only its bits need clearing
     pa.zero_out = reinterpret_cast<float*>(lr_mask_.get());
@@ -846,17 +856,8 @@ void Engine::train_step(const BatchView& b) {
     // table, which the earlier groups updated, instead of the pull's stash
     const bool stash = k == 0;
 
-    FwdArgs fa;
-    fa.batch = bk;
-    fa.pos = posk;
-    fa.wpull = wpull_;
-    fa.grad = grad_;
-    fa.stats = stats_;
-    fa.model = cfg_.model;
-    fa.S = Sg;
+    FwdArgs fa = train_fwd_args(bk, posk, Sg);
     fa.agg_ok = key_bound * Sg * ps < 4294967295.0;  // (32-bit dest * ps, see rows_ok)
-    fa.fx_bad = overflow_;
-    set_reduction(fa);
     if (upos) fa.red_nuq = ws_->n_uniq;
     // slice bits from the reduction (unique order with the outputs, else
     // slot-indexed), else per occurrence
@@ -866,72 +867,36 @@ void Engine::train_step(const BatchView& b) {
     // reference-math FM on the GPU reduction path: (B, C) rows, expanded by the apply
     fa.fm_compact = fa.red_pairs && fa.agg_ok && cfg_.model.kind == kFM &&
                     cfg_.model.fm_math == kFmReference;
-    fa.fm_vals = fm_vals_;
     if (fm_vals_ && !fa.fm_compact) throw std::logic_error("train_step: compact FM rows need the reduction");
-    // (unique-index positions: the outputs' rows are the dests' own)
-    const u32* oinv = upos ? nullptr : ws_->inv.get();
-    if (lr16) {
-      fa.red_out = lr_grad_;
-      fa.red_inv = oinv;
-      fa.red_rows = srk;
-    }
-    if (fmu) {  // (B, C) normalised before the expansion: 2 divisions a key, not P
-      fa.red_out = fm_grad_;
-      fa.red_inv = oinv;
-      fa.red_rows = srk;
-    }
-    if (rowu) {
-      fa.red_out = row_grad_;
-      fa.red_inv = oinv;
+    if (uo.buf) {
+      fa.red_out = uo.buf;
+      // (unique-index positions: the outputs' rows are the dests' own)
+      fa.red_inv = upos ? nullptr : ws_->inv.get();
+      if (uo.normalised) fa.red_rows = srk;
     }
     be_->forward_backward(fa);
 
-    ApplyArgs aa;
-    aa.table = table_;
-    aa.opt = cfg_.opt;
-    aa.keys = uniq_keys_;
-    aa.slots = uniq_slot_;
-    aa.n_dev = ws_->n_uniq;
-    aa.n_max = b.nnz;
-    aa.grads = grad_;
-    aa.grad_map = upos ? nullptr : ws_->uniq_pos.get();  // (slot- or unique-indexed rows)
-    aa.masks = masks ? tmask_.get() : nullptr;
-    aa.masks_rw = masks ? tmask_.get() : nullptr;
-    aa.zero_after = true;
-    aa.S = Sg;
-    aa.pstride = ps;
-    aa.P = cfg_.model.P();
+    ApplyArgs aa = apply_args(uniq_keys_, uniq_slot_, ws_->n_uniq, b.nnz, Sg);
     aa.sum_slices = cfg_.sum_slices;
-    aa.slice_rows = srk;
     aa.fm_compact = fa.fm_compact;
-    aa.fm_D = cfg_.model.v_dim;
     if (fm_keep_w) aa.pulled = fm_w_;
-    if (lr16) {  // unique-order, already normalised, zeroed by the next pull
-      aa.grads = lr_grad_;
-      aa.grad_map = nullptr;
-      aa.zero_after = false;
-      aa.slice_rows = nullptr;
-      aa.nz_stash = stash ? lr_nz_.get() : nullptr;
-    }
-    if (lr16s && stash) aa.nz_stash = lr_nz_;  // (unique order, as the apply's entries)
-    if (grpst && stash) aa.nz_stash = grp_nz_;
-    if (fmu) {  // unique-order normalised (B, C), zeroed by the next pull
-      aa.grads = fm_grad_;
-      aa.grad_map = nullptr;
-      aa.zero_after = false;
-      aa.slice_rows = nullptr;
-      aa.gstride = 2;
-    }
-    if (rowu) {  // unique-order rows, zeroed by the next pull
-      aa.grads = row_grad_;
-      aa.grad_map = nullptr;
-      aa.zero_after = false;
-      aa.gstride = ps;
+    aa.nz_stash = stash ? nz : nullptr;  // (unique order, as the apply's entries)
+    if (uo.buf) {  // already in unique order, zeroed by the next pull
+      aa.grads = uo.buf;
+      aa.gstride = uo.width;
+      aa.slice_rows = uo.normalised ? nullptr : srk;
+    } else {  // slot- or unique-indexed rows of raw sums
+      aa.grads = grad_;
+      aa.grad_map = upos ? nullptr : ws_->uniq_pos.get();
+      aa.zero_after = true;
+      aa.slice_rows = srk;
     }
     if (uq) {  // present slices by the unique-order bits (cleared by the next pull)
       aa.masks = lr_mask_;
-      aa.masks_rw = nullptr;
       aa.masks_clear = k + 1 < ng;  // (for the next group's reduction)
+    } else if (masks) {
+      aa.masks = tmask_;
+      aa.masks_rw = tmask_;
     }
     attach_snapshot(aa);
     be_->table_apply(aa);
@@ -939,34 +904,31 @@ void Engine::train_step(const BatchView& b) {
   end_step();
 }
 
+PullArgs Engine::begin_fused_step(const BatchView& b, bool want_inv, bool upos) {
+  if (want_inv) ensure_inv();
+  dedup_(b, 1, nullptr, want_inv);
+  ws_->inv_valid = false;  // (the sharded step's send order is not this one)
+  if (upos) be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
+  guard_inserts(b.nnz);  // (<= nnz new keys; may grow the table first)
+  PullArgs pa = pull_args(uniq_keys_, ws_->n_uniq, b.nnz, true, uniq_slot_);
+  pa.admit = admit_;
+  pa.out_vals = wpull_;
+  pa.out_map = upos ? nullptr : ws_->uniq_pos.get();
+  pa.pstride = pstride();
+  pa.fm_vals = fm_vals_;
+  return pa;
+}
+
 void Engine::eval_step(const BatchView& b, float* pctr) {
   use_worker_set(0);
   dedup_(b);
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = uniq_keys_;
-  pa.n_dev = ws_->n_uniq;
-  pa.n_max = b.nnz;
-  pa.insert = false;
-  pa.out_slot = uniq_slot_;
+  PullArgs pa = pull_args(uniq_keys_, ws_->n_uniq, b.nnz, false, uniq_slot_);
   pa.out_vals = wpull_;
   pa.out_map = ws_->uniq_pos;
   pa.pstride = pstride();
   pa.fm_vals = fm_vals_;
   be_->table_pull(pa);
-
-  FwdArgs fa;
-  fa.batch = b;
-  fa.pos = ws_->pos;
-  fa.wpull = wpull_;
-  fa.grad = nullptr;
-  fa.pctr = pctr;
-  fa.stats = stats_ + 1;
-  fa.model = cfg_.model;
-  fa.S = 1;
-  fa.fm_vals = fm_vals_;
-  be_->forward_backward(fa);
+  be_->forward_backward(eval_fwd_args(b, pctr));
 }
 
 // the device arrays of push_host / pull_host: exactly n keys when they grow
@@ -986,29 +948,15 @@ void Engine::push_host(const std::vector<u64>& keys, const std::vector<float>& g
   ensure_host_staging(n);
   be_->copy_h2d(host_keys_dev_, keys.data(), sizeof(u64) * n);
   be_->copy_h2d(host_vals_dev_, grads.data(), sizeof(float) * n * P);
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = host_keys_dev_;
-  pa.n_host = n;
-  pa.n_max = n;
-  pa.insert = true;
-  pa.out_slot = host_slots_dev_;
-  be_->table_pull(pa);
+  // (no admission filter: explicit pushes insert regardless; no values read)
+  be_->table_pull(pull_args(host_keys_dev_, nullptr, n, true, host_slots_dev_));
   // Pushes of one call are applied one key at a time in order; duplicate keys
   // inside one call are applied sequentially by separate launches.
-  ApplyArgs aa;
-  aa.table = table_;
-  aa.opt = cfg_.opt;
-  aa.keys = host_keys_dev_;
-  aa.S = 1;
-  aa.pstride = P;
-  aa.P = P;
+  ApplyArgs aa = apply_args(host_keys_dev_, host_slots_dev_, nullptr, 1, 1);
+  aa.pstride = P;  // (host rows are P wide, not padded to the kernels' latent width)
   for (int64_t i = 0; i < n; ++i) {
     aa.slots = host_slots_dev_ + i;
     aa.grads = host_vals_dev_ + i * P;
-    aa.n_host = 1;
-    aa.n_max = 1;
     be_->table_apply(aa);
   }
   be_->synchronize();
@@ -1031,16 +979,9 @@ std::vector<float> Engine::pull_host(const std::vector<u64>& keys) {
   if (n == 0) return out;
   ensure_host_staging(n);
   be_->copy_h2d(host_keys_dev_, keys.data(), sizeof(u64) * n);
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = host_keys_dev_;
-  pa.n_host = n;
-  pa.n_max = n;
-  pa.insert = false;
-  pa.out_slot = host_slots_dev_;
+  PullArgs pa = pull_args(host_keys_dev_, nullptr, n, false, host_slots_dev_);
   pa.out_vals = host_vals_dev_;
-  pa.pstride = P;
+  pa.pstride = P;  // (host rows: P wide, no compact FM value rows)
   be_->table_pull(pa);
   be_->copy_d2h(out.data(), host_vals_dev_, sizeof(float) * n * P);
   return out;
@@ -1113,17 +1054,7 @@ void Engine::w_forward(const BatchView& b, const float* pulled, int64_t n_send, 
                        int wb) {
   use_worker_set(wb);
   be_->scatter_rows(pulled, wpull_, ws_->send_map, nullptr, n_send, vstride_);
-  FwdArgs fa;
-  fa.batch = b;
-  fa.pos = ws_->pos;
-  fa.wpull = wpull_;
-  fa.grad = nullptr;
-  fa.pctr = pctr;
-  fa.stats = stats_ + 1;
-  fa.model = cfg_.model;
-  fa.S = 1;
-  fa.fm_vals = fm_vals_;
-  be_->forward_backward(fa);
+  be_->forward_backward(eval_fwd_args(b, pctr));
 }
 
 void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool insert, int buf,
@@ -1141,15 +1072,8 @@ void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool inser
     guard_inserts(n);
     group_entries(recv_keys, n, buf, src_offsets);
   }
-  PullArgs pa;
-  pa.table = table_;
-  pa.opt = cfg_.opt;
-  pa.keys = recv_keys;
-  pa.n_host = n;
-  pa.n_max = n;
-  pa.insert = insert;
+  PullArgs pa = pull_args(recv_keys, nullptr, n, insert, sb.slots);
   if (insert) pa.admit = admit_;
-  pa.out_slot = sb.slots;
   pa.out_vals = out_vals;
   pa.pstride = pstride();
   pa.fm_vals = fm_vals_;
@@ -1263,21 +1187,11 @@ void Engine::w_forward_backward(const BatchView& b, const float* pulled, int64_t
   if (group == 0)
     be_->scatter_rows(pulled, wpull_, ws_->send_map, nullptr, n_send, vstride_,
                       direct ? grads_out : nullptr, grad_width());
-  FwdArgs fa;
-  fa.batch = bk;
-  fa.pos = posk;
-  fa.wpull = wpull_;
-  fa.grad = grad_;
-  fa.stats = stats_;
-  fa.model = cfg_.model;
-  fa.S = S;
+  FwdArgs fa = train_fwd_args(bk, posk, S);
   fa.agg_ok = (double)scratch_.cap * S * pstride() < 4294967295.0;
-  fa.fx_bad = overflow_;
-  set_reduction(fa);
   if (masks && reduction_masks(false)) fa.red_masks = tmask_;
   else if (masks) be_->slice_masks(bk, posk, tmask_);
   fa.fm_compact = sharded_fm_compact() && fa.agg_ok;
-  fa.fm_vals = fm_vals_;
   if (sharded_fm_compact() && !fa.fm_compact)
     throw std::logic_error("w_forward_backward: compact FM rows need the reduction path");
   if (direct) {
@@ -1313,27 +1227,17 @@ void Engine::s_apply(const u64* recv_keys, const float* recv_grads, const u32* r
   if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
   SrvBuf& sb = srv_[buf];
   sb.keys = nullptr;  // applied: no slot remap needed after a growth
-  const int ps = pstride();
   const int gw = grad_width();
-  // the first source applied sees the state its pull saw; a key sent by
-  // several sources is updated by the earlier ones, so later sources re-read
-  // (the grouped apply pushes every source of a key at once: its stash stays valid)
+  // (the grouped apply pushes every source of a key at once: its stash stays
+  // valid; source by source only the first launch takes it, apply_by_source)
   bool stash = sb.nz_fresh;
   stale_stashes();
-  ApplyArgs base;
-  base.table = table_;
-  base.opt = cfg_.opt;
+  ApplyArgs base = apply_args(recv_keys, sb.slots, nullptr, 0, S);
+  base.grads = const_cast<float*>(recv_grads);
+  base.masks = recv_masks;
   base.gstride = gw;
-  if (sharded_fm_compact()) {
-    base.fm_compact = true;
-    base.fm_D = cfg_.model.v_dim;
-  }
-  base.zero_after = false;
-  base.S = S;
-  base.pstride = ps;
-  base.P = cfg_.model.P();
+  base.fm_compact = sharded_fm_compact();
   base.sum_slices = cfg_.sum_slices;
-  base.slice_rows = nullptr;
   const SrcGroups& g = sb.grp;
   bool same = g.oidx && (int)src_offsets.size() == g.nsrc + 1;
   for (int s = 0; same && s <= g.nsrc; ++s) same = src_offsets[s] == g.offs[s];
@@ -1342,47 +1246,23 @@ void Engine::s_apply(const u64* recv_keys, const float* recv_grads, const u32* r
     const int64_t n = g.offs[g.nsrc];
     if (n > sb.n) throw std::invalid_argument("s_apply: offsets beyond pull");
     ApplyArgs aa = base;
-    aa.keys = recv_keys;
-    aa.slots = sb.slots;
     aa.n_host = n;
     aa.n_max = n;
-    aa.grads = const_cast<float*>(recv_grads);
     if (aa.fm_compact) aa.pulled = pulled_weights(buf, 0);
-    aa.masks = recv_masks;
     if (stash) aa.nz_stash = sb.nz;
     aa.grp = g;
     attach_snapshot(aa);
     be_->table_apply(aa);
     return;
   }
-  size_t first_src = 0;
-  while (first_src + 1 < src_offsets.size() && src_offsets[first_src + 1] <= src_offsets[first_src])
-    ++first_src;
-  for (size_t src = 0; src + 1 < src_offsets.size(); ++src) {
-    int64_t off = src_offsets[src];
-    int64_t cnt = src_offsets[src + 1] - off;
-    if (cnt <= 0) continue;
-    if (src_offsets[src + 1] > sb.n) throw std::invalid_argument("s_apply: offsets beyond pull");
-    ApplyArgs aa = base;
-    aa.keys = recv_keys + off;
-    aa.slots = sb.slots + off;
-    aa.n_host = cnt;
-    aa.n_max = cnt;
-    aa.grads = const_cast<float*>(recv_grads) + off * (int64_t)S * gw;
-    if (aa.fm_compact) {
-      aa.pulled = pulled_weights(buf, off);
-      // compact value rows carry no per-parameter weights: a later source
-      // would expand its (B, C) with weights the earlier sources updated
-      if (!aa.pulled && src > first_src)
-        throw std::logic_error("s_apply: compact FM rows of several sources need the grouped "
-                               "apply or s_pull(keep_weights)");
-    }
-    aa.masks = recv_masks ? recv_masks + off : nullptr;
-    if (stash) aa.nz_stash = sb.nz + 2 * off;
-    stash = false;
-    attach_snapshot(aa);
-    be_->table_apply(aa);
-  }
+  apply_by_source(base, src_offsets, buf, stash,
+                  "s_apply: compact FM rows of several sources need the grouped "
+                  "apply or s_pull(keep_weights)",
+                  [&](ApplyArgs& aa, int64_t off, int64_t cnt) {
+                    if (off + cnt > sb.n) throw std::invalid_argument("s_apply: offsets beyond pull");
+                    aa.grads = base.grads + off * (int64_t)S * gw;
+                    if (recv_masks) aa.masks = recv_masks + off;
+                  });
 }
 
 // Per-parameter pre-step weights of buffer entries from `off` for the compact
@@ -1613,14 +1493,7 @@ void Engine::grow_table(int lg) {
 void Engine::remap_server_slots() {
   for (SrvBuf& sb : srv_) {
     if (!sb.keys || sb.n <= 0) continue;
-    PullArgs pa;
-    pa.table = table_;
-    pa.opt = cfg_.opt;
-    pa.keys = sb.keys;
-    pa.n_host = sb.n;
-    pa.n_max = sb.n;
-    pa.insert = false;
-    pa.out_slot = sb.slots;
+    PullArgs pa = pull_args(sb.keys, nullptr, sb.n, false, sb.slots);
     pa.pstride = pstride();
     be_->table_pull(pa);
   }

@@ -183,7 +183,6 @@ class HipBackend final : public Backend {
     XF_HIP_CHECK(r);
     return true;
   }
-  void event_wait(void* e) override { XF_HIP_CHECK(hipEventSynchronize(static_cast<hipEvent_t>(e))); }
   // nullptr selects the null (default) stream, which is what torch reports as
   // its default current stream.
   void set_stream(void* s) override { stream_ = reinterpret_cast<hipStream_t>(s); }
@@ -193,9 +192,6 @@ class HipBackend final : public Backend {
   void table_clear(const TableView& t) override { hip::launch_table_clear(t, stream_); }
   void dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o) override {
     hip::launch_dedup(keys, nnz, s, o, stream_);
-  }
-  void scratch_reset(ScratchView s, const u32* pos, const int64_t* n_dev, int64_t n_max) override {
-    hip::launch_scratch_reset(s, pos, n_dev, n_max, stream_);
   }
   void table_pull(const PullArgs& a) override { hip::launch_table_pull(a, stream_); }
   void table_apply(const ApplyArgs& a) override { hip::launch_table_apply(a, stream_); }
@@ -238,18 +234,6 @@ class HipBackend final : public Backend {
   void scatter_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
                     int64_t n_max, int width, float* zero_out, int zero_width) override {
     hip::launch_scatter_rows(src, dst, map, n_dev, n_max, width, zero_out, zero_width, stream_);
-  }
-  void gather_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
-                   int64_t n_max, int width, bool zero_src) override {
-    hip::launch_gather_rows(src, dst, map, n_dev, n_max, width, zero_src, stream_);
-  }
-  void gather_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev, int64_t n_max,
-                  bool zero_src) override {
-    hip::launch_gather_u32(src, dst, map, n_dev, n_max, zero_src, stream_);
-  }
-  void scatter_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                   int64_t n_max) override {
-    hip::launch_scatter_u32(src, dst, map, n_dev, n_max, stream_);
   }
   void synth_batch(const SynthArgs& a) override { hip::launch_synth(a, stream_); }
   void unpack_block(const UnpackArgs& a) override { hip::launch_unpack_block(a, stream_); }

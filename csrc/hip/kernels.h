@@ -10,8 +10,6 @@ namespace hip {
 
 // kernels_table.hip
 void launch_dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o, hipStream_t st);
-void launch_scratch_reset(ScratchView s, const u32* pos, const int64_t* n_dev, int64_t n_max,
-                          hipStream_t st);
 void launch_table_pull(const PullArgs& a, hipStream_t st);
 void launch_table_apply(const ApplyArgs& a, hipStream_t st);
 void launch_gather_grads(const GatherGradArgs& a, hipStream_t st);
@@ -23,12 +21,6 @@ void launch_partition_counts(const ScratchView& s, const u32* chunk_offsets,
 void launch_scatter_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
                          int64_t n_max, int width, float* zero_out, int zero_width,
                          hipStream_t st);
-void launch_gather_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
-                        int64_t n_max, int width, bool zero_src, hipStream_t st);
-void launch_gather_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                       int64_t n_max, bool zero_src, hipStream_t st);
-void launch_scatter_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                        int64_t n_max, hipStream_t st);
 void launch_fill_u64(u64* p, u64 v, size_t n, hipStream_t st);
 // CSR exchange: exclusive scan (out[n] = total; tiles: n_max / 4096 + 2 words)
 void launch_scan_u32(const u32* in, u32* out, const int64_t* n_dev, int64_t n_max, u32* tiles,

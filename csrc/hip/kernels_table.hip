@@ -496,24 +496,6 @@ void launch_dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o, hipSt
   XF_HIP_CHECK(hipGetLastError());
 }
 
-// The persistent scratch needs no per-step reset (stamps expire with the
-// epoch); kept as an explicit full clear for callers that want a cold table.
-__global__ void k_scratch_reset(u64* __restrict__ skeys, const u32* __restrict__ pos,
-                                const int64_t* n_dev, int64_t n_max) {
-  int64_t n = dev_count(n_dev, n_max, n_max);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    skeys[pos[i]] = kEmptyKey;
-}
-
-void launch_scratch_reset(ScratchView s, const u32* pos, const int64_t* n_dev, int64_t n_max,
-                          hipStream_t st) {
-  if (n_max <= 0) return;
-  hipLaunchKernelGGL(k_scratch_reset, dim3(grid_for(n_max)), dim3(kBlock), 0, st, s.keys, pos,
-                     n_dev, n_max);
-  XF_HIP_CHECK(hipGetLastError());
-}
-
 __global__ void k_fill_u64(u64* p, u64 v, size_t n) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
@@ -1169,7 +1151,6 @@ __global__ void __launch_bounds__(kBlock) k_apply_lr16(ApplyArgs a) {
       const In x = nx;
       if (i + stride < n) nx = load(i + stride);
       if (a.zero_after) a.grads[x.row] = 0.0f;
-      if (a.reset_pos) a.scratch.keys[a.reset_pos[i]] = kEmptyKey;
       if (x.slot == kNoSlot) continue;
       float2 nz = x.nz;
       const float w = ftrl_weight(nz.y, nz.x, fp);
@@ -1352,7 +1333,6 @@ __global__ void __launch_bounds__(kBlock) k_apply_generic(ApplyArgs a) {
       for (int j = 0; j < S * ps; ++j) g[j] = 0.0f;
       if (a.masks_rw) a.masks_rw[row] = 0u;
     }
-    if (a.reset_pos) a.scratch.keys[a.reset_pos[i]] = kEmptyKey;
   }
 }
 
@@ -1751,12 +1731,11 @@ void launch_table_apply(const ApplyArgs& a, hipStream_t st) {
   const bool lr16 = lr16_slot && a.S == 1 && !a.masks;
   // S > 1 on unique-order sums and slice bits (Engine::train_step's fused LR step)
   const bool lr16_slices = lr16_slot && a.S > 1 && a.masks && !a.masks_rw && !a.grad_map &&
-                           !a.zero_after && !a.reset_pos && !a.sum_slices && !a.slice_rows &&
-                           !a.grp.oidx;
+                           !a.zero_after && !a.sum_slices && !a.slice_rows && !a.grp.oidx;
   if (a.nz_stash && !a.keys && !a.grp.oidx && L.P > 1)
     throw std::runtime_error("table_apply: a stash needs the entries' keys");
   if (a.csr_cnt) {
-    if (a.zero_after || a.reset_pos || a.sum_slices || a.grp.oidx || a.grad_map || a.slice_rows)
+    if (a.zero_after || a.sum_slices || a.grp.oidx || a.grad_map || a.slice_rows)
       throw std::runtime_error("CSR apply: bad arguments (entries come normalised)");
     // deferral lists (CsrDefer, CsrDense): [counts W][regions W x R][offsets
     // W + 1][dense list <= n][scan tiles]
@@ -1796,7 +1775,7 @@ void launch_table_apply(const ApplyArgs& a, hipStream_t st) {
       throw std::runtime_error("CSR apply: LR-FTRL 16-byte slots, compact reference-FM rows or full rows");
     }
   } else if (a.grp.oidx) {
-    if (a.zero_after || a.reset_pos) throw std::runtime_error("multi-source apply: bad arguments");
+    if (a.zero_after) throw std::runtime_error("multi-source apply: bad arguments");
     if (lr16) hipLaunchKernelGGL(k_apply_lr16_multi, dim3(grid), dim3(kBlock), 0, st, a);
     else if (a.S > 1)
       hipLaunchKernelGGL(k_apply_group<true>, dim3(packed_grid(nm, L.P)), dim3(kBlock), 0, st, a);
@@ -1805,7 +1784,7 @@ void launch_table_apply(const ApplyArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_apply_lr16<false>, dim3(grid), dim3(kBlock), 0, st, a);
   } else if (lr16_slices) {
     hipLaunchKernelGGL(k_apply_lr16<true>, dim3(grid), dim3(kBlock), 0, st, a);
-  } else if ((a.pstride >= 2 || (L.P == 1 && a.nz_stash)) && L.P <= kWave && !a.reset_pos) {
+  } else if ((a.pstride >= 2 || (L.P == 1 && a.nz_stash)) && L.P <= kWave) {
     // (LR with several slices and the pull's stash: one lane per key, packed)
     if (a.S > 1)
       hipLaunchKernelGGL(k_apply_group<true>, dim3(packed_grid(nm, L.P)), dim3(kBlock), 0, st, a);
@@ -2208,39 +2187,6 @@ __global__ void k_scatter_rows(const float* __restrict__ src, float* __restrict_
       zero_out[i] = 0.0f;
 }
 
-__global__ void k_gather_rows(const float* __restrict__ src, float* __restrict__ dst,
-                              const u32* __restrict__ map, const int64_t* n_dev, int64_t n_max,
-                              int width, bool zero_src) {
-  int64_t n = dev_count(n_dev, n_max, n_max) * width;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-    int64_t i = e / width;
-    int c = (int)(e - i * width);
-    int64_t r = (int64_t)map[i] * width + c;
-    dst[e] = src[r];
-    if (zero_src) const_cast<float*>(src)[r] = 0.0f;
-  }
-}
-
-__global__ void k_gather_u32(const u32* __restrict__ src, u32* __restrict__ dst,
-                             const u32* __restrict__ map, const int64_t* n_dev, int64_t n_max,
-                             bool zero_src) {
-  int64_t n = dev_count(n_dev, n_max, n_max);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    dst[i] = src[map[i]];
-    if (zero_src) const_cast<u32*>(src)[map[i]] = 0u;
-  }
-}
-
-__global__ void k_scatter_u32(const u32* __restrict__ src, u32* __restrict__ dst,
-                              const u32* __restrict__ map, const int64_t* n_dev, int64_t n_max) {
-  int64_t n = dev_count(n_dev, n_max, n_max);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-    dst[map[i]] = src[i];
-}
-
 void launch_scatter_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
                          int64_t n_max, int width, float* zero_out, int zero_width,
                          hipStream_t st) {
@@ -2256,30 +2202,6 @@ void launch_scatter_rows(const float* src, float* dst, const u32* map, const int
   }
   hipLaunchKernelGGL(k_scatter_rows, dim3(grid_for(n_max * width)), dim3(kBlock), 0, st, src, dst,
                      map, n_dev, n_max, width, zero_out, zero_width);
-  XF_HIP_CHECK(hipGetLastError());
-}
-
-void launch_gather_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
-                        int64_t n_max, int width, bool zero_src, hipStream_t st) {
-  if (n_max <= 0) return;
-  hipLaunchKernelGGL(k_gather_rows, dim3(grid_for(n_max * width)), dim3(kBlock), 0, st, src, dst,
-                     map, n_dev, n_max, width, zero_src);
-  XF_HIP_CHECK(hipGetLastError());
-}
-
-void launch_gather_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                       int64_t n_max, bool zero_src, hipStream_t st) {
-  if (n_max <= 0) return;
-  hipLaunchKernelGGL(k_gather_u32, dim3(grid_for(n_max)), dim3(kBlock), 0, st, src, dst, map,
-                     n_dev, n_max, zero_src);
-  XF_HIP_CHECK(hipGetLastError());
-}
-
-void launch_scatter_u32(const u32* src, u32* dst, const u32* map, const int64_t* n_dev,
-                        int64_t n_max, hipStream_t st) {
-  if (n_max <= 0) return;
-  hipLaunchKernelGGL(k_scatter_u32, dim3(grid_for(n_max)), dim3(kBlock), 0, st, src, dst, map,
-                     n_dev, n_max);
   XF_HIP_CHECK(hipGetLastError());
 }
 

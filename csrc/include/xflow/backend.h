@@ -202,7 +202,6 @@ struct FwdArgs {
   // feature instead of the whole (1+D)-float row (PullArgs::fm_vals).
   bool fm_vals = false;
   float* grad = nullptr;           // [scratch_cap][S][pstride] (null: forward only)
-  u32* tmask = nullptr;            // [scratch_cap] slice-touch bits (null unless S>1)
   float* pctr = nullptr;           // [rows] optional
   LossStats* stats = nullptr;      // accumulated (device)
   ModelSpec model;
@@ -497,9 +496,6 @@ struct ApplyArgs {
   // served for entry i ([n][pstride], the workers' pre-step weights), since
   // the table already holds the previous sources' updates.  Null: the table.
   const float* pulled = nullptr;
-  // Optional fused reset of the worker dedup scratch (single-device path).
-  ScratchView scratch;
-  const u32* reset_pos = nullptr;
   // CSR gradients (csr_cnt != null, CsrOut): entry i's pushes are its CSR
   // entries in order (the entries carry their slices; grads / masks unused)
   const u32* csr_off = nullptr;
@@ -651,7 +647,6 @@ class Backend {
   virtual void event_destroy(void* e) { (void)e; }
   virtual void event_record(void* e) { (void)e; }
   virtual bool event_done(void* e) { (void)e; return true; }
-  virtual void event_wait(void* e) { (void)e; }
   // wait by polling (no blocking-sync wake-up latency: a host that must
   // enqueue the next device work the moment this event fires -- the CSR
   // exchange's entry totals, the async parameter server's hand-overs)
@@ -677,8 +672,6 @@ class Backend {
   // Mark every slot free (key words = kEmptyKey) with zero optimizer state.
   virtual void table_clear(const TableView& t) = 0;
   virtual void dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o) = 0;
-  virtual void scratch_reset(ScratchView s, const u32* pos, const int64_t* n_dev,
-                             int64_t n_max) = 0;
   virtual void table_pull(const PullArgs& a) = 0;
   virtual void table_apply(const ApplyArgs& a) = 0;
   virtual void forward_backward(const FwdArgs& a) = 0;
@@ -734,14 +727,6 @@ class Backend {
   virtual void scatter_rows(const float* src, float* dst, const u32* map,
                             const int64_t* n_dev, int64_t n_max, int width,
                             float* zero_out = nullptr, int zero_width = 1) = 0;
-  // dst[i] = src[map[i]]; optionally zero the source row   (gather)
-  virtual void gather_rows(const float* src, float* dst, const u32* map,
-                           const int64_t* n_dev, int64_t n_max, int width,
-                           bool zero_src) = 0;
-  virtual void gather_u32(const u32* src, u32* dst, const u32* map,
-                          const int64_t* n_dev, int64_t n_max, bool zero_src) = 0;
-  virtual void scatter_u32(const u32* src, u32* dst, const u32* map,
-                           const int64_t* n_dev, int64_t n_max) = 0;
   virtual void synth_batch(const SynthArgs& a) = 0;
   // [rows][F] -> [F][rows] of 4- or 8-byte elements (field-major batches)
   // widen (elem_bytes 4 only): u32 source elements zero-extended to u64 --

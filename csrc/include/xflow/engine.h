@@ -466,6 +466,30 @@ class Engine {
   int red_maxb_ = 0;  // FwdArgs::red_maxb
   int red_groups_ = 0;  // FwdArgs::red_groups
   void set_reduction(FwdArgs& fa) const;
+  // Kernel arguments are filled here and nowhere else: each builder sets what
+  // every caller of its struct sets, a call site then adds only what is its
+  // own.  Counts: *n_dev entries (at most n) when n_dev is set, else n.
+  PullArgs pull_args(const u64* keys, const int64_t* n_dev, int64_t n, bool insert,
+                     u32* out_slot) const;
+  // (fm_D is read by compact-FM applies only)
+  ApplyArgs apply_args(const u64* keys, const u32* slots, const int64_t* n_dev, int64_t n,
+                       int S) const;
+  // training forward/backward of S slices; calls set_reduction (once per forward)
+  FwdArgs train_fwd_args(const BatchView& b, const u32* pos, int S) const;
+  // forward only (eval_step, w_forward): eval stats, optional predictions
+  FwdArgs eval_fwd_args(const BatchView& b, float* pctr) const;
+  // The fused step's prologue: dedup (want_inv: with the slot -> unique index
+  // map) -> unique-index positions (upos) -> growth guard; returns the
+  // inserting pull over the unique keys for the caller to complete and launch.
+  PullArgs begin_fused_step(const BatchView& b, bool want_inv, bool upos);
+  // The owner's per-source applies of server buffer buf: base (keys / slots at
+  // entry 0) offset to every non-empty source of src_offsets in order, the
+  // pull's (n, z) stash handed to the first launch only, compact FM rows of a
+  // later source refused without kept weights (logic_error need_weights).
+  // source(aa, first entry, entries) adds the source's own arguments.
+  template <typename Source>
+  void apply_by_source(const ApplyArgs& base, const std::vector<int64_t>& src_offsets, int buf,
+                       bool stash, const char* need_weights, Source source);
   // CSR gradients (CsrOut): the single-rank step of several slices, LR-FTRL on
   // 16-byte slots or compact reference-FM rows -- one producer pass, one
   // reduction and one apply for any slice count
