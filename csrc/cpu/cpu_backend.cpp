@@ -268,7 +268,7 @@ class CpuBackend final : public Backend {
           y = wx + (vsum * vsum - vp);
         }
       } else {  // MVM
-        if (!b.fgid) throw std::runtime_error("MVM needs field ids (fgid)");
+        if (!b.fgid && b.nnz > 0) throw std::runtime_error("MVM needs field ids (fgid)");
         for (int64_t j = 0, o = rs.base; j < rs.len; ++j, o += rs.step) maxf = std::max(maxf, (int)b.fgid[o]);
         G = (m.mvm_math == kMvmCompat) ? maxf : maxf + 1;
         S.assign((size_t)(maxf + 1) * D, 0.0f);

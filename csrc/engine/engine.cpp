@@ -136,7 +136,9 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   // standard FM: vector records (dest, 1 + D sums) per (key, slice, column)
   // and workgroup (k_fm_std_red), at most one per occurrence
   const bool fm_std = cfg_.model.kind == kFM && cfg_.model.fm_math == kFmStandard;
-  const bool mvm = cfg_.model.kind == kMVM;
+  // (MVM: the reduction sums the D-wide T = loss*M rows, which the kernels
+  // have for D >= 2; width 1 aggregates in LDS / by atomics, dispatch_mvm)
+  const bool mvm = cfg_.model.kind == kMVM && cfg_.model.kernel_dim() >= 2;
   if (be.is_gpu() && (cfg_.model.kind == kLR || fm_ref || fm_std || mvm)) {
     // values per record: 1 (LR), 2 (reference FM), the vector records of
     // standard FM (1 + D) and MVM (D: per-row T = loss*M sums)
@@ -438,6 +440,14 @@ void Engine::dedup_(const BatchView& b, int parts, u64* uniq_keys_out, bool want
   if (b.rows > cfg_.max_rows) throw std::invalid_argument("batch rows exceed max_rows");
   if (b.col_stride > 0 && (b.row_ptr || b.col_stride < b.rows || b.nnz != b.rows * b.nnz_per_row))
     throw std::invalid_argument("field-major batch needs fixed nnz_per_row and col_stride >= rows");
+  if (b.nnz == 0) {
+    // rows without occurrences: no keys.  The backends' dedup writes the
+    // unique count only when it runs over occurrences, so it is cleared here
+    // (a count left from the batch before would pull, insert and flag that
+    // batch's keys again)
+    be_->memset(ws_->n_uniq, 0, sizeof(int64_t));
+    return;
+  }
   // table-ordered unique lists (ScratchView::home_bits) on the one-owner GPU path
   const int hb = be_->is_gpu() && parts == 1
                      ? table_.seg_log2 + table_.level + (table_.split > 0 ? 1 : 0)
@@ -568,7 +578,8 @@ StepPlan plan_step(const StepInputs& in, int S) {
   // slice bits from the reduction (dest * pstride in 32 bits)
   const double key_bound = p.upos ? in.max_nnz : in.scratch_cap;
   const bool red_masks = in.red_pairs && key_bound * in.slice_cap * in.pstride < k32 &&
-                         (in.kind == kLR || in.kind == kFM || (in.kind == kMVM && in.red_rowv));
+                         (in.kind == kLR || in.kind == kFM ||
+                          (in.kind == kMVM && in.red_rowv && in.kdim >= 2));
   p.lr16 = lr16_ok && (p.Sf == 1 || (p.masks && red_masks));
   // summed slices: slot-indexed sums (packed apply), still the (n, z) stash
   p.lr16s = lr16_ok && p.Sf > 1 && !p.lr16;
@@ -586,7 +597,9 @@ StepPlan plan_step(const StepInputs& in, int S) {
   // paths: the per-key gradient rows land in unique order too (a dense apply
   // read instead of slot-indexed rows the apply had to zero after reading)
   const bool rows_ok = in.gpu && in.red_pairs && key_bound * in.pstride * in.slice_cap < k32;
-  p.mvmu = rows_ok && p.Sf == 1 && in.kind == kMVM && in.red_rowv;
+  // (kdim >= 2, here and in red_masks: an Engine never has red_rowv at width
+  // 1, so this only matters to callers of the bare plan_step who pass it)
+  p.mvmu = rows_ok && p.Sf == 1 && in.kind == kMVM && in.red_rowv && in.kdim >= 2;
   p.fsu = rows_ok && (p.Sf == 1 || p.uqm) && in.kind == kFM && in.fm_math == kFmStandard;
   p.rowu = p.mvmu || p.fsu;
   // FTRL with several params per key on the packed apply: the pull stashes

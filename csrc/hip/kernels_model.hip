@@ -3072,7 +3072,8 @@ void launch_forward_backward(const FwdArgs& a, hipStream_t st) {
       else dispatch_fm<false>(a, st);
       break;
     case kMVM:
-      if (!a.batch.fgid) throw std::runtime_error("MVM needs field ids (fgid)");
+      // (a batch without occurrences has no field ids to point at)
+      if (!a.batch.fgid && a.batch.nnz > 0) throw std::runtime_error("MVM needs field ids (fgid)");
       if (grad) dispatch_mvm<true>(a, st);
       else dispatch_mvm<false>(a, st);
       break;
