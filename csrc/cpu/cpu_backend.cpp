@@ -325,8 +325,11 @@ class CpuBackend final : public Backend {
     c[6] = blk.row_ptr[used];
     for (int64_t i = 0; i < a.n; ++i) c[4] += a.text[i] == '\n';
     if (a.n > 0 && a.text[a.n - 1] != '\n') ++c[4];
+    // (a block of mostly empty lines: rejected as on the device, whose
+    // workspace holds text_max_lines(n) lines)
+    c[5] = c[4] > a.max_lines;
     a.row_ptr[0] = 0;
-    if (c[0] > a.max_rows || c[1] > a.max_nnz) return;  // (the caller checks the counts)
+    if (c[5] || c[0] > a.max_rows || c[1] > a.max_nnz) return;  // (the caller checks the counts)
     for (int64_t r = 0; r < blk.rows(); ++r) {
       a.labels[r] = blk.labels[r];
       a.row_ptr[r + 1] = blk.row_ptr[r + 1];

@@ -1,7 +1,7 @@
 // xflow-amd: libffm text -> CSR batch on the device (gfx950).
 //
 // The reference parses every block of text on its training threads
-// (/root/reference/src/io/load_data_from_disk.cc:103-210, the only loader it
+// (its src/io/load_data_from_disk.cc:103-210, the only loader it
 // uses); csrc/io/reader.cpp does the same on the host at ~1.3 GB/s.  Here a
 // block's bytes are uploaded as they are and tokenised where they will be
 // used:
@@ -23,9 +23,11 @@
 // at ' ' (empty ones skipped); a token without ':' is no feature; the key
 // hashes the text between the first and second ':' (a 2-part token: to the
 // end, trailing '\r' stripped); the value is never read.  Bit-equal keys,
-// field ids, labels and row offsets (tests/test_gpu_parse.py).
+// field ids, labels and row offsets (tests/test_gpu_parse.py; against an
+// independent reference: tests/test_parse_rules.py).
 #include "kernels.h"
 #include "hip_util.h"
+#include "xflow/atof_exact.h"
 
 namespace xflow {
 namespace hip {
@@ -100,62 +102,12 @@ __global__ void __launch_bounds__(kPBlock) k_nl_write(const char* __restrict__ t
     if (text[i] == '\n') line_end[k++] = (u32)i;
 }
 
-__device__ __forceinline__ bool is_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r'); }
+__device__ __forceinline__ bool is_space(char c) { return atof_space(c); }
 
-// atof of the NUL-terminated copy of [b, e) (reader.cpp range_atof: at most
-// 63 characters): leading white space, sign, inf / nan, decimal digits with
-// a fraction and an exponent.  Correctly rounded for up to 19 significant
-// digits and |decimal exponent| <= 22 (exact powers of ten) -- every label
-// and field id of CTR data; hexadecimal floats are not recognised (0).
-__device__ double dev_atof(const char* __restrict__ b, const char* __restrict__ e) {
-  if (e - b > 63) e = b + 63;
-  const char* p = b;
-  while (p < e && is_space(*p)) ++p;
-  bool neg = false;
-  if (p < e && (*p == '+' || *p == '-')) neg = *p++ == '-';
-  if (e - p >= 3 && (p[0] | 32) == 'i' && (p[1] | 32) == 'n' && (p[2] | 32) == 'f')
-    return neg ? -INFINITY : INFINITY;
-  if (e - p >= 3 && (p[0] | 32) == 'n' && (p[1] | 32) == 'a' && (p[2] | 32) == 'n') return NAN;
-  unsigned long long mant = 0;
-  int digits = 0, ex = 0;
-  bool any = false;
-  for (; p < e && *p >= '0' && *p <= '9'; ++p) {
-    any = true;
-    if (digits < 19) {
-      mant = mant * 10ull + (unsigned long long)(*p - '0');
-      digits += mant != 0ull;
-    } else {
-      ++ex;
-    }
-  }
-  if (p < e && *p == '.') {
-    for (++p; p < e && *p >= '0' && *p <= '9'; ++p) {
-      any = true;
-      if (digits < 19) {
-        mant = mant * 10ull + (unsigned long long)(*p - '0');
-        digits += mant != 0ull;
-        --ex;
-      }
-    }
-  }
-  if (!any) return 0.0;
-  if (p < e && (*p | 32) == 'e') {
-    const char* q = p + 1;
-    bool eneg = false;
-    if (q < e && (*q == '+' || *q == '-')) eneg = *q++ == '-';
-    if (q < e && *q >= '0' && *q <= '9') {
-      int v = 0;
-      for (; q < e && *q >= '0' && *q <= '9'; ++q) v = v < 100000 ? v * 10 + (*q - '0') : v;
-      ex += eneg ? -v : v;
-    }
-  }
-  double r = (double)mant;
-  if (mant != 0ull && ex != 0) {
-    if (ex > 0 && ex <= 22) r *= exp10((double)ex);
-    else if (ex < 0 && ex >= -22) r /= exp10((double)-ex);
-    else r *= exp10((double)ex);
-  }
-  return neg ? -r : r;
+// atof of the NUL-terminated copy of [b, e) (reader.cpp range_atof), correctly
+// rounded for every input of at most 63 characters: xflow/atof_exact.h
+__device__ __forceinline__ double dev_atof(const char* __restrict__ b, const char* __restrict__ e) {
+  return range_atof_exact(b, e);
 }
 
 // libstdc++ std::hash<std::string> on LP64: _Hash_bytes(p, n, 0xc70f6907)

@@ -1,7 +1,7 @@
 """libffm text parsed on the GPU: raw blocks -> pinned ring -> H2D -> CSR.
 
 The reference parses each 2 MB text block on its training threads
-(/root/reference/src/io/load_data_from_disk.cc:103-210) and the native host
+(its src/io/load_data_from_disk.cc:103-210) and the native host
 parser here (csrc/io/reader.cpp) reaches ~1.3 GB/s on 8 CPUs -- ~5 M Criteo
 rows/s, two orders of magnitude below one MI355X step.  ``TextStream`` moves
 the tokenising to the device:
@@ -140,8 +140,9 @@ class TextStream:
         self.stage_s = 0.0   # host seconds reading blocks into the pinned slots
         self.parse_s = 0.0   # host seconds waiting for parses (their counts)
         self.stop = False
-        # (device output arrays: one set per block, _arrays; a line needs >= 2
-        # bytes, a feature token >= 4 (" a:b"))
+        # (device output arrays: one set per block, _arrays; a row needs >= 2
+        # bytes ("\t\n"), a feature token of real data >= 4 (" a:b") -- the
+        # shortest the parser accepts is 2 (" :"), see _parse)
         self._texts = [None, None]  # device text buffers (block t parses while t+1 uploads)
         self._tb = 0
         self._pending = None        # an uploaded block not yet parsed
@@ -165,14 +166,16 @@ class TextStream:
             self.error = e
         self.ready.put(None)
 
-    def _arrays(self, n: int):
+    def _arrays(self, n: int, dense: bool = False):
         """Fresh output arrays for one block.  Every block owns its arrays (the
         caching allocator on the compute stream recycles them once the block's
         tensors die, stream-ordered): a multi-rank step announces block t+1 --
         which parses right away -- before block t trains, and ``--resident``
-        keeps the first epoch's blocks, so reused arrays would alias them."""
+        keeps the first epoch's blocks, so reused arrays would alias them.
+        The feature arrays hold n/4 tokens (" a:b" each); ``dense``: the n/2
+        of the shortest token the parser accepts (" :")."""
         rows = n // 2 + 2
-        nnz = n // 4 + 2
+        nnz = (n // 2 if dense else n // 4) + 2
         dev = self.device
         return {"keys": torch.empty(nnz, dtype=torch.int64, device=dev),
                 "fgid": torch.empty(nnz, dtype=torch.int32, device=dev),
@@ -236,7 +239,15 @@ class TextStream:
             torch.cuda.current_stream(self.device).wait_event(ev)
         o = self._arrays(n)
         t0 = time.perf_counter()
-        rows, nnz, lmin, lmax, nused = e.parse_text(text, n, o, self.row_mod)
+        try:
+            rows, nnz, lmin, lmax, nused = e.parse_text(text, n, o, self.row_mod)
+        except RuntimeError as err:
+            if "more rows / features than the arrays" not in str(err):
+                raise
+            # (tokens shorter than " a:b": nothing was written; once more with
+            # the arrays of the densest block the host reader parses)
+            o = self._arrays(n, dense=True)
+            rows, nnz, lmin, lmax, nused = e.parse_text(text, n, o, self.row_mod)
         self.parse_s += time.perf_counter() - t0
         if ev is None:  # (CPU: parsed from the slot itself)
             self.free.put((slot, None))
