@@ -634,6 +634,67 @@ class CpuBackend final : public Backend {
     }
     return m;
   }
+  GroupedEval eval_grouped(const float* pctr, const float* labels, const u64* groups, int64_t n,
+                           GroupTable* table) override {
+    // the definitions of GroupedEval: rows ordered by (group, pctr descending), one walk
+    GroupedEval r;
+    r.n = n;
+    if (table) *table = GroupTable();
+    auto bits = [&](int64_t i) {
+      const float p = pctr[i] > 0.0f ? pctr[i] : 0.0f;
+      u32 b;
+      std::memcpy(&b, &p, sizeof(b));
+      return b;
+    };
+    std::vector<int64_t> idx((size_t)n);
+    for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = i;
+    std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {
+      if (groups[a] != groups[b]) return groups[a] < groups[b];
+      return bits(a) > bits(b);
+    });
+    for (int64_t i = 0; i < n;) {
+      const u64 g = groups[idx[(size_t)i]];
+      int64_t ng = 0, pos = 0, sump = 0;
+      uint64_t area2 = 0;
+      int64_t j = i;
+      while (j < n && groups[idx[(size_t)j]] == g) {  // one tie run of the group
+        const u32 b = bits(idx[(size_t)j]);
+        int64_t rp = 0, rn = 0;
+        for (; j < n && groups[idx[(size_t)j]] == g && bits(idx[(size_t)j]) == b; ++j) {
+          const int64_t row = idx[(size_t)j];
+          if (labels[row] > 0.5f) ++rp;
+          else ++rn;
+          sump += group_fx(pctr[row]);
+        }
+        area2 += (uint64_t)rn * (uint64_t)(2 * pos + rp);
+        pos += rp;
+        ng += rp + rn;
+      }
+      i = j;
+      if (g == kNoGroup) {
+        r.n_nogroup = ng;
+        continue;
+      }
+      ++r.groups;
+      if (pos > 0 && pos < ng) {
+        ++r.groups_used;
+        r.rows_used += ng;
+        r.gauc_num += group_auc_term(ng, pos, area2);
+      }
+      r.cal_abs += group_cal_term(sump, pos);
+      if (table) {
+        table->key.push_back(g);
+        table->n.push_back(ng);
+        table->pos.push_back(pos);
+        table->area2.push_back(area2);
+        table->sump.push_back(sump);
+      }
+    }
+    return r;
+  }
+  void row_group_keys(const BatchView& b, int field, u64* out) override {
+    for (int64_t r = 0; r < b.rows; ++r) out[r] = row_group_key(b, r, field);
+  }
   int64_t table_nonzero(const TableView& t, const OptSpec& o) override {
     int64_t n = 0;
     for (u64 s = 0; s < t.cap; ++s) {

@@ -385,6 +385,15 @@ class HipBackend final : public Backend {
     hip::launch_eval_metrics(pctr, labels, n, &m, stream_);
     return m;
   }
+  GroupedEval eval_grouped(const float* pctr, const float* labels, const u64* groups, int64_t n,
+                           GroupTable* table) override {
+    GroupedEval r;
+    hip::launch_eval_grouped(pctr, labels, groups, n, &r, table, stream_);
+    return r;
+  }
+  void row_group_keys(const BatchView& b, int field, u64* out) override {
+    hip::launch_row_group_keys(b, field, out, stream_);
+  }
   int64_t table_nonzero(const TableView& t, const OptSpec& o) override {
     hip::launch_table_nonzero(t, o, counter_, stream_);
     unsigned long long n = 0;

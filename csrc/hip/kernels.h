@@ -66,6 +66,10 @@ void launch_parse_text(const TextParseArgs& a, hipStream_t st);
 // kernels_eval.hip
 void launch_eval_metrics(const float* pctr, const float* labels, int64_t n, EvalMetrics* out,
                          hipStream_t st);
+// per-group AUC counts and calibration (GroupedEval); table: optional per-group sums
+void launch_eval_grouped(const float* pctr, const float* labels, const u64* groups, int64_t n,
+                         GroupedEval* out, GroupTable* table, hipStream_t st);
+void launch_row_group_keys(const BatchView& b, int field, u64* out, hipStream_t st);
 
 // kernels_synth.hip
 void launch_synth(const SynthArgs& a, hipStream_t st);

@@ -19,6 +19,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "xflow/types.h"
 
@@ -591,6 +592,59 @@ struct EvalMetrics {
   double ln_sum = 0;      // sum of -ln likelihood, p clipped to [1e-7, 1-1e-7]
 };
 
+// Grouped evaluation (Backend::eval_grouped): the predictions are split by a
+// u64 group key per row, and every group gets its own tie-aware AUC counts
+// and a calibration sum.  Inputs pctr[n], labels[n] (positive iff > 0.5f),
+// groups[n]; n < 2^31.  A row whose group is kNoGroup belongs to no group
+// and is only counted (n_nogroup); kNoGroup is the table's empty key, which
+// no batch key equals.  Per distinct group g, all integers:
+//   n_g     rows, pos_g positive rows
+//   area2_g sum over (positive i, negative j) of g of 2*[p_i > p_j] + [p_i == p_j]
+//           (the Mann-Whitney count doubled, ties worth 1/2), compared on the
+//           float bits of fmaxf(p, 0).  Unlike EvalMetrics::area, which breaks
+//           ties by prediction order to match the reference's printer, it
+//           does not depend on the order of the rows.
+//   sump_g  sum of llrint(fmaxf(p, 0) * 2^32) (fixed point: order-free)
+// A group is used iff 0 < pos_g < n_g.  gauc_num and cal_abs are double sums
+// over the groups in ascending key order (fixed, so identical run to run).
+constexpr u64 kNoGroup = ~0ull;
+struct GroupedEval {
+  int64_t n = 0;            // predictions
+  int64_t n_nogroup = 0;    // rows with group kNoGroup
+  int64_t groups = 0;       // distinct groups (without kNoGroup)
+  int64_t groups_used = 0;  // groups with a positive and a negative row
+  int64_t rows_used = 0;    // sum of n_g over the used groups
+  double gauc_num = 0;      // sum over used groups of n_g * area2_g / (2 pos_g (n_g - pos_g))
+  double cal_abs = 0;       // sum over all groups of |sump_g * 2^-32 - pos_g|
+};
+// the per-group sums, in ascending key order (host memory)
+struct GroupTable {
+  std::vector<u64> key;
+  std::vector<int64_t> n, pos;
+  std::vector<uint64_t> area2;
+  std::vector<int64_t> sump;
+};
+// one group's terms of GroupedEval::gauc_num / cal_abs (both backends)
+XF_HD double group_auc_term(int64_t n, int64_t pos, uint64_t area2) {
+  return ((double)n * (double)area2) / (2.0 * (double)pos * (double)(n - pos));
+}
+XF_HD double group_cal_term(int64_t sump, int64_t pos) {
+  const double d = (double)sump * (1.0 / 4294967296.0) - (double)pos;
+  return d < 0 ? -d : d;
+}
+XF_HD int64_t group_fx(float p) {
+  const double d = (double)(p > 0.0f ? p : 0.0f) * 4294967296.0;
+  return (int64_t)__builtin_rint(d);
+}
+// Backend::row_group_keys for one row
+XF_HD u64 row_group_key(const BatchView& b, int64_t r, int field) {
+  const RowSpan s = row_span(b, r);
+  if (!b.fgid) return field >= 0 && field < s.len ? b.keys[s.at(field)] : kNoGroup;
+  for (int j = 0; j < s.len; ++j)
+    if (b.fgid[s.at(j)] == field) return b.keys[s.at(j)];
+  return kNoGroup;
+}
+
 class Backend {
  public:
   virtual ~Backend() = default;
@@ -778,6 +832,15 @@ class Backend {
   virtual bool table_in_place() const { return true; }
   // AUC / logloss sums of n predictions (backend memory; labels 0/1 floats)
   virtual EvalMetrics eval_metrics(const float* pctr, const float* labels, int64_t n) = 0;
+  // per-group AUC counts and calibration of n predictions (see GroupedEval;
+  // backend memory).  table != null: also the per-group sums
+  virtual GroupedEval eval_grouped(const float* pctr, const float* labels, const u64* groups,
+                                   int64_t n, GroupTable* table) = 0;
+  // out[r] = the group key of row r for grouping on `field` (backend memory):
+  // with fgid, the key of the row's first occurrence whose field id equals
+  // field; without it (fixed-width batches only) occurrence `field` of the
+  // row; kNoGroup when the row has none
+  virtual void row_group_keys(const BatchView& b, int field, u64* out) = 0;
 };
 
 std::unique_ptr<Backend> make_cpu_backend();

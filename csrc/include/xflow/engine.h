@@ -238,6 +238,18 @@ class Engine {
   EvalMetrics eval_metrics(const float* pctr, const float* labels, int64_t n) {
     return be_->eval_metrics(pctr, labels, n);
   }
+  // per-group AUC counts and calibration of n predictions split by groups[n]
+  // (GroupedEval, backend.h); table: optional per-group sums in key order
+  GroupedEval eval_grouped(const float* pctr, const float* labels, const u64* groups, int64_t n,
+                           GroupTable* table = nullptr) {
+    return be_->eval_grouped(pctr, labels, groups, n, table);
+  }
+  // out[r] = the key row r is grouped by for `field` (Backend::row_group_keys)
+  void row_group_keys(const BatchView& b, int field, u64* out) {
+    if (!b.fgid && b.row_ptr)
+      throw std::invalid_argument("row_group_keys: a CSR batch needs its field ids (fgid)");
+    be_->row_group_keys(b, field, out);
+  }
 
   // ---- stats / introspection -------------------------------------------
   // which = 0: training forward passes, 1: eval_step passes.

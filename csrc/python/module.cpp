@@ -525,6 +525,42 @@ PYBIND11_MODULE(_xflow_native, m) {
              d["line"] = r.line;
              return d;
            })
+      .def("eval_grouped",
+           [](Engine& e, uintptr_t pctr, uintptr_t labels, uintptr_t groups, int64_t n,
+              bool per_group) {
+             GroupedEval g;
+             GroupTable t;
+             {
+               py::gil_scoped_release nogil;
+               g = e.eval_grouped(P<const float>(pctr), P<const float>(labels),
+                                  P<const u64>(groups), n, per_group ? &t : nullptr);
+             }
+             py::dict d;
+             d["n"] = g.n;
+             d["n_nogroup"] = g.n_nogroup;
+             d["groups"] = g.groups;
+             d["groups_used"] = g.groups_used;
+             d["rows_used"] = g.rows_used;
+             d["gauc_num"] = g.gauc_num;
+             d["cal_abs"] = g.cal_abs;
+             if (per_group) {
+               py::dict p;
+               p["key"] = to_np(t.key);
+               p["n"] = to_np(t.n);
+               p["pos"] = to_np(t.pos);
+               p["area2"] = to_np(t.area2);
+               p["sump"] = to_np(t.sump);
+               d["per_group"] = p;
+             }
+             return d;
+           },
+           py::arg("pctr"), py::arg("labels"), py::arg("groups"), py::arg("n"),
+           py::arg("per_group") = false)
+      .def("row_group_keys",
+           [](Engine& e, const BatchView& b, int field, uintptr_t out) {
+             e.row_group_keys(b, field, P<u64>(out));
+           },
+           py::call_guard<py::gil_scoped_release>())
       .def("download_small",
            [](Engine& e, uintptr_t dst, uintptr_t src, size_t bytes) {
              e.download_small(P<void>(dst), P<const void>(src), bytes);

@@ -72,6 +72,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--prune-max-n", type=float, default=-1.0,
                     help="--prune-every, FTRL: drop only keys with every n <= this (0: never "
                          "pushed a non-zero gradient; negative: no bound)")
+    ap.add_argument("--gauc-field", type=int, default=-1,
+                    help="also report the grouped AUC (GAUC) and per-group calibration of the "
+                         "test predictions, grouped by the key of this field id (-1: off)")
     ap.add_argument("--train-block-bytes", type=int, default=2 << 20)
     ap.add_argument("--test-block-bytes", type=int, default=0)
     ap.add_argument("--gpu-parse", action="store_true",
@@ -114,7 +117,7 @@ def config_from_args(a) -> TrainConfig:
         init_push=not a.no_init_push, pred_dir=a.pred_dir, write_pred=not a.no_pred_file,
         checkpoint_dir=a.save,
         save_every=a.save_every, resume_dir=a.resume,
-        prune_every=a.prune_every, prune_max_n=a.prune_max_n,
+        prune_every=a.prune_every, prune_max_n=a.prune_max_n, gauc_field=a.gauc_field,
         metrics_file=a.metrics, async_p2p=a.async_p2p, async_ps=a.async_ps,
         staleness=a.staleness,
         model=ModelConfig(kind=kind, v_dim=a.v_dim, fm_math=a.fm_math, mvm_math=a.mvm_math,

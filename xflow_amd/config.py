@@ -139,6 +139,10 @@ class TrainConfig:
     # only keys with every n <= it (negative: no bound)
     prune_every: int = 0
     prune_max_n: float = -1.0
+    # also report the grouped AUC (GAUC) and per-group calibration of the
+    # predict pass, grouping the test rows by their key of this field id
+    # (Engine.eval_grouped); -1: off
+    gauc_field: int = -1
     metrics_file: str = ""
     async_p2p: bool = False      # lock-step staleness-k steps, pushes riding the next exchange
     # the asynchronous parameter server (parallel/async_ps.py): per-rank server

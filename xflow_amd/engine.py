@@ -523,6 +523,52 @@ class Engine:
         self._sync_stream()
         return dict(self._e.eval_metrics(p.data_ptr(), y.data_ptr(), int(p.numel())))
 
+    def eval_grouped(self, pctr: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor,
+                     per_group: bool = False) -> dict:
+        """Grouped AUC (GAUC) and per-group calibration of predictions on this
+        engine's device, computed there (GroupedEval, csrc/include/xflow/backend.h).
+        ``groups`` is int64 holding u64 bit patterns, like batch keys; a row
+        whose group is all ones (-1) belongs to no group.  Returns the exact
+        counts n / n_nogroup / groups / groups_used / rows_used, the sums
+        gauc_num / cal_abs, and gauc (None when no group has both a positive
+        and a negative row), coverage and group_cal_error derived from them.
+        ``per_group``: also ``per_group`` = numpy arrays key / n / pos / area2 /
+        sump in ascending key order."""
+        if pctr.device != self.device or labels.device != self.device or \
+                groups.device != self.device:
+            raise ValueError("eval_grouped: tensors must be on the engine's device")
+        if groups.dtype != torch.int64:
+            raise TypeError(f"eval_grouped: groups must be int64, got {groups.dtype}")
+        p = pctr.contiguous().float()
+        y = labels.contiguous().float()
+        g = groups.contiguous()
+        if p.numel() != y.numel() or p.numel() != g.numel():
+            raise ValueError("eval_grouped: pctr, labels and groups differ in length")
+        self._sync_stream()
+        r = dict(self._e.eval_grouped(p.data_ptr(), y.data_ptr(), g.data_ptr(), int(p.numel()),
+                                      bool(per_group)))
+        in_groups = r["n"] - r["n_nogroup"]
+        r["gauc"] = r["gauc_num"] / r["rows_used"] if r["groups_used"] > 0 else None
+        r["coverage"] = r["rows_used"] / r["n"] if r["n"] > 0 else 0.0
+        r["group_cal_error"] = r["cal_abs"] / in_groups if in_groups > 0 else 0.0
+        if per_group:
+            r["per_group"] = dict(r["per_group"])
+        return r
+
+    def row_group_keys(self, batch: Batch, field: int) -> torch.Tensor:
+        """The key each row of ``batch`` is grouped by for ``field`` (int64
+        holding u64 bit patterns, on the device): with fgid, the key of the
+        row's first occurrence of that field id; without fgid, on a fixed-width
+        batch, occurrence ``field`` of the row; all ones (no group) when the
+        row has none.  A CSR batch without fgid is an error."""
+        batch.check(self.device)
+        if batch.fgid is None and batch.row_ptr is not None:
+            raise ValueError("row_group_keys: a CSR batch needs its field ids (fgid)")
+        out = torch.empty(batch.rows, dtype=torch.int64, device=self.device)
+        self._sync_stream()
+        self._e.row_group_keys(batch.view(), int(field), out.data_ptr())
+        return out
+
     def export_table(self):
         self._sync_stream()
         return self._e.export_table()

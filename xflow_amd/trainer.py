@@ -25,6 +25,7 @@ Differences by design (MI355X-first):
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import warnings
 import sys
@@ -127,17 +128,21 @@ class Trainer:
         self._resident = None
 
     # ------------------------------------------------------------------ data
-    def _to_batch(self, blk: Optional[dict], used: int, slice_rows: int) -> Batch:
+    def _to_batch(self, blk: Optional[dict], used: int, slice_rows: int,
+                  with_fgid: Optional[bool] = None) -> Batch:
+        """with_fgid: carry the field ids (None: only when the model reads them)."""
         dev = self.device
+        if with_fgid is None:
+            with_fgid = self._with_fgid
         if blk is not None and used > 0 and "packed" in blk:
             # a packed (v3 .xfb) block: its bytes, expanded on the device
             p = blk["packed"]
             if not isinstance(p, torch.Tensor):
                 p = torch.from_numpy(np.array(p)).to(dev)
             return self.engine.unpack_packed(p, int(blk["rows"]), blk["shard"], slice_rows,
-                                             self._with_fgid, used)
+                                             with_fgid, used)
         if blk is not None and used > 0 and isinstance(blk["keys"], torch.Tensor):
-            return self._device_batch(blk, used, slice_rows)
+            return self._device_batch(blk, used, slice_rows, with_fgid)
         if blk is None or used <= 0:
             return Batch(keys=torch.empty(0, dtype=torch.int64, device=dev),
                          labels=torch.empty(0, dtype=torch.float32, device=dev),
@@ -160,14 +165,14 @@ class Trainer:
         k = np.asarray(blk["keys"][:nnz])
         # (compact u32 .xfb keys upload as int32 and widen on the device)
         keys = up(k.view(np.int32) if k.dtype == np.uint32 else k.view(np.int64))
-        fgid = up(blk["fgid"][:nnz]) if self._with_fgid else None
+        fgid = up(blk["fgid"][:nnz]) if with_fgid else None
         if F:
             return Batch(keys=keys, labels=up(blk["labels"][:used]), fgid=fgid, nnz_per_row=F,
                          slice_rows=slice_rows).to_field_major(self.engine)
         return Batch(keys=widen_keys(keys), labels=up(blk["labels"][:used]), row_ptr=up(rp),
                      fgid=fgid, slice_rows=slice_rows)
 
-    def _device_batch(self, blk: dict, used: int, slice_rows: int) -> Batch:
+    def _device_batch(self, blk: dict, used: int, slice_rows: int, with_fgid: bool) -> Batch:
         """Batch over a block already on the device (data.upload.BlockStream,
         or data.textstream.TextStream: its parse counted the used rows' nnz)."""
         if "row_ptr_host" in blk:
@@ -176,7 +181,7 @@ class Trainer:
             if used != blk["rows"] - blk["rows"] % (1 if self.cfg.keep_remainder else self.threads):
                 raise ValueError("text-stream block: used rows differ from the parse's")
             nnz = int(blk["nnz_used"])
-        fgid = blk["fgid"][:nnz] if self._with_fgid else None
+        fgid = blk["fgid"][:nnz] if with_fgid else None
         F = blk["nnz_per_row"] if self.cfg.fixed_width else 0
         if F:
             return Batch(keys=blk["keys"][:nnz], labels=blk["labels"][:used], fgid=fgid,
@@ -421,7 +426,8 @@ class Trainer:
         the host only for the reference's pred_<rank>_<block>.txt file."""
         cfg = self.cfg
         nat = _native.load()
-        dev_p, dev_y = [], []
+        dev_p, dev_y, dev_g = [], [], []
+        gfield = cfg.gauc_field
         reader = None
         if self.rank == 0:
             tpath = shard_path(cfg.test_prefix, 0)
@@ -446,7 +452,14 @@ class Trainer:
                     break
             if self.sharded is None and blk is None:
                 break
-            b = self._to_batch(blk, used, sr)
+            if gfield >= 0:
+                # the grouped figures read the rows' field ids, under every
+                # model; a model that does not read them predicts on the batch
+                # it gets with the option off
+                bg = self._to_batch(blk, used, sr, with_fgid=True)
+                b = bg if self._with_fgid else dataclasses.replace(bg, fgid=None)
+            else:
+                b = self._to_batch(blk, used, sr)
             if aps is not None:
                 pctr = aps.eval_step(b) if b.rows > 0 else None
                 if pctr is None:
@@ -462,12 +475,17 @@ class Trainer:
             if b.rows == 0:
                 continue
             p, y = pctr[:used], b.labels[:used]
+            g = self.engine.row_group_keys(bg, gfield)[:used] if gfield >= 0 else None
             if compat_mvm and sr > 0:
                 keep = torch.from_numpy((np.arange(used) % sr) < min(self.engine.model.v_dim, sr))
                 keep = keep.to(p.device)
                 p, y = p[keep], y[keep]
+                if g is not None:
+                    g = g[keep]
             dev_p.append(p.clone())
             dev_y.append(y.clone())
+            if g is not None:
+                dev_g.append(g)
         if aps is not None:
             aps.pause()
         if self.rank != 0:
@@ -491,9 +509,21 @@ class Trainer:
             if len(ph) <= (1 << 22):
                 res = reference_auc(yh, ph)
         _say(res["line"])
-        self.metrics.log(event="eval", auc=res["auc"], auc_device=dev_auc,
-                         ln_logloss=res["ln_logloss"], logloss_printed=res["logloss_printed"],
-                         n=res["n"])
+        rec = dict(event="eval", auc=res["auc"], auc_device=dev_auc,
+                   ln_logloss=res["ln_logloss"], logloss_printed=res["logloss_printed"],
+                   n=res["n"])
+        if gfield >= 0:
+            gk = torch.cat(dev_g) if dev_g else torch.zeros(0, dtype=torch.int64, device=dev)
+            gr = self.engine.eval_grouped(p, y, gk)
+            _say("gauc(field %d): %s groups=%d/%d rows=%d/%d" % (
+                gfield, "none" if gr["gauc"] is None else "%.6f" % gr["gauc"],
+                gr["groups_used"], gr["groups"], gr["rows_used"], gr["n"]))
+            extra = dict(gauc=gr["gauc"], gauc_field=gfield, gauc_groups=gr["groups"],
+                         gauc_groups_used=gr["groups_used"], gauc_rows_used=gr["rows_used"],
+                         group_cal_error=gr["group_cal_error"])
+            rec.update(extra)
+            res = dict(res, **extra)
+        self.metrics.log(**rec)
         return res
 
     def train(self) -> Optional[dict]:
