@@ -435,7 +435,7 @@ void Engine::ensure_inv() {
 }
 
 void Engine::dedup_(const BatchView& b, int parts, u64* uniq_keys_out, bool want_inv,
-                    int64_t* n_copy) {
+                    int64_t* n_copy, bool lead) {
   if (b.nnz > cfg_.max_nnz) throw std::invalid_argument("batch nnz exceeds max_nnz");
   if (b.rows > cfg_.max_rows) throw std::invalid_argument("batch rows exceed max_rows");
   if (b.col_stride > 0 && (b.row_ptr || b.col_stride < b.rows || b.nnz != b.rows * b.nnz_per_row))
@@ -484,6 +484,7 @@ void Engine::dedup_(const BatchView& b, int parts, u64* uniq_keys_out, bool want
   o.inv = want_inv ? ws_->inv.get() : nullptr;
   o.n_uniq_copy = n_copy;
   o.cap_out = ws_->bcap;
+  o.lead = lead;
   be_->dedup(b.keys, b.nnz, scratch_, o);
 }
 
@@ -519,6 +520,7 @@ StepInputs Engine::step_inputs() const {
   in.pstride = pstride();
   in.slice_cap = slice_cap_;
   in.kdim = cfg_.model.kernel_dim();
+  in.lead_handoff = cfg_.lead_handoff;
   return in;
 }
 
@@ -612,6 +614,14 @@ StepPlan plan_step(const StepInputs& in, int S) {
            : p.rowu ? GradPath::kUniqueRows
            : p.lr16s ? GradPath::kSlotSums
            : GradPath::kSlotRows;
+  // The leader handoff: one-slice LR on the bucket reduction with slot
+  // positions (nothing between the dedup and k_lr_lead reads pos), a
+  // field-major batch of whole kLeadTile-row tiles no wider than the
+  // kernel's register rows, slots below the follower bit.  Does not change
+  // the gradient layout.
+  p.lead = in.lead_handoff && in.gpu && in.kind == kLR && S == 1 && in.red_pairs && !p.upos &&
+           in.field_major && in.rows >= kLeadTile && std::fmod(in.rows, (double)kLeadTile) == 0.0 &&
+           in.fields >= 1.0 && in.fields <= kLeadMaxFields && in.scratch_cap < 2147483648.0;
   return p;
 }
 
@@ -804,7 +814,7 @@ void Engine::train_step(const BatchView& b) {
   if (cfg_.sum_slices && slice_groups(S) > 1)
     throw std::invalid_argument("sum_slices: at most 32 slices per step (ordered pushes: any count)");
   // every layout decision, made once (plan_step)
-  const StepPlan P = plan(S);
+  const StepPlan P = plan(S, b.rows, b.nnz_per_row, !b.row_ptr && b.col_stride > 0 && b.col_stride == b.rows);
   if (P.grad == GradPath::kCsr) {
     train_step_csr(b, S, P.csr_slog2);
     return;
@@ -845,7 +855,7 @@ void Engine::train_step(const BatchView& b) {
   if (fm_keep_w) fm_w_.ensure(*be_, un * ps);
   if (uq) lr_mask_.ensure(*be_, un);
 
-  PullArgs pa = begin_fused_step(b, upos || uo.buf, upos);
+  PullArgs pa = begin_fused_step(b, upos || uo.buf, upos, P.lead);
   if (fm_keep_w) pa.out_w = fm_w_;
   pa.out_nz = nz;
   if (uo.buf && uo.pull_zeroes) {
@@ -872,6 +882,7 @@ void Engine::train_step(const BatchView& b) {
     FwdArgs fa = train_fwd_args(bk, posk, Sg);
     fa.agg_ok = key_bound * Sg * ps < 4294967295.0;  // (32-bit dest * ps, see rows_ok)
     if (upos) fa.red_nuq = ws_->n_uniq;
+    fa.lead = P.lead;  // (one group, one slice: the whole batch's positions)
     // slice bits from the reduction (unique order with the outputs, else
     // slot-indexed), else per occurrence
     if (uq) fa.red_masks = lr_mask_;
@@ -917,9 +928,11 @@ void Engine::train_step(const BatchView& b) {
   end_step();
 }
 
-PullArgs Engine::begin_fused_step(const BatchView& b, bool want_inv, bool upos) {
+PullArgs Engine::begin_fused_step(const BatchView& b, bool want_inv, bool upos, bool lead) {
   if (want_inv) ensure_inv();
-  dedup_(b, 1, nullptr, want_inv);
+  // (leader-encoded positions are not slots: nothing may remap them)
+  if (lead && upos) throw std::logic_error("begin_fused_step: leader handoff with unique positions");
+  dedup_(b, 1, nullptr, want_inv, nullptr, lead);
   ws_->inv_valid = false;  // (the sharded step's send order is not this one)
   if (upos) be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
   guard_inserts(b.nnz);  // (<= nnz new keys; may grow the table first)

@@ -428,6 +428,7 @@ struct PosStream {
 // instead of one per 4 features), and the backward column walk reuses them
 // instead of re-reading pos.  Longer rows take the streaming path.
 constexpr int kLrRegCols = 40;
+static_assert(kLeadMaxFields <= kLrRegCols, "k_lr_lead's register rows");
 
 // Backward of one column: exact LDS aggregation, then the LDS-only barrier
 // and the flush of the table (global atomics left in flight, or pairs).
@@ -462,6 +463,7 @@ __global__ void __launch_bounds__(BLOCK) k_lr(FwdArgs a) {
   __shared__ unsigned short s_list[kRed ? 2 : 1][kRed ? (1 << LOG2R) / 2 : 1];
   __shared__ u32 s_hist[kRed ? kRedMaxBuckets : 1];
   __shared__ u32 s_nlist[3];
+  XF_DASSERT(!a.lead);  // (leader-encoded positions: k_lr_lead only)
   const BatchView& b = a.batch;
   const u32* __restrict__ pos = a.pos;
   const float* __restrict__ wp = a.wpull;
@@ -594,6 +596,133 @@ __global__ void __launch_bounds__(BLOCK) k_lr(FwdArgs a) {
       a.red_hist[(size_t)i * gridDim.x + blockIdx.x] = s_hist[i];
   }
   st.bad |= lagg.bad;
+  flush_stats<BLOCK>(st, a.stats, a.fx_bad);
+  XF_KT(3);
+  XF_KT_FLUSH();
+}
+
+// LR on leader-encoded positions (FwdArgs::lead): the dedup's tile -- one
+// field of kLeadTile consecutive rows -- is this workgroup's column, and its
+// grouping arrives in pos (a leader's slot, or kLeadBit | the leader's row in
+// the tile), so no column is hashed a second time (no ListAgg).
+//   forward   a leader gathers wpull[slot] and publishes the word in LDS at
+//             its own row, kPosChunk columns per barrier (two buffers); a
+//             follower reads its leader's word (same-address LDS reads
+//             broadcast).  The row's sum order stays f = 0..F-1.
+//   backward  a follower adds its fixed-point loss to acc[leader row] (two
+//             buffers alternate, one LDS-only barrier per column); after the
+//             barrier a leader adds its own, zeroes the entry and writes the
+//             record (slot, sum) exactly as ListAgg's claimer does, so the
+//             workgroup's region holds the same record set in another order.
+// Rows of at most kLrRegCols features, S = 1, every row of the grid live.
+__global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
+  XF_KT_DECL;
+  constexpr int BLOCK = kLeadTile;
+  constexpr int C = kLrRegCols;
+  constexpr int Q = kPosChunk;
+  constexpr int kFx = FxBits<1>::kFx;
+  constexpr u32 kIdx = (u32)BLOCK - 1u;
+  __shared__ float s_w[2][Q][BLOCK];
+  __shared__ long long s_acc[2][BLOCK];
+  __shared__ u32 s_hist[kRedMaxBuckets];
+  __shared__ u32 s_n;
+  const BatchView& b = a.batch;
+  const u32* __restrict__ pos = a.pos;
+  const float* __restrict__ wp = a.wpull;
+  const int t = threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * BLOCK + t;
+  XF_DASSERT(a.lead && a.S == 1 && r < b.rows && b.col_stride == b.rows && !b.row_ptr);
+  const int len = (int)b.nnz_per_row;
+  XF_DASSERT(len <= C);
+  u64* __restrict__ region = a.red_pairs + (int64_t)blockIdx.x * BLOCK * len;
+  const int nb = red_active(a, red_shift(1));
+  const int shift = red_geom(a).shift(red_shift(1));
+  s_acc[0][t] = 0ll;
+  s_acc[1][t] = 0ll;
+  for (int i = t; i < nb; i += BLOCK) s_hist[i] = 0u;
+  if (t == 0) s_n = 0u;
+  XF_KT(0);
+  // every position load, then every leader's gather, in flight at once
+  u32 pv[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) pv[j] = j < len ? pos[(int64_t)j * b.col_stride + r] : kLeadBit;
+  float wv[C];
+#pragma unroll
+  for (int j = 0; j < C; ++j) {
+    XF_DASSERT((pv[j] & kLeadBit) || pv[j] <= a.trash_pos);
+    wv[j] = pv[j] & kLeadBit ? 0.0f : wp[pv[j]];
+  }
+#pragma unroll
+  for (int j0 = 0; j0 < C; j0 += Q) {
+    if (j0 >= len) continue;  // (block-uniform)
+    const int buf = (j0 / Q) & 1;
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      if (j0 + q < len && !(pv[j0 + q] & kLeadBit)) s_w[buf][q][t] = wv[j0 + q];
+    // (buffer buf is written again two chunks on, after the next barrier:
+    // every read of this chunk is before that barrier)
+    lds_barrier();
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      if (j0 + q < len && (pv[j0 + q] & kLeadBit)) wv[j0 + q] = s_w[buf][q][pv[j0 + q] & kIdx];
+  }
+  StatAcc st;
+  float wx = 0.0f;
+#pragma unroll
+  for (int j = 0; j < C; ++j)
+    if (j < len) wx += wv[j];
+  const float p = sigmoid_ref(wx);
+  const float y = b.labels[r];
+  const float loss = p - y;
+  if (a.pctr) a.pctr[r] = p;
+  st.add(p, y);
+  XF_KT(1);
+  u32 bad = 0;
+  const long long v = fx_from<kFx>(fx_clamp<kFx>(loss, bad));
+  // (the init's s_acc / s_hist / s_n stores are ordered by the forward's barrier)
+#pragma unroll
+  for (int j = 0; j < C; ++j) {
+    if (j >= len) continue;  // (block-uniform)
+    const int tb = j & 1;
+    const u32 pj = pv[j];
+    const bool follows = (pj & kLeadBit) != 0u;
+    // a trash-slot leader (a full scratch table) emits nothing, as ListAgg
+    const bool emits = !follows && pj != a.trash_pos;
+    if (follows)
+      atomicAdd(reinterpret_cast<unsigned long long*>(&s_acc[tb][pj & kIdx]), (unsigned long long)v);
+    const unsigned long long m = __ballot(emits);
+    u32 idx = 0;
+    if (m) {
+      const int lane = lane_id();
+      const int first = __ffsll((long long)m) - 1;
+      u32 base = 0;
+      if (lane == first) base = atomicAdd(&s_n, (u32)__popcll(m));
+      idx = __shfl(base, first) + (u32)__popcll(m & ((1ull << lane) - 1ull));
+    }
+    if (emits) {
+      XF_DASSERT((int)(pj >> shift) < kRedMaxBuckets);
+      atomicAdd(&s_hist[pj >> shift], 1u);
+    }
+    XF_KT(4);
+    lds_barrier();
+    XF_KT(5);
+    if (!follows) {
+      const long long sum = v + s_acc[tb][t];
+      s_acc[tb][t] = 0ll;
+      if (emits) {
+        XF_DASSERT(idx < (u32)BLOCK * (u32)len);
+        region[idx] = (u64)pj | ((u64)__float_as_uint((float)fx_to_double<kFx>(sum)) << 32);
+      }
+    }
+    XF_KT(6);
+  }
+  __syncthreads();
+  if (t == 0) {
+    a.red_count[blockIdx.x] = s_n;
+    if (a.red_records) atomicAdd(a.red_records, (unsigned long long)s_n);
+  }
+  for (int i = t; i < nb; i += BLOCK) a.red_hist[(size_t)i * gridDim.x + blockIdx.x] = s_hist[i];
+  st.bad |= bad;
   flush_stats<BLOCK>(st, a.stats, a.fx_bad);
   XF_KT(3);
   XF_KT_FLUSH();
@@ -3046,7 +3175,21 @@ void launch_forward_backward(const FwdArgs& a, hipStream_t st) {
         throw std::runtime_error("red_out needs the LR bucket reduction (S > 1: with slice bits)");
       if (a.red_masks && a.S > 1 && !red)
         throw std::runtime_error("red_masks need the LR bucket reduction");
-      if (red) {
+      if (a.lead) {
+        // leader-encoded positions (DedupOut::lead): one workgroup per dedup
+        // tile row block, whatever the batch size (no narrow_rows)
+        const BatchView& b = a.batch;
+        if (!red || a.S != 1 || a.red_masks || a.red_nuq || a.red_csr.cnt || b.row_ptr ||
+            b.col_stride != b.rows || b.rows % kLeadTile || b.nnz_per_row > kLrRegCols ||
+            b.nnz_per_row < 1 || a.trash_pos >= kLeadBit)
+          throw std::runtime_error("LR leader handoff: not a step it covers (plan_step)");
+        const int gr = (int)(b.rows / kLeadTile);
+        hipLaunchKernelGGL(k_lr_lead, dim3(gr), dim3(kLeadTile), 0, st, a);
+#ifdef XFLOW_KTIMING
+        ktime_dump("lr lead (init forward - tail add barrier flush)", 7, st);
+#endif
+        launch_reduction<1>(a, gr, kLeadTile, st);
+      } else if (red) {
         const int R = narrow_rows(a, kLrGroupRows);
         const int gr = (int)((a.batch.rows + R - 1) / R);
         switch (R) {
@@ -3068,11 +3211,13 @@ void launch_forward_backward(const FwdArgs& a, hipStream_t st) {
       break;
     }
     case kFM:
+      if (a.lead) throw std::runtime_error("leader-encoded positions: LR only");
       if (grad) dispatch_fm<true>(a, st);
       else dispatch_fm<false>(a, st);
       break;
     case kMVM:
       // (a batch without occurrences has no field ids to point at)
+      if (a.lead) throw std::runtime_error("leader-encoded positions: LR only");
       if (!a.batch.fgid && a.batch.nnz > 0) throw std::runtime_error("MVM needs field ids (fgid)");
       if (grad) dispatch_mvm<true>(a, st);
       else dispatch_mvm<false>(a, st);

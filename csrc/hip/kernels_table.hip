@@ -113,11 +113,21 @@ __global__ void k_scratch_grow(unsigned long long* __restrict__ ctl, u64 cap_all
 // Hot keys (an int-field value can occur in half the rows) otherwise send one
 // read and one stamp store per occurrence to the same L2 channel; with (a)
 // they cost one per workgroup.
+//
+// kLead (DedupOut::lead, the leader handoff to k_lr_lead): the tile's
+// grouping is handed on instead of thrown away.  A leader's LDS entry also
+// carries its in-tile occurrence index (bits 32..41), a leader still writes
+// pos = its slot and a follower writes pos = kLeadBit | its leader's index.
+// Which occurrence of a key wins the LDS CAS is a race: consumers may rely on
+// the grouping only, never on who leads.  Slots stay below kLeadBit
+// (launch_dedup checks the allocation).
 constexpr int kDedupItems = 4;
 constexpr int kDedupChunk = kBlock * kDedupItems;
 constexpr int kDedupLog2 = 11;  // LDS slots = 2 * kDedupChunk
 static_assert((1 << kDedupLog2) == 2 * kDedupChunk, "LDS dedup table sizing");
+static_assert(kDedupChunk == kLeadTile, "the handoff's tile is the dedup chunk");
 
+template <bool kLead>
 __global__ void __launch_bounds__(kBlock) k_dedup_insert(const u64* __restrict__ keys, int64_t nnz,
                                                          ScratchView sv, u32* __restrict__ pos,
                                                          u32* __restrict__ overflow) {
@@ -229,14 +239,22 @@ __global__ void __launch_bounds__(kBlock) k_dedup_insert(const u64* __restrict__
       c = skeys[sj];
     }
     XF_DASSERT(sj <= sv.cap);
-    t_key[h[j]] = sj;
+    if constexpr (kLead) {
+      XF_DASSERT(sj < kLeadBit);
+      t_key[h[j]] = sj | ((u64)(j * kBlock + (int)threadIdx.x) << 32);
+    } else {
+      t_key[h[j]] = sj;
+    }
     if (sj < sv.cap) sv.stamps[sj] = (unsigned char)sv.epoch;
   }
   __syncthreads();
 #pragma unroll
   for (int j = 0; j < kDedupItems; ++j) {
     int64_t i = base + (int64_t)j * kBlock;
-    if (i < nnz) pos[i] = (u32)t_key[h[j]];
+    if (i >= nnz) continue;
+    const u64 e = t_key[h[j]];
+    if constexpr (kLead) pos[i] = (lead >> j) & 1u ? (u32)e : kLeadBit | (u32)(e >> 32);
+    else pos[i] = (u32)e;
   }
   // one no-return atomic per workgroup for the rebuild counter
   block_count_add<kBlock>(sv.claims, claimed);
@@ -482,8 +500,16 @@ void launch_dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o, hipSt
                        s.ctl);
   }
   int g1 = (int)((nnz + kDedupChunk - 1) / kDedupChunk);
-  hipLaunchKernelGGL(k_dedup_insert, dim3(g1), dim3(kBlock), 0, st, keys, nnz, s, o.pos,
-                     o.overflow);
+  if (o.lead) {
+    // (whole tiles only, and slots -- the trash slot included -- below the follower bit)
+    if (nnz % kDedupChunk || s.cap >= kLeadBit || s.parts != 1)
+      throw std::runtime_error("dedup: the leader handoff needs whole tiles and < 2^31 slots");
+    hipLaunchKernelGGL(k_dedup_insert<true>, dim3(g1), dim3(kBlock), 0, st, keys, nnz, s, o.pos,
+                       o.overflow);
+  } else {
+    hipLaunchKernelGGL(k_dedup_insert<false>, dim3(g1), dim3(kBlock), 0, st, keys, nnz, s, o.pos,
+                       o.overflow);
+  }
   if (!o.block_counts) throw std::runtime_error("dedup: block_counts workspace missing");
   // sized for the allocated capacity; blocks past the active one count zero
   int g2 = (int)((s.cap + kCompactChunk - 1) / kCompactChunk);

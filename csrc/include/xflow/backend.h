@@ -145,7 +145,17 @@ struct DedupOut {
   u32* inv = nullptr;          // optional [cap]: unique-list index of each slot of the batch (HIP)
   int64_t* n_uniq_copy = nullptr;  // optional second destination of the unique count
   unsigned long long* cap_out = nullptr;  // optional: the capacity this batch was deduplicated with
+  // HIP, the leader handoff (StepPlan::lead): pos of a tile's followers is
+  // kLeadBit | the in-tile index of their leader instead of the slot
+  bool lead = false;
 };
+// The leader handoff's tile: kLeadTile consecutive occurrences -- one field of
+// kLeadTile consecutive rows in a field-major batch of a multiple of
+// kLeadTile rows -- deduplicated by one workgroup and walked by one.
+constexpr int kLeadTile = 1024;
+constexpr u32 kLeadBit = 0x80000000u;
+// widest row of the handoff: k_lr_lead keeps a row's positions in registers
+constexpr int kLeadMaxFields = 40;
 
 // Sparse per-(key, slice) gradient sums in CSR form -- the step's pushes as
 // the reference makes them: each Hogwild slice pushes only the keys it
@@ -193,6 +203,8 @@ struct FwdArgs {
   BatchView batch;
   MvmDup mdup;
   const u32* pos = nullptr;        // [nnz]
+  // pos is leader-encoded (DedupOut::lead): only k_lr_lead reads it
+  bool lead = false;
   // dedup slot of overflowed occurrences (the scratch's trash slot, == cap):
   // read as zero weights, never reduced (none: ~0)
   u32 trash_pos = 0xFFFFFFFFu;

@@ -79,6 +79,10 @@ struct EngineConfig {
   // is allocated once and never grows.
   int admit_min_count = 1;
   int admit_log2 = 0;
+  // The leader handoff (StepPlan::lead): on for the steps it
+  // covers; false keeps the column-hashing k_lr everywhere (the A/B switch --
+  // the results are bit-equal either way).
+  bool lead_handoff = true;
 };
 
 // What the single-rank step's gradient layout depends on (Engine::step_inputs)
@@ -96,6 +100,11 @@ struct StepInputs {
   double scratch_cap = 0.0, max_nnz = 0.0, max_rows = 0.0;
   int pstride = 1, slice_cap = 1;
   int kdim = 1;  // latent width of the kernels (ModelSpec::kernel_dim)
+  // the leader handoff's inputs: the switch and the batch's shape (the only
+  // per-batch inputs; Engine::plan(S) without a batch leaves rows at 0: off)
+  bool lead_handoff = true;  // EngineConfig::lead_handoff
+  bool field_major = false;  // fixed width, col_stride == rows
+  double rows = 0.0, fields = 0.0;
 };
 
 // Where a step's gradients land, one per step:
@@ -128,7 +137,11 @@ struct StepPlan {
   bool mvmu = false, fsu = false, rowu = false;  // kUniqueRows (MVM, standard FM, either)
   bool grpst = false;     // the pull stashes (n, z) of multi-parameter FTRL keys
   bool uq = false;        // unique-order slice bits (S > 1 on a unique-order layout)
+  // the leader handoff: the dedup writes leader-encoded positions
+  // (DedupOut::lead) and k_lr_lead consumes them
+  bool lead = false;
 };
+
 StepPlan plan_step(const StepInputs& in, int S);
 
 class Engine {
@@ -204,6 +217,14 @@ class Engine {
   // the single-rank step's layout for S slices (plan_step on this engine)
   StepInputs step_inputs() const;
   StepPlan plan(int S) const { return plan_step(step_inputs(), S); }
+  // ... for a batch of this shape (the leader handoff depends on it)
+  StepPlan plan(int S, int64_t rows, int64_t fields, bool field_major) const {
+    StepInputs in = step_inputs();
+    in.rows = (double)rows;
+    in.fields = (double)fields;
+    in.field_major = field_major;
+    return plan_step(in, S);
+  }
   // bytes of one CSR entry: LR (slice | value) 8, reference FM (slice, B, C)
   // 12, standard FM a full row (csr_row_words)
   int csr_entry_bytes() const {
@@ -441,7 +462,7 @@ class Engine {
   // parts > 1: owner-partitioned scratch (ScratchView::parts); uniq_keys_out
   // redirects the unique-key list (the sharded step's send buffer)
   void dedup_(const BatchView& b, int parts = 1, u64* uniq_keys_out = nullptr,
-              bool want_inv = false, int64_t* n_copy = nullptr);
+              bool want_inv = false, int64_t* n_copy = nullptr, bool lead = false);
   bool sharded_fm_compact() const {
     return red_pairs_ && cfg_.model.kind == kFM && cfg_.model.fm_math == kFmReference &&
            (double)scratch_.cap * slice_cap_ * pstride() < 4294967295.0;
@@ -493,7 +514,7 @@ class Engine {
   // The fused step's prologue: dedup (want_inv: with the slot -> unique index
   // map) -> unique-index positions (upos) -> growth guard; returns the
   // inserting pull over the unique keys for the caller to complete and launch.
-  PullArgs begin_fused_step(const BatchView& b, bool want_inv, bool upos);
+  PullArgs begin_fused_step(const BatchView& b, bool want_inv, bool upos, bool lead = false);
   // The owner's per-source applies of server buffer buf: base (keys / slots at
   // entry 0) offset to every non-empty source of src_offsets in order, the
   // pull's (n, z) stash handed to the first launch only, compact FM rows of a

@@ -104,6 +104,7 @@ py::dict plan_dict(const StepPlan& p) {
   d["rowu"] = p.rowu;
   d["grpst"] = p.grpst;
   d["uq"] = p.uq;
+  d["lead"] = p.lead;
   return d;
 }
 
@@ -131,6 +132,11 @@ StepInputs inputs_from(py::dict d) {
   in.slice_cap = d.contains("slice_cap") ? d["slice_cap"].cast<int>() : Engine::kSliceGroup;
   in.max_rows = d.contains("max_rows") ? d["max_rows"].cast<double>() : (double)(1 << 16);
   in.kdim = m.kernel_dim();
+  // the leader handoff: the switch and the batch's shape
+  in.lead_handoff = flag("lead_handoff", true);
+  in.field_major = flag("field_major", false);
+  in.rows = d.contains("rows") ? d["rows"].cast<double>() : 0.0;
+  in.fields = d.contains("fields") ? d["fields"].cast<double>() : 0.0;
   return in;
 }
 
@@ -389,8 +395,9 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int64_t max_nnz, int max_slices, bool sum_slices, double scratch_factor,
                        int device, bool table_grow, double grow_load, int max_log2_cap,
                        int monitor_lag, int owner_group, double grow_start, bool csr,
-                       int admit_min_count, int admit_log2) {
+                       int admit_min_count, int admit_log2, bool lead_handoff) {
              EngineConfig c;
+             c.lead_handoff = lead_handoff;
              c.admit_min_count = admit_min_count;
              c.admit_log2 = admit_log2;
              c.owner_group = owner_group;
@@ -417,7 +424,8 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("scratch_factor") = 2.5, py::arg("device") = -1,
            py::arg("table_grow") = true, py::arg("grow_load") = 0.8, py::arg("max_log2_cap") = 0,
            py::arg("monitor_lag") = 2, py::arg("owner_group") = 0, py::arg("grow_start") = 0.6,
-           py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0)
+           py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
+           py::arg("lead_handoff") = true)
       .def_property_readonly("admit_bytes", &Engine::admit_bytes)
       .def_property_readonly("admit_log2", &Engine::admit_log2)
       .def("admit_counts",
@@ -447,7 +455,12 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("buf") = 0)
       .def_property_readonly("table_growths", &Engine::table_growths)
       .def_property_readonly("csr_steps", &Engine::csr_steps)
-      .def("step_plan", [](const Engine& e, int S) { return plan_dict(e.plan(S)); })
+      // (rows, fields, field_major: the batch's shape, which the leader handoff depends on)
+      .def("step_plan",
+           [](const Engine& e, int S, int64_t rows, int64_t fields, bool field_major) {
+             return plan_dict(e.plan(S, rows, fields, field_major));
+           },
+           py::arg("S"), py::arg("rows") = 0, py::arg("fields") = 0, py::arg("field_major") = false)
       .def_property_readonly("table_splits", &Engine::table_splits)
       .def_property_readonly("table_geometry", &Engine::table_geometry)
       .def_property_readonly("table_committed", &Engine::table_committed)

@@ -110,6 +110,11 @@ class EngineConfig:
     # log2 capacity + 1).  csrc/include/xflow/engine.h, docs/DESIGN.md §2
     admit_min_count: int = 1
     admit_log2: int = 0
+    # LR leader handoff (docs/DESIGN.md §3): the dedup hands its tile leaders
+    # to the forward/backward kernel on one-slice field-major batches of a
+    # multiple of 1024 rows; False keeps the column-hashing kernel (bit-equal
+    # results, the A/B switch)
+    lead_handoff: bool = True
 
 
 @dataclass

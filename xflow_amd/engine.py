@@ -145,7 +145,8 @@ class Engine:
                            monitor_lag=self.cfg.monitor_lag, owner_group=self.cfg.owner_group,
                            grow_start=self.cfg.grow_start, csr=self.cfg.csr,
                            admit_min_count=self.cfg.admit_min_count,
-                           admit_log2=self.cfg.admit_log2)
+                           admit_log2=self.cfg.admit_log2,
+                           lead_handoff=self.cfg.lead_handoff)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
