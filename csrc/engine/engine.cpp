@@ -115,9 +115,11 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   scratch_.epoch = 0;
   if (be.is_gpu()) {
     // adaptive active capacity (ScratchView::ctl): starts at the allocation
-    scratch_.ctl = scratch_ctl_.alloc(be, 5);
-    unsigned long long c0[5] = {scratch_.cap, 0ull, 0ull, 0ull, 0ull};
+    scratch_.ctl = scratch_ctl_.alloc(be, kScratchCtlWords);
+    unsigned long long c0[kScratchCtlWords] = {scratch_.cap};
+    static_assert(kScratchCtlWords >= 8, "ScratchView::ctl[0..7]");
     be.copy_h2d(scratch_.ctl, c0, sizeof(c0));
+    scratch_.carry = cfg_.scratch_carry;
   }
   block_counts_.alloc(be, scratch_.cap / 4096 + 1);
 
@@ -1608,6 +1610,22 @@ int64_t Engine::scratch_capacity() {
   unsigned long long c = 0;
   be_->copy_d2h(&c, scratch_.ctl, sizeof(c));
   return (int64_t)c;  // ctl[0]: the capacity the next batch is deduplicated with
+}
+
+ScratchStats Engine::scratch_stats() {
+  ScratchStats s;
+  unsigned long long claims = 0;
+  be_->copy_d2h(&claims, scratch_.claims, sizeof(claims));
+  s.occupancy = (int64_t)claims;
+  s.capacity = (int64_t)scratch_.cap;
+  if (scratch_.ctl) {
+    unsigned long long c[kScratchCtlWords];
+    be_->copy_d2h(c, scratch_.ctl, sizeof(c));
+    s.capacity = (int64_t)c[0];
+    s.rebuilds = (int64_t)c[6];
+    s.carried = (int64_t)c[7];
+  }
+  return s;
 }
 
 bool Engine::overflowed() {

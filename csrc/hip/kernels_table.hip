@@ -49,6 +49,11 @@ constexpr int kGroupGridCap = 8192;
 // k_compact_write frees the new capacity's slots right after reading its own
 // (each thread owns 16 slots) -- no extra launches per step.  Without ctl the
 // table is rebuilt by the two kernels below once `claims` exceeds rebuild_at.
+//
+// Carry-over (ScratchView::carry): a rebuild at an unchanged capacity keeps
+// the slots stamped with this epoch -- the batch's own keys, the ones most
+// likely to come back -- and frees the rest; see k_compact_scan and the note
+// on holes above k_dedup_insert.
 __device__ __forceinline__ u64 active_cap(const ScratchView& sv) {
   return sv.ctl ? (u64)sv.ctl[0] : sv.cap;
 }
@@ -121,6 +126,20 @@ __global__ void k_scratch_grow(unsigned long long* __restrict__ ctl, u64 cap_all
 // Which occurrence of a key wins the LDS CAS is a race: consumers may rely on
 // the grouping only, never on who leads.  Slots stay below kLeadBit
 // (launch_dedup checks the allocation).
+//
+// Holes (carry-over rebuilds).  A carry-over rebuild frees some slots of a
+// probe chain and keeps others, so a kept key K can sit behind a hole of its
+// own chain.  The loop below needs no change for that.  Within a batch slots
+// only go from empty to occupied, so "the first slot of K's chain that holds
+// K or is empty" is the same slot for every leader of K: the first leader to
+// reach the hole claims it with one CAS (or loses the CAS to another leader
+// of K and reads K back), every other leader probes from the same home and
+// meets that slot before the old copy.  All of K's occurrences get the one
+// slot and only it is stamped, so K is in the unique list once (the list
+// holds stamped slots only).  The old copy behind it is never reached again,
+// so never stamped again, and goes at the next rebuild; until then it only
+// occupies a slot (the occupancy counter counted it when it was claimed).
+// Which slot a key gets was a CAS race before and no result depends on it.
 constexpr int kDedupItems = 4;
 constexpr int kDedupChunk = kBlock * kDedupItems;
 constexpr int kDedupLog2 = 11;  // LDS slots = 2 * kDedupChunk
@@ -299,15 +318,32 @@ __global__ void __launch_bounds__(kBlock) k_compact_count(ScratchView sv,
 
 // Also sizes the scratch for the next batch (ctl): active cap = the power of
 // two >= kScratchHeadroom x the largest batch seen, rebuilt when it should
-// grow, when it is 4x too large, or when the keys claimed since the last
-// rebuild fill half of it.  A rebuild takes effect here: ctl[3] keeps this
-// batch's capacity for k_compact_write / k_partition_counts, ctl[0] becomes
-// the new one, ctl[2] tells k_compact_write how many slots to free.
+// grow, when it is 4x too large, or when the rebuild counter passes its
+// threshold.  A rebuild takes effect here: ctl[3] keeps this batch's capacity
+// for k_compact_write / k_partition_counts, ctl[0] becomes the new one,
+// ctl[2] tells k_compact_write how many slots to free and ctl[5] how.
+//
+// Without carry-over the counter holds the keys claimed since the last
+// rebuild, a rebuild frees every slot and comes once they pass half the
+// table.  With it (ScratchView::carry) a rebuild at an unchanged capacity of
+// a batch that did not spill keeps the batch's own slots -- `carry` below, the
+// unique count, is exactly their number -- so the counter restarts there and
+// means occupied slots, and the rebuild comes at kCarryRebuildEighths / 8 of
+// the table: a rebuild no longer makes the next batch claim its hot keys
+// again, so it can come earlier and keep the probe chains shorter.  A resize,
+// a spilled batch and a batch over 1 / kScratchHeadroom of the table (a
+// capacity clamped to the allocation) keep the full clear.
+// (interleaved A/B on the bench step, profiles/dedup_carry_ab.txt: 3/8 -- a
+// two-step cycle at insert loads 0.20 / 0.35 -- beat 1/2 and a rebuild in
+// every step; 0 would mean every step)
+constexpr u64 kCarryRebuildEighths = 3;
+static_assert(kCarryRebuildEighths <= 4, "stale claims <= cur / 2 at a batch start");
+
 __global__ void __launch_bounds__(kScanBlock) k_compact_scan(
     unsigned int* __restrict__ counts, int nb, unsigned long long* __restrict__ n_out,
     unsigned long long* __restrict__ claims, unsigned long long* __restrict__ ctl,
     u64 cap_alloc, unsigned long long* __restrict__ n_copy,
-    unsigned long long* __restrict__ cap_out, u32 epoch) {
+    unsigned long long* __restrict__ cap_out, u32 epoch, bool carry_on) {
   // only the blocks of this batch's capacity hold stamps (the rest count 0):
   // at 4x headroom that is 1/8 of the allocation's blocks
   if (ctl) {
@@ -335,13 +371,22 @@ __global__ void __launch_bounds__(kScanBlock) k_compact_scan(
       if (want > cap_alloc) want = cap_alloc;
       const u64 cur = ctl[0];
       // (stale claims <= cur / 2 at a batch start: 2x the most unique keys
-      // seen fit in the active table; a larger surge spills, see ctl[4])
-      const bool rebuild = *claims > cur / 2 || want > cur || want * 4 <= cur;
+      // seen fit in the active table; a larger surge spills, see ctl[4].
+      // With carry-over: at most the threshold <= cur / 2 without a rebuild,
+      // the kept keys <= cur / kScratchHeadroom after one)
+      const bool resize = want > cur || want * 4 <= cur;
+      const u64 full_at = carry_on ? cur * kCarryRebuildEighths / 8 : cur / 2;
+      const bool rebuild = *claims > full_at || resize;
+      const bool keep = carry_on && rebuild && !resize && ctl[4] != epoch &&
+                        carry * kScratchHeadroom <= cur;
       ctl[3] = cur;
       ctl[2] = rebuild ? want : 0ull;
+      ctl[5] = keep ? 1ull : 0ull;
       if (rebuild) {
         ctl[0] = want;
-        *claims = 0ull;
+        *claims = keep ? carry : 0ull;
+        ctl[6] += 1ull;
+        ctl[7] = keep ? carry : 0ull;
       }
     }
     // (the reduction's bucket geometry: a spilled batch's slots reach cap_alloc)
@@ -393,12 +438,22 @@ __global__ void __launch_bounds__(kBlock) k_compact_write(ScratchView sv,
       ip[j] = make_uint4(iv[4 * j], iv[4 * j + 1], iv[4 * j + 2], iv[4 * j + 3]);
   }
   // rebuild decided by k_compact_scan: free this thread's slots of the new
-  // capacity (its own slots, already read above)
+  // capacity (its own slots, already read above).  A carry-over rebuild
+  // (ctl[5]; the capacity is the batch's) keeps the slots stamped with this
+  // epoch: the line goes back whole, kv[j] where hit -- nothing else touches
+  // the scratch while the compaction runs
   const u64 fresh = sv.ctl ? (u64)sv.ctl[2] : 0ull;
   if (base < fresh) {
     ulonglong2* kp = reinterpret_cast<ulonglong2*>(sv.keys + base);
+    if (hit && sv.ctl[5]) {
 #pragma unroll
-    for (int j = 0; j < kCompactItems / 2; ++j) kp[j] = make_ulonglong2(kEmptyKey, kEmptyKey);
+      for (int j = 0; j < kCompactItems / 2; ++j)
+        kp[j] = make_ulonglong2(hit & (1u << (2 * j)) ? kv[2 * j] : kEmptyKey,
+                                hit & (1u << (2 * j + 1)) ? kv[2 * j + 1] : kEmptyKey);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kCompactItems / 2; ++j) kp[j] = make_ulonglong2(kEmptyKey, kEmptyKey);
+    }
   }
 }
 
@@ -516,7 +571,8 @@ void launch_dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o, hipSt
   hipLaunchKernelGGL(k_compact_count, dim3(g2), dim3(kBlock), 0, st, s, o.block_counts);
   hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(kScanBlock), 0, st, o.block_counts, g2,
                      reinterpret_cast<unsigned long long*>(o.n_uniq), s.claims, s.ctl, s.cap,
-                     reinterpret_cast<unsigned long long*>(o.n_uniq_copy), o.cap_out, s.epoch);
+                     reinterpret_cast<unsigned long long*>(o.n_uniq_copy), o.cap_out, s.epoch,
+                     s.carry);
   hipLaunchKernelGGL(k_compact_write, dim3(g2), dim3(kBlock), 0, st, s, o.block_counts,
                      o.uniq_keys, o.uniq_pos, o.inv);
   XF_HIP_CHECK(hipGetLastError());

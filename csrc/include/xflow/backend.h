@@ -95,11 +95,21 @@ struct ScratchView {
   // rebuild (0: none), ctl[3] = the cap the current batch was deduplicated with,
   // ctl[4] = epoch of the last batch that spilled past the active capacity (a
   // full active table: the insert probes on into [ctl[0], cap) and that
-  // batch's compaction and reduction cover the whole allocation).
+  // batch's compaction and reduction cover the whole allocation),
+  // ctl[5] = how the compaction frees those slots: 0 all of them, 1 a
+  // carry-over rebuild (`carry` below) that keeps the slots stamped with this
+  // epoch, ctl[6] = rebuilds the compaction has decided so far, ctl[7] = keys
+  // the last of them carried over (0: a full clear).  kScratchCtlWords words;
+  // ctl[6..7] are counters for Engine::scratch_stats, nothing reads them on
+  // the device.
   // The table is probed modulo ctl[0]; the compaction scan re-sizes it to
   // kScratchHeadroom x the largest batch seen (a table that fits the Infinity
   // Cache instead of one sized for all-distinct batches).  Null: use cap.
   unsigned long long* ctl = nullptr;
+  // (with ctl) EngineConfig::scratch_carry: a rebuild at an unchanged
+  // capacity keeps the batch's own keys (k_compact_scan), and `claims` counts
+  // occupied slots instead of the keys claimed since the last rebuild
+  bool carry = false;
   // (with ctl) > 0 when this batch has more occurrences than any before, by
   // this factor: the active capacity grows to kScratchHeadroom x (most unique
   // keys seen) x grow before the insert, so a batch larger than the ones the
@@ -134,6 +144,7 @@ XF_HD int64_t encode_count(int64_t count, int64_t seq) {
 constexpr u32 kStampEpochs = 255;
 constexpr u64 kScratchHeadroom = 4;      // active cap >= 4 x max unique keys per batch (A/B: 8 and 2 slower)
 constexpr u64 kScratchMinCap = 1ull << 16;
+constexpr int kScratchCtlWords = 8;      // ScratchView::ctl
 
 struct DedupOut {
   u32* pos = nullptr;          // [nnz] scratch slot of each occurrence

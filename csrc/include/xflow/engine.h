@@ -83,6 +83,23 @@ struct EngineConfig {
   // covers; false keeps the column-hashing k_lr everywhere (the A/B switch --
   // the results are bit-equal either way).
   bool lead_handoff = true;
+  // Carry-over rebuilds of the GPU dedup scratch (ScratchView::carry, DESIGN
+  // §3): a rebuild at an unchanged capacity keeps the batch's own keys.
+  // false: every rebuild frees the whole table (the A/B switch -- the results
+  // are bit-equal either way).
+  bool scratch_carry = true;
+};
+
+// The dedup scratch's counters (Engine::scratch_stats).  The CPU backend has
+// a fixed capacity and counts no rebuilds: it reports its capacity and the
+// keys claimed since its last clear.
+struct ScratchStats {
+  int64_t capacity = 0;   // active capacity (ScratchView::ctl[0])
+  // the rebuild counter: occupied slots with carry-over, else the keys
+  // claimed since the last rebuild
+  int64_t occupancy = 0;
+  int64_t rebuilds = 0;   // rebuilds the compaction decided (ctl[6])
+  int64_t carried = 0;    // keys the last of them kept (ctl[7]; 0: a full clear)
 };
 
 // What the single-rank step's gradient layout depends on (Engine::step_inputs)
@@ -278,6 +295,7 @@ class Engine {
   int64_t n_unique();            // unique keys of the last prepared batch (syncs)
   int64_t table_size();          // occupied slots (syncs)
   int64_t scratch_capacity();    // active dedup scratch capacity (adaptive on the GPU; syncs)
+  ScratchStats scratch_stats();  // (syncs: tests and tools only)
   uint64_t table_capacity() const { return table_.cap; }
   size_t table_bytes() const { return table_bytes_; }
   bool overflowed();

@@ -395,9 +395,11 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int64_t max_nnz, int max_slices, bool sum_slices, double scratch_factor,
                        int device, bool table_grow, double grow_load, int max_log2_cap,
                        int monitor_lag, int owner_group, double grow_start, bool csr,
-                       int admit_min_count, int admit_log2, bool lead_handoff) {
+                       int admit_min_count, int admit_log2, bool lead_handoff,
+                       bool scratch_carry) {
              EngineConfig c;
              c.lead_handoff = lead_handoff;
+             c.scratch_carry = scratch_carry;
              c.admit_min_count = admit_min_count;
              c.admit_log2 = admit_log2;
              c.owner_group = owner_group;
@@ -425,7 +427,7 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("table_grow") = true, py::arg("grow_load") = 0.8, py::arg("max_log2_cap") = 0,
            py::arg("monitor_lag") = 2, py::arg("owner_group") = 0, py::arg("grow_start") = 0.6,
            py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
-           py::arg("lead_handoff") = true)
+           py::arg("lead_handoff") = true, py::arg("scratch_carry") = true)
       .def_property_readonly("admit_bytes", &Engine::admit_bytes)
       .def_property_readonly("admit_log2", &Engine::admit_log2)
       .def("admit_counts",
@@ -690,6 +692,16 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def("n_unique", &Engine::n_unique)
       .def("table_size", &Engine::table_size)
       .def("scratch_capacity", &Engine::scratch_capacity)
+      .def("scratch_stats",
+           [](Engine& e) {
+             const ScratchStats s = e.scratch_stats();
+             py::dict d;
+             d["capacity"] = s.capacity;
+             d["occupancy"] = s.occupancy;
+             d["rebuilds"] = s.rebuilds;
+             d["carried"] = s.carried;
+             return d;
+           })
       .def("overflowed", &Engine::overflowed)
       .def("nonzero_weights", &Engine::nonzero_weights)
       .def("export_table",

@@ -304,8 +304,8 @@ int main(int argc, char** argv) {
     sv.claims = dalloc<unsigned long long>(1);
     sv.rebuild_at = cap / 2;
     if (getenv("KB_ADAPT") && atoi(getenv("KB_ADAPT"))) {
-      sv.ctl = dalloc<unsigned long long>(4);
-      unsigned long long c0[4] = {cap, 0, 0, 0};
+      sv.ctl = dalloc<unsigned long long>(kScratchCtlWords);
+      unsigned long long c0[kScratchCtlWords] = {cap};
       XF_HIP_CHECK(hipMemcpy(sv.ctl, c0, sizeof(c0), hipMemcpyHostToDevice));
     }
     DedupOut o;

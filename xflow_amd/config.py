@@ -115,6 +115,10 @@ class EngineConfig:
     # multiple of 1024 rows; False keeps the column-hashing kernel (bit-equal
     # results, the A/B switch)
     lead_handoff: bool = True
+    # carry-over rebuilds of the GPU dedup scratch (docs/DESIGN.md §3): a
+    # rebuild at an unchanged capacity keeps the batch's own keys; False frees
+    # the whole table at every rebuild (bit-equal results, the A/B switch)
+    scratch_carry: bool = True
 
 
 @dataclass

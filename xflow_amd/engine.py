@@ -146,7 +146,8 @@ class Engine:
                            grow_start=self.cfg.grow_start, csr=self.cfg.csr,
                            admit_min_count=self.cfg.admit_min_count,
                            admit_log2=self.cfg.admit_log2,
-                           lead_handoff=self.cfg.lead_handoff)
+                           lead_handoff=self.cfg.lead_handoff,
+                           scratch_carry=self.cfg.scratch_carry)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -488,6 +489,16 @@ class Engine:
         """Active dedup scratch capacity (device-adaptive on the GPU)."""
         self._sync_stream()
         return int(self._e.scratch_capacity())
+
+    def scratch_stats(self) -> dict:
+        """The dedup scratch's counters: ``capacity`` (active), ``occupancy``
+        (the rebuild counter: occupied slots with scratch_carry, else the keys
+        claimed since the last rebuild), ``rebuilds`` decided by the compaction
+        so far and the keys ``carried`` by the last of them (0: a full clear).
+        Synchronises: for tests and tools.  The CPU backend reports its fixed
+        capacity and its claims, and no rebuilds."""
+        self._sync_stream()
+        return {k: int(v) for k, v in self._e.scratch_stats().items()}
 
     def overflowed(self) -> bool:
         self._sync_stream()
