@@ -56,7 +56,7 @@ void launch_unpack_block(const UnpackArgs& a, hipStream_t st);
 void launch_field_major(const void* src, void* dst, int64_t rows, int F, int elem_bytes, bool widen,
                         hipStream_t st);
 
-// kernels_model.hip
+// kernels_model.hip (the kernels: kernels_lr / _fm / _mvm / _reduce / _reduce_vec .hip)
 void launch_forward_backward(const FwdArgs& a, hipStream_t st);
 void launch_slice_masks(const BatchView& b, const u32* pos, u32* tmask, hipStream_t st);
 

@@ -156,7 +156,9 @@ run_kbench() {
   if [ ! -x build/kbench ] || [ -n "$REBUILD" ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
       -Icsrc/include -Icsrc/hip tools/kbench.hip csrc/hip/kernels_table.hip \
-      csrc/hip/kernels_model.hip csrc/hip/kernels_synth.hip -o build/kbench || exit 1
+      csrc/hip/kernels_model.hip csrc/hip/kernels_lr.hip csrc/hip/kernels_fm.hip \
+      csrc/hip/kernels_mvm.hip csrc/hip/kernels_reduce.hip csrc/hip/kernels_reduce_vec.hip \
+      csrc/hip/kernels_synth.hip -o build/kbench || exit 1
   fi
   timeout -k 10 300 build/kbench ${1:-} > "$O/kbench.log" 2>&1 || { echo "kbench failed"; tail -20 "$O/kbench.log"; exit 1; }
   cat "$O/kbench.log"

@@ -202,7 +202,7 @@ def test_unadmitted_keys_neither_train_nor_disturb(device, S):
     Every row lists its unadmitted occurrences last, in both runs, so that
     removing them leaves each remaining occurrence at its position in the
     row: the GPU gradient reduction rounds a workgroup's partial sum per row
-    position (kernels_model.hip ListAgg::column), with or without admission,
+    position (model_common.h ListAgg::column), with or without admission,
     so a key's bits depend on the positions of its occurrences."""
     LOG2, MIN = 22, 2
     sched = _anchored()

@@ -27,7 +27,7 @@ BUILD = os.path.join(ROOT, "build")
 # (XF_DASSERT in csrc/hip/hip_util.h); objects go to their own directory
 DEVICE_ASSERT = os.environ.get("XFLOW_DEVICE_ASSERT", "0") not in ("", "0")
 # XFLOW_KTIMING=1: diagnostic build with per-phase cycle counters in the
-# standard-FM producer (XF_KT in csrc/hip/kernels_model.hip), own directory
+# standard-FM producer (XF_KT in csrc/hip/model_common.h), own directory
 KTIMING = os.environ.get("XFLOW_KTIMING", "0") not in ("", "0")
 OBJ = os.path.join(BUILD, "obj-dassert" if DEVICE_ASSERT else ("obj-ktime" if KTIMING else "obj"))
 PKG = os.path.join(ROOT, "xflow_amd")
