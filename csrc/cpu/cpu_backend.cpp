@@ -445,6 +445,28 @@ class CpuBackend final : public Backend {
         std::memcpy(d + ((int64_t)f * rows + r) * elem_bytes, s + (r * F + f) * elem_bytes,
                     (size_t)elem_bytes);
   }
+  void shuffle_rows(const ShuffleArgs& a) override {
+    check_shuffle_args(a);
+    const BatchView& s = a.src;
+    const ShufflePerm pi = shuffle_perm((u64)s.rows, a.seed);
+    const u32* k32 = reinterpret_cast<const u32*>(s.keys);
+    if (s.row_ptr) a.row_ptr[0] = 0;
+    int64_t o = 0;  // CSR: the next destination entry
+    for (int64_t i = 0; i < s.rows; ++i) {
+      const int64_t p = (int64_t)pi.at((u64)i);
+      a.labels[i] = s.labels[p];
+      const RowSpan sp = row_span(s, p);
+      for (int j = 0; j < sp.len; ++j) {
+        const int64_t from = sp.at(j);
+        const int64_t to = s.row_ptr ? o + j
+                                     : (a.field_major_out ? (int64_t)j * s.rows + i
+                                                          : i * s.nnz_per_row + j);
+        a.keys[to] = a.key_bytes == 4 ? (u64)k32[from] : s.keys[from];
+        if (s.fgid) a.fgid[to] = s.fgid[from];
+      }
+      if (s.row_ptr) a.row_ptr[i + 1] = (int32_t)(o += sp.len);
+    }
+  }
   int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                        int64_t max_rows) override {
     const int W = t.L.stride - 2;

@@ -267,6 +267,26 @@ std::vector<int64_t> Engine::parse_text(const char* text, int64_t n, u64* keys, 
   return {c[0], c[1], c[0] > 0 ? c[2] : 0, c[3], c[6]};
 }
 
+void Engine::shuffle_rows(const BatchView& src, u64 seed, u64* keys, int32_t* fgid, float* labels,
+                          int32_t* row_ptr, bool field_major_out, int key_bytes) {
+  if (src.col_stride > 0)
+    throw std::invalid_argument("shuffle_rows: a field-major source (row-major or CSR only)");
+  if (src.rows > cfg_.max_rows) throw std::invalid_argument("shuffle_rows: batch rows exceed max_rows");
+  if (src.nnz > cfg_.max_nnz) throw std::invalid_argument("shuffle_rows: batch nnz exceeds max_nnz");
+  ShuffleArgs a;
+  a.src = src;
+  a.key_bytes = key_bytes;
+  a.seed = seed;
+  a.keys = keys;
+  a.fgid = fgid;
+  a.labels = labels;
+  a.row_ptr = row_ptr;
+  a.field_major_out = field_major_out;
+  // (the workspace of the CSR form: allocated on the first CSR call, never again)
+  if (src.row_ptr && be_->is_gpu()) a.len = shuf_len_.ensure(*be_, (size_t)cfg_.max_rows + 1);
+  be_->shuffle_rows(a);
+}
+
 void Engine::count_records(bool on) {
   if (on && !rec_count_) rec_count_.alloc_zero(*be_, 1);
   rec_on_ = on;

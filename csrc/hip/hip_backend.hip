@@ -241,6 +241,22 @@ class HipBackend final : public Backend {
                    bool widen) override {
     hip::launch_field_major(src, dst, rows, F, elem_bytes, widen, stream_);
   }
+  void shuffle_rows(const ShuffleArgs& a) override {
+    check_shuffle_args(a);
+    if (!a.src.row_ptr) {
+      hip::launch_shuffle_fixed(a, stream_);
+      return;
+    }
+    if (a.src.rows <= 0) {
+      memset(a.row_ptr, 0, sizeof(int32_t));
+      return;
+    }
+    if (!a.len) throw std::invalid_argument("shuffle_rows: a CSR batch needs the len workspace");
+    hip::launch_shuffle_len(a, stream_);
+    // (the exclusive offsets of the lengths are the new row_ptr; [rows] = nnz)
+    scan_u32(a.len, reinterpret_cast<u32*>(a.row_ptr), nullptr, a.src.rows);
+    hip::launch_shuffle_gather(a, stream_);
+  }
   int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                        int64_t max_rows) override {
     hip::launch_table_export(t, keys_out, words_out, max_rows, counter_, stream_);

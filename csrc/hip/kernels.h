@@ -56,6 +56,12 @@ void launch_unpack_block(const UnpackArgs& a, hipStream_t st);
 void launch_field_major(const void* src, void* dst, int64_t rows, int F, int elem_bytes, bool widen,
                         hipStream_t st);
 
+// kernels_shuffle.hip (ShuffleArgs): fixed width in one pass; CSR as lengths +
+// labels, launch_scan_u32 of a.len into a.row_ptr, then the entries
+void launch_shuffle_fixed(const ShuffleArgs& a, hipStream_t st);
+void launch_shuffle_len(const ShuffleArgs& a, hipStream_t st);
+void launch_shuffle_gather(const ShuffleArgs& a, hipStream_t st);
+
 // kernels_model.hip (the kernels: kernels_lr / _fm / _mvm / _reduce / _reduce_vec .hip)
 void launch_forward_backward(const FwdArgs& a, hipStream_t st);
 void launch_slice_masks(const BatchView& b, const u32* pos, u32* tmask, hipStream_t st);

@@ -589,6 +589,50 @@ struct UnpackArgs {
   int32_t* fgid = nullptr;                 // out [F][rows], optional
 };
 
+// Per-epoch row shuffling (Backend::shuffle_rows): destination row i receives
+// source row shuffle_index(i, src.rows, seed) (common.h) -- its keys, its
+// field ids when src.fgid is set, its label; the entries inside a row keep
+// their order.  The source is a CSR batch or a fixed-width ROW-major one
+// (col_stride == 0): a row is then one contiguous run, so the gather reads
+// whole rows.  (A field-major source would read one element per cache line;
+// it is refused.)  Fixed width: the destination is field-major ([F][rows],
+// the layout the step reads) or row-major, keys of key_bytes 4 (compact
+// .xfb keys) come out zero-extended to u64, nnz_per_row <= 64 (the HIP tile,
+// as Backend::field_major).  CSR: u64 keys, the destination's row_ptr is
+// written too.  All pointers are backend memory; nothing syncs.
+struct ShuffleArgs {
+  BatchView src;                   // (keys: key_bytes per element)
+  int key_bytes = 8;               // 8, or 4 (fixed width only)
+  u64 seed = 0;
+  u64* keys = nullptr;             // out [nnz]
+  int32_t* fgid = nullptr;         // out [nnz] (with src.fgid)
+  float* labels = nullptr;         // out [rows]
+  int32_t* row_ptr = nullptr;      // out [rows + 1] (CSR)
+  bool field_major_out = false;    // fixed width: [F][rows] instead of [rows][F]
+  u32* len = nullptr;              // CSR, HIP: [rows] workspace (the rows' lengths)
+};
+// what both backends refuse
+inline void check_shuffle_args(const ShuffleArgs& a) {
+  const BatchView& s = a.src;
+  if (s.col_stride > 0)
+    throw std::invalid_argument("shuffle_rows: a field-major source (row-major or CSR only)");
+  if (s.rows < 0 || s.nnz < 0 || s.nnz > 0x7fffffffll)
+    throw std::invalid_argument("shuffle_rows: bad batch size");
+  if (s.row_ptr) {
+    if (a.key_bytes != 8) throw std::invalid_argument("shuffle_rows: CSR keys are 8 bytes");
+    if (a.field_major_out) throw std::invalid_argument("shuffle_rows: a CSR batch stays CSR");
+    if (!a.row_ptr) throw std::invalid_argument("shuffle_rows: a CSR batch needs row_ptr out");
+  } else {
+    if (a.key_bytes != 8 && a.key_bytes != 4)
+      throw std::invalid_argument("shuffle_rows: 4- or 8-byte keys");
+    if (s.nnz_per_row <= 0 || s.nnz != s.rows * s.nnz_per_row)
+      throw std::invalid_argument("shuffle_rows: fixed width needs nnz == rows * nnz_per_row");
+  }
+  if ((s.rows > 0 && (!s.labels || !a.labels)) ||
+      (s.nnz > 0 && (!s.keys || !a.keys || (s.fgid && !a.fgid))))
+    throw std::invalid_argument("shuffle_rows: null array");
+}
+
 struct SynthArgs {                 // synthetic Criteo-shaped batch generator
   u64* keys = nullptr;
   float* labels = nullptr;
@@ -813,6 +857,8 @@ class Backend {
                            bool widen = false) = 0;
   // packed .xfb block -> field-major keys / labels / fgid (see UnpackArgs)
   virtual void unpack_block(const UnpackArgs& a) = 0;
+  // the batch with its rows permuted by shuffle_index (see ShuffleArgs)
+  virtual void shuffle_rows(const ShuffleArgs& a) = 0;
   // count occupied slots / dump table rows (checkpointing); returns rows written
   virtual int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                                int64_t max_rows) = 0;

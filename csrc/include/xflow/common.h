@@ -43,6 +43,51 @@ XF_HD u64 fmix64(u64 h) {
   return h;
 }
 
+// Row shuffling (Backend::shuffle_rows, docs/DESIGN.md §9): a keyed bijection
+// of [0, n) that needs no memory and no sort, so every lane computes its own
+// pi(i).  A 4-round Feistel network over the 2h-bit domain 2^(2h) >= n
+// (h = half the bit length of n - 1, rounded up; the domain is below 4n),
+// cycle-walked back into [0, n): a pass maps the domain onto itself one to
+// one, so repeating it from i until the value falls below n is a bijection
+// of [0, n) (the walk from i < n returns to i at the latest, so it ends).
+// Round keys k_r = fmix64(seed + 0x9E3779B97F4A7C15 * (r + 1)), r = 0..3;
+// one pass: L = x >> h, R = x & mask; four times (L, R) = (R, (L ^ fmix64(R ^
+// k_r)) & mask); x = L << h | R.  Well mixed at block sizes (thousands of
+// rows), not uniform over all permutations at tiny n.
+constexpr int kShuffleRounds = 4;
+struct ShufflePerm {
+  u64 n = 0, mask = 0;
+  int h = 0;
+  u64 k[kShuffleRounds] = {};
+  XF_HD u64 at(u64 i) const {
+    if (n <= 1) return i;
+    u64 x = i;
+    do {
+      u64 L = x >> h, R = x & mask;
+      for (int r = 0; r < kShuffleRounds; ++r) {
+        const u64 t = (L ^ fmix64(R ^ k[r])) & mask;
+        L = R;
+        R = t;
+      }
+      x = (L << h) | R;
+    } while (x >= n);
+    return x;
+  }
+};
+XF_HD ShufflePerm shuffle_perm(u64 n, u64 seed) {
+  ShufflePerm p;
+  p.n = n;
+  if (n <= 1) return p;
+  const int b = 64 - __builtin_clzll(n - 1);  // bit length of n - 1
+  p.h = (b + 1) / 2 < 1 ? 1 : (b + 1) / 2;
+  p.mask = (1ull << p.h) - 1;
+  for (int r = 0; r < kShuffleRounds; ++r)
+    p.k[r] = fmix64(seed + 0x9E3779B97F4A7C15ull * (u64)(r + 1));
+  return p;
+}
+// pi(i): the source row of destination row i
+XF_HD u64 shuffle_index(u64 i, u64 n, u64 seed) { return shuffle_perm(n, seed).at(i); }
+
 // Synthetic "historic" key i of a prefilled table (Backend::table_prefill):
 // bit 62 set, so it never equals a hashed feature below 2^62.
 XF_HD u64 prefill_key(u64 seed, u64 i) {

@@ -289,6 +289,16 @@ class Engine {
     be_->row_group_keys(b, field, out);
   }
 
+  // Per-epoch row shuffling (Backend::shuffle_rows, ShuffleArgs): destination
+  // row i of the outputs (backend memory) receives row shuffle_index(i, rows,
+  // seed) of src, a CSR or fixed-width row-major batch within max_rows /
+  // max_nnz; a field-major source is refused.  Fixed width: keys of key_bytes
+  // 4 are zero-extended, field_major_out writes [F][rows] (row_ptr unused).
+  // Queued on the engine's stream: no allocation after the first CSR call,
+  // no host sync.
+  void shuffle_rows(const BatchView& src, u64 seed, u64* keys, int32_t* fgid, float* labels,
+                    int32_t* row_ptr, bool field_major_out, int key_bytes = 8);
+
   // ---- stats / introspection -------------------------------------------
   // which = 0: training forward passes, 1: eval_step passes.
   LossStats read_stats(bool reset, int which = 0);
@@ -641,6 +651,7 @@ class Engine {
   DeviceBuffer<u32> red_vmax_;                   // MVM: per-step scale words [2], dup words [2]
   DeviceBuffer<u32> text_ws_;                    // parse_text workspace
   DeviceBuffer<long long> text_counts_;          // parse_text counts [7]
+  DeviceBuffer<u32> shuf_len_;                   // shuffle_rows (CSR): the rows' lengths [max_rows + 1]
   mutable int vmax_parity_ = 0;
   bool rec_on_ = false;
   int log2_cap_ = 0, max_log2_cap_ = 31;

@@ -194,6 +194,16 @@ PYBIND11_MODULE(_xflow_native, m) {
     ok = (std::fclose(f) == 0) && ok;
     if (!ok) throw std::runtime_error("write_pred: write failed " + path);
   });
+  // the row-shuffle permutation (shuffle_index, common.h): out[i] = the source
+  // row of destination row i, from the host function the backends share
+  m.def("shuffle_permutation", [](int64_t n, uint64_t seed) {
+    if (n < 0) throw std::invalid_argument("shuffle_permutation: n < 0");
+    py::array_t<int64_t> out((py::ssize_t)n);
+    int64_t* o = out.mutable_data();
+    const ShufflePerm pi = shuffle_perm((u64)n, seed);
+    for (int64_t i = 0; i < n; ++i) o[i] = (int64_t)pi.at((u64)i);
+    return out;
+  }, py::arg("n"), py::arg("seed"));
   m.def("feature_hash", [](py::bytes b) {
     std::string s = b;
     return feature_hash(s.data(), s.size());
@@ -575,6 +585,15 @@ PYBIND11_MODULE(_xflow_native, m) {
            [](Engine& e, const BatchView& b, int field, uintptr_t out) {
              e.row_group_keys(b, field, P<u64>(out));
            },
+           py::call_guard<py::gil_scoped_release>())
+      .def("shuffle_rows",
+           [](Engine& e, const BatchView& b, uint64_t seed, uintptr_t keys, uintptr_t fgid,
+              uintptr_t labels, uintptr_t row_ptr, bool field_major_out, int key_bytes) {
+             e.shuffle_rows(b, seed, P<u64>(keys), P<int32_t>(fgid), P<float>(labels),
+                            P<int32_t>(row_ptr), field_major_out, key_bytes);
+           },
+           py::arg("batch"), py::arg("seed"), py::arg("keys"), py::arg("fgid"), py::arg("labels"),
+           py::arg("row_ptr"), py::arg("field_major_out"), py::arg("key_bytes") = 8,
            py::call_guard<py::gil_scoped_release>())
       .def("download_small",
            [](Engine& e, uintptr_t dst, uintptr_t src, size_t bytes) {

@@ -82,6 +82,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "field ids bit-equal to the host parser)")
     ap.add_argument("--resident", action="store_true",
                     help="keep the training shard in HBM after the first epoch (no re-read)")
+    ap.add_argument("--shuffle", action="store_true",
+                    help="reshuffle each block's rows on the device every epoch (with --resident "
+                         "also the block order); not for packed shards or --serial-slices")
+    ap.add_argument("--shuffle-seed", type=int, default=0,
+                    help="--shuffle: the run's seed (a block's order depends only on it, the "
+                         "epoch, the block and the rank)")
     ap.add_argument("--csr-only", action="store_true",
                     help="train fixed-width blocks through the CSR path as well")
     ap.add_argument("--block-rows", type=int, default=0,
@@ -112,6 +118,7 @@ def config_from_args(a) -> TrainConfig:
         train_prefix=a.train_prefix, test_prefix=a.test_prefix, epochs=a.epochs,
         threads=a.threads, train_block_bytes=a.train_block_bytes, block_rows=a.block_rows,
         resident=a.resident, fixed_width=not a.csr_only, gpu_parse=a.gpu_parse,
+        shuffle=a.shuffle, shuffle_seed=a.shuffle_seed,
         test_block_bytes=a.test_block_bytes, serial_slices=a.serial_slices,
         keep_remainder=a.keep_remainder, mvm_predict_compat=a.mvm_predict_compat,
         init_push=not a.no_init_push, pred_dir=a.pred_dir, write_pred=not a.no_pred_file,

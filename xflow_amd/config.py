@@ -131,6 +131,12 @@ class TrainConfig:
     block_rows: int = 0          # rows per block of binary (.xfb) shards; 0 => 65536
     fixed_width: bool = True     # blocks whose rows all hold F features train field-major
     resident: bool = False       # keep the first epoch's device batches in HBM for the rest
+    # reshuffle every block's used rows on the device each epoch
+    # (Engine.shuffle_batch; with resident also the block order): the seed of
+    # a block is a pure function of (shuffle_seed, epoch, block, rank), so a
+    # resumed run shuffles like an uninterrupted one (docs/DESIGN.md §9)
+    shuffle: bool = False
+    shuffle_seed: int = 0
     copy_threads: int = 8        # host threads staging a block into pinned memory
     gpu_parse: bool = False      # libffm text shards tokenised on the GPU (data/textstream.py)
     test_block_bytes: int = 0    # 0 => 4 MB LR, 2 MB FM/MVM

@@ -54,11 +54,15 @@ class Batch:
         v.col_stride = self.rows if self.field_major else 0
         return v
 
-    def check(self, device: torch.device) -> None:
+    def check(self, device: torch.device, compact_ok: bool = False) -> None:
+        """compact_ok: the keys may also be compact u32 keys in an int32 tensor
+        (what Engine.shuffle_batch and to_field_major widen)."""
         for name, t, dt in (("keys", self.keys, torch.int64), ("labels", self.labels, torch.float32),
                             ("row_ptr", self.row_ptr, torch.int32), ("fgid", self.fgid, torch.int32)):
             if t is None:
                 continue
+            if name == "keys" and compact_ok and t.dtype == torch.int32:
+                dt = torch.int32
             if t.dtype != dt:
                 raise TypeError(f"batch.{name} must be {dt}, got {t.dtype}")
             if t.device != device:
@@ -112,6 +116,14 @@ def widen_keys(keys: torch.Tensor) -> torch.Tensor:
     if keys.dtype != torch.int32:
         raise TypeError(f"keys must be int64 or compact int32, got {keys.dtype}")
     return keys.to(torch.int64) & 0xFFFFFFFF
+
+
+def shuffle_permutation(n: int, seed: int) -> np.ndarray:
+    """The row-shuffle permutation of ``n`` rows under ``seed`` (int64 [n]):
+    element i is the source row of destination row i.  A keyed bijection of
+    [0, n) (shuffle_index, csrc/include/xflow/common.h) computed by the
+    native host function both backends share; the seed is taken modulo 2^64."""
+    return native.load().shuffle_permutation(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
 def _device_index(device: torch.device) -> int:
@@ -580,6 +592,53 @@ class Engine:
         self._sync_stream()
         self._e.row_group_keys(batch.view(), int(field), out.data_ptr())
         return out
+
+    def shuffle_batch(self, batch: Batch, seed: int, field_major: bool | None = None) -> Batch:
+        """``batch`` with its rows permuted on the device, as new tensors: row
+        i of the result is row ``shuffle_permutation(rows, seed)[i]`` of
+        ``batch`` (keys, field ids, label; a row's entries keep their order).
+        The source is CSR or fixed-width row-major -- a field-major one is
+        refused: its rows are not contiguous -- and is left unchanged.  A
+        fixed-width result is field-major unless ``field_major`` is False (the
+        fused shuffle + transpose: the one pass the step's layout costs
+        anyway); a CSR batch stays CSR.  Compact u32 keys (int32) come out as
+        u64.  Above 64 fields torch gathers, as in ``to_field_major``."""
+        batch.check(self.device, compact_ok=True)
+        fixed = batch.row_ptr is None
+        if batch.field_major:
+            raise ValueError("shuffle_batch: a field-major source (row-major or CSR only)")
+        fm = fixed if field_major is None else bool(field_major)
+        if fm and not fixed:
+            raise ValueError("shuffle_batch: only fixed-width batches have a field-major form")
+        if batch.rows > self.cfg.max_rows or batch.nnz > self.cfg.max_nnz:
+            raise ValueError("shuffle_batch: the batch exceeds max_rows / max_nnz")
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        rows, F, dev = batch.rows, batch.nnz_per_row, self.device
+        if not fixed and batch.keys.dtype == torch.int32:
+            batch = Batch(keys=widen_keys(batch.keys), labels=batch.labels, row_ptr=batch.row_ptr,
+                          fgid=batch.fgid, slice_rows=batch.slice_rows)
+        if fixed and F > 64:
+            perm = torch.from_numpy(shuffle_permutation(rows, seed)).to(dev)
+
+            def g(x):
+                if x is None:
+                    return None
+                y = x.view(rows, F)[perm]
+                return (y.t() if fm else y).contiguous().view(-1)
+            return Batch(keys=g(widen_keys(batch.keys)), labels=batch.labels[perm],
+                         fgid=g(batch.fgid), nnz_per_row=F, slice_rows=batch.slice_rows,
+                         field_major=fm)
+        keys = torch.empty(batch.nnz, dtype=torch.int64, device=dev)
+        labels = torch.empty(rows, dtype=torch.float32, device=dev)
+        fgid = torch.empty_like(batch.fgid) if batch.fgid is not None else None
+        row_ptr = None if fixed else torch.empty(rows + 1, dtype=torch.int32, device=dev)
+        self._sync_stream()
+        self._e.shuffle_rows(batch.view(), seed, keys.data_ptr(),
+                             fgid.data_ptr() if fgid is not None else 0, labels.data_ptr(),
+                             row_ptr.data_ptr() if row_ptr is not None else 0, fm,
+                             batch.keys.element_size())
+        return Batch(keys=keys, labels=labels, row_ptr=row_ptr, fgid=fgid,
+                     nnz_per_row=batch.nnz_per_row, slice_rows=batch.slice_rows, field_major=fm)
 
     def export_table(self):
         self._sync_stream()

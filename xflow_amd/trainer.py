@@ -41,10 +41,10 @@ from xflow_amd.config import TrainConfig, model_kind
 from xflow_amd.data import binfmt
 from xflow_amd.data.textstream import TextStream
 from xflow_amd.data.upload import BlockStream
-from xflow_amd.engine import Batch, Engine, widen_keys
+from xflow_amd.engine import Batch, Engine, shuffle_permutation, widen_keys
 from xflow_amd.metrics import MetricsLogger, reference_auc
 from xflow_amd.parallel import dist as xdist
-from xflow_amd.testing.hashing import owner_of
+from xflow_amd.testing.hashing import fmix64_int, owner_of
 from xflow_amd.utils.faults import injector_from_env, watchdog_from_env
 from xflow_amd.utils.trace import PhaseTimer, StreamTimeline
 
@@ -68,8 +68,16 @@ def _uniform_width(row_ptr) -> int:
 class Trainer:
     def __init__(self, cfg: TrainConfig, device: Optional[torch.device] = None):
         self.cfg = cfg
+        if cfg.shuffle and cfg.serial_slices:
+            raise ValueError("--shuffle trains with concurrent slices (not --serial-slices)")
         self.world = xdist.start(device)
         self.rank = xdist.my_rank()
+        if cfg.shuffle:
+            xfb = binfmt.shard_file(shard_path(cfg.train_prefix, self.rank))
+            if xfb and binfmt.version_of(xfb) == binfmt.VERSION_PACKED:
+                raise ValueError("--shuffle: packed (version 3) .xfb shards are expanded straight "
+                                 "to field-major on the device and cannot be shuffled; convert "
+                                 "the shard without --packed")
         self.device = device or xdist.device_for_rank()
         self.threads = cfg.resolved_threads()
         self.concurrent = not cfg.serial_slices
@@ -129,20 +137,24 @@ class Trainer:
 
     # ------------------------------------------------------------------ data
     def _to_batch(self, blk: Optional[dict], used: int, slice_rows: int,
-                  with_fgid: Optional[bool] = None) -> Batch:
-        """with_fgid: carry the field ids (None: only when the model reads them)."""
+                  with_fgid: Optional[bool] = None, seed: Optional[int] = None,
+                  raw: bool = False) -> Batch:
+        """with_fgid: carry the field ids (None: only when the model reads them).
+        seed / raw: the block's layout step (_laid_out)."""
         dev = self.device
         if with_fgid is None:
             with_fgid = self._with_fgid
         if blk is not None and used > 0 and "packed" in blk:
             # a packed (v3 .xfb) block: its bytes, expanded on the device
+            if seed is not None or raw:
+                raise ValueError("--shuffle: packed .xfb blocks cannot be shuffled")
             p = blk["packed"]
             if not isinstance(p, torch.Tensor):
                 p = torch.from_numpy(np.array(p)).to(dev)
             return self.engine.unpack_packed(p, int(blk["rows"]), blk["shard"], slice_rows,
                                              with_fgid, used)
         if blk is not None and used > 0 and isinstance(blk["keys"], torch.Tensor):
-            return self._device_batch(blk, used, slice_rows, with_fgid)
+            return self._device_batch(blk, used, slice_rows, with_fgid, seed, raw)
         if blk is None or used <= 0:
             return Batch(keys=torch.empty(0, dtype=torch.int64, device=dev),
                          labels=torch.empty(0, dtype=torch.float32, device=dev),
@@ -167,12 +179,34 @@ class Trainer:
         keys = up(k.view(np.int32) if k.dtype == np.uint32 else k.view(np.int64))
         fgid = up(blk["fgid"][:nnz]) if with_fgid else None
         if F:
-            return Batch(keys=keys, labels=up(blk["labels"][:used]), fgid=fgid, nnz_per_row=F,
-                         slice_rows=slice_rows).to_field_major(self.engine)
-        return Batch(keys=widen_keys(keys), labels=up(blk["labels"][:used]), row_ptr=up(rp),
-                     fgid=fgid, slice_rows=slice_rows)
+            return self._laid_out(Batch(keys=keys, labels=up(blk["labels"][:used]), fgid=fgid,
+                                        nnz_per_row=F, slice_rows=slice_rows), seed, raw)
+        return self._laid_out(Batch(keys=widen_keys(keys), labels=up(blk["labels"][:used]),
+                                    row_ptr=up(rp), fgid=fgid, slice_rows=slice_rows), seed, raw)
 
-    def _device_batch(self, blk: dict, used: int, slice_rows: int, with_fgid: bool) -> Batch:
+    def _laid_out(self, b: Batch, seed: Optional[int], raw: bool = False) -> Batch:
+        """The batch the step trains from a block's device arrays (CSR, or
+        fixed-width row-major with possibly compact keys): fixed-width blocks
+        field-major; with a seed, the rows shuffled in that same pass
+        (Engine.shuffle_batch).  raw: the arrays as they are (what --resident
+        --shuffle keeps, to lay out again every epoch)."""
+        if raw:
+            return b
+        if seed is not None:
+            return self.engine.shuffle_batch(b, seed)
+        return b.to_field_major(self.engine) if b.row_ptr is None else b
+
+    def _block_seed(self, block: int) -> Optional[int]:
+        """--shuffle: the seed of this rank's block `block` in the current
+        epoch -- a pure function of (shuffle_seed, epoch, block, rank), so a
+        resumed run (self.epoch restored) shuffles like an uninterrupted one."""
+        if not self.cfg.shuffle:
+            return None
+        return fmix64_int(fmix64_int(fmix64_int(self.cfg.shuffle_seed + self.epoch) + block)
+                          + self.rank)
+
+    def _device_batch(self, blk: dict, used: int, slice_rows: int, with_fgid: bool,
+                      seed: Optional[int] = None, raw: bool = False) -> Batch:
         """Batch over a block already on the device (data.upload.BlockStream,
         or data.textstream.TextStream: its parse counted the used rows' nnz)."""
         if "row_ptr_host" in blk:
@@ -184,10 +218,12 @@ class Trainer:
         fgid = blk["fgid"][:nnz] if with_fgid else None
         F = blk["nnz_per_row"] if self.cfg.fixed_width else 0
         if F:
-            return Batch(keys=blk["keys"][:nnz], labels=blk["labels"][:used], fgid=fgid,
-                         nnz_per_row=F, slice_rows=slice_rows).to_field_major(self.engine)
-        return Batch(keys=widen_keys(blk["keys"][:nnz]), labels=blk["labels"][:used],
-                     row_ptr=blk["row_ptr"][:used + 1], fgid=fgid, slice_rows=slice_rows)
+            return self._laid_out(Batch(keys=blk["keys"][:nnz], labels=blk["labels"][:used],
+                                        fgid=fgid, nnz_per_row=F, slice_rows=slice_rows),
+                                  seed, raw)
+        return self._laid_out(Batch(keys=widen_keys(blk["keys"][:nnz]), labels=blk["labels"][:used],
+                                    row_ptr=blk["row_ptr"][:used + 1], fgid=fgid,
+                                    slice_rows=slice_rows), seed, raw)
 
     def _split(self, rows: int):
         """(used rows, slice rows) under the reference's slicing rule."""
@@ -204,6 +240,10 @@ class Trainer:
     def _epoch_batches(self, nxt, record):
         """This rank's batches of one epoch: blocks from ``nxt()`` (None at
         the end), each as one concurrent step or one step per slice."""
+        if self.cfg.shuffle and (record is not None or self._resident is not None):
+            yield from self._resident_shuffled(nxt, record)
+            return
+        block = 0
         while True:
             blk = nxt()
             if blk is None:
@@ -211,19 +251,41 @@ class Trainer:
             if self._resident is not None:
                 batches = blk
             else:
-                batches = list(self._slices_of(blk))
+                batches = list(self._slices_of(blk, self._block_seed(block)))
                 if record is not None:
                     record.append(batches)
+            block += 1
             yield from batches
 
-    def _slices_of(self, blk: Optional[dict]):
-        """Batches of one block: one concurrent step, or one step per slice."""
+    def _resident_shuffled(self, nxt, record):
+        """--resident --shuffle: what stays in HBM is every block's batch
+        BEFORE the shuffle (row-major or CSR); every epoch, the first
+        included, lays each one out again with the epoch's seed -- the fused
+        shuffle + transpose, no host in the loop -- and takes the blocks in
+        the epoch's own order.  Both are functions of the epoch alone, so the
+        first epoch reads the whole shard before it trains."""
+        if record is not None:
+            while True:
+                blk = nxt()
+                if blk is None:
+                    break
+                record.append(list(self._slices_of(blk, raw=True)))
+        blocks = record if record is not None else self._resident
+        order = shuffle_permutation(len(blocks), fmix64_int(
+            fmix64_int(self.cfg.shuffle_seed + self.epoch) + self.rank))
+        for j in order:
+            for raw in blocks[int(j)]:
+                yield raw if raw.rows == 0 else self._laid_out(raw, self._block_seed(int(j)))
+
+    def _slices_of(self, blk: Optional[dict], seed: Optional[int] = None, raw: bool = False):
+        """Batches of one block: one concurrent step, or one step per slice.
+        seed / raw: the block's layout step (_laid_out; concurrent steps)."""
         rows = 0 if blk is None else (int(blk["rows"]) if "packed" in blk else len(blk["labels"]))
         if blk is not None and "packed" in blk and not self.concurrent:
             raise ValueError("packed .xfb shards train with concurrent slices (not --serial-slices)")
         used, sr = self._split(rows)
         if self.concurrent or blk is None or used <= 0:
-            yield self._to_batch(blk, used, sr)
+            yield self._to_batch(blk, used, sr, seed=seed, raw=raw)
             return
         rp = np.asarray(blk.get("row_ptr_host", blk["row_ptr"]))
         for s0 in range(0, used, sr):
@@ -369,6 +431,8 @@ class Trainer:
                        table_capacity=self.table.table_capacity,
                        table_growths=self.table.table_growths,
                        monitor_waits=self.table.monitor_waits)
+            rec["shuffle"] = bool(cfg.shuffle)
+            rec["shuffle_seed"] = int(cfg.shuffle_seed)
             if cfg.engine.admit_min_count > 1:
                 rec["admit_min_count"] = cfg.engine.admit_min_count
             if pruned is not None:
