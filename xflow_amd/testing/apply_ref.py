@@ -1,0 +1,268 @@
+"""A float32 model of the owner apply (csrc/hip/kernels_table.hip, the CPU
+backend's table_apply), for tests that compare table contents bit for bit.
+
+With the gradients given, the apply is a sequential float32 recurrence per
+(key, parameter).  ``ApplyModel`` runs it in numpy, one IEEE float32 operation
+per operation of csrc/include/xflow/common.h and types.h (numpy neither
+contracts nor widens float32 array arithmetic, its sqrt is correctly rounded):
+
+  ia = f32(1) / alpha                                      ftrl_inv_alpha
+  w  = 0                         if |z| <= lambda1         ftrl_weight_sn
+       (z -+ lambda1) / (-1 * ((beta + sqrt(n)) * ia + lambda2))
+  n' = n + g * g                                           ftrl_push_sn
+  z' = z + (g - ((sqrt(n') - sqrt(n)) * ia) * w)
+  SGD: w' = w - lr * g                                     slot_push
+
+The kernels carry sn = sqrtf(n) through a chain; the carried value is always
+the square root of the current n, so the model recomputes it.  A latent
+parameter (p >= p_w, layouts with a pushed flag) of a key that was never
+pushed reads its lazy-init weight until the key's first push, which sets the
+flag.  The lazy-init value goes through logf / cosf, which need not agree bit
+for bit between numpy and the device: it is an input of the apply, so the
+model takes it from the engine (``lazy_weights``: a lookup-only pull before
+anything is pushed) and the tests hold it to hashing.normal_init within 4 ulp.
+
+A table entry is what export_table returns per key: ``state_words`` uint32 =
+the P parameters' states ((n, z) pairs with FTRL, w with SGD), the pushed flag
+word (latent models), zero padding up to the slot stride.
+
+CSR entry formats of Engine.s_apply_csr (read from k_red_csr, k_red_csr_vec,
+csr_row_words and Engine::csr_entry_bytes; the apply kernels never read the
+slice word, a key's entries are simply consumed in order):
+
+  LR-FTRL          8 bytes: word 0 the slice, word 1 (the u64's high half) the gradient
+  reference FM    12 bytes: (slice, B, C); g_w = f32(v_dim) * B, g_v = C - w_pre * B
+  full rows       csr_row_words(P) = (1 + P + 3) & ~3 words: (slice, g_0 .. g_{P-1}, pad)
+                  (standard FM, MVM)
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from xflow_amd.config import OptimConfig
+
+F32 = np.float32
+NO_SLOT = 0xFFFFFFFF
+CSR_SHORT_CHAIN = 16   # kCsrShortChain, csrc/hip/kernels_table.hip
+
+ALL_KERNELS = frozenset({
+    "k_apply_lr16<false>", "k_apply_lr16<true>", "k_apply_lr16_multi",
+    "k_apply_lr16_csr<false>", "k_apply_lr16_csr<true>",
+    "k_apply_group<false>", "k_apply_group<true>",
+    "k_apply_group_csr<false,false>", "k_apply_group_csr<true,false>",
+    "k_apply_group_csr<false,true>", "k_apply_group_csr<true,true>",
+    "k_apply_generic"})
+
+
+def csr_row_words(P: int) -> int:
+    return (1 + P + 3) & ~3
+
+
+class Layout:
+    """TableLayout::make (csrc/include/xflow/types.h) for a model / optimiser."""
+
+    def __init__(self, kind: str, opt: str, v_dim: int = 4, fm_math: str = "reference"):
+        self.kind, self.opt, self.v_dim, self.fm_math = kind, opt, v_dim, fm_math
+        self.P = 1 if kind == "lr" else (1 + v_dim if kind == "fm" else v_dim)
+        self.p_w = 0 if kind == "mvm" else 1
+        self.ftrl = opt == "ftrl"
+        self.sp = 2 if self.ftrl else 1
+        self.has_flag = self.P > self.p_w
+        self.flag_col = self.sp * self.P
+        self.stride = (2 + self.sp * self.P + int(self.has_flag) + 3) & ~3
+        self.W = self.stride - 2
+        # ModelSpec::pstride at the kernels' latent width (device_latent_width)
+        d = v_dim
+        kd = d if d <= 2 else (4 if d <= 4 else (8 if d <= 8 else (10 if d <= 10 else (16 if d <= 16 else 32))))
+        p = 1 if kind == "lr" else (1 + kd if kind == "fm" else kd)
+        self.pstride = 1 if p == 1 else (p + 3) & ~3
+        self.compact_ok = kind == "fm" and fm_math == "reference"   # GPU: (B, C) rows
+        self.full_rows = (kind == "fm" and fm_math == "standard") or (kind == "mvm" and kd >= 2)
+
+
+def apply_kernels(L: Layout, *, gpu: bool, S: int, masks: bool, csr: bool = False,
+                  grouped: bool = False, stash: bool = False, sum_slices: bool = False,
+                  pstride: int | None = None) -> frozenset:
+    """The kernels one owner apply launches: launch_table_apply's dispatch
+    (csrc/hip/kernels_table.hip, from ``const bool lr16_slot`` to the final
+    ``k_apply_generic`` branch) as a function of what the callers set.
+    grouped: ApplyArgs::grp (s_pull grouped >= 2 active sources and s_apply got
+    the same offsets); stash: ApplyArgs::nz_stash (only the LR-FTRL 16-byte
+    layout keeps one for s_pull, Engine::ensure_server_capacity); pstride:
+    ApplyArgs::pstride where the caller overrides it (push_host: P).  The
+    s_apply / s_apply_csr / push_host routes pass no grad_map, slice_rows,
+    masks_rw or zero_after.  csr_long is live when S > 16 (Engine::s_apply_csr)."""
+    if not gpu:
+        return frozenset({"cpu"})
+    ps = L.pstride if pstride is None else pstride
+    lr16_slot = L.stride == 4 and L.P == 1 and L.ftrl and not L.has_flag and ps == 1
+    lr16 = lr16_slot and S == 1 and not masks
+    lr16_slices = lr16_slot and S > 1 and masks and not sum_slices and not grouped
+    group = f"k_apply_group<{'true' if S > 1 else 'false'}>"
+    if csr:
+        long = S > CSR_SHORT_CHAIN
+        if lr16_slot:
+            ks = ["k_apply_lr16_csr<false>"] + (["k_apply_lr16_csr<true>"] if long else [])
+        elif L.compact_ok and L.P <= 64:
+            ks = ["k_apply_group_csr<false,false>"] + (["k_apply_group_csr<true,false>"] if long else [])
+        elif L.full_rows and L.P <= 64:
+            ks = ["k_apply_group_csr<false,true>"] + (["k_apply_group_csr<true,true>"] if long else [])
+        else:
+            raise ValueError("no CSR apply for this layout")
+        return frozenset(ks)
+    if grouped:
+        return frozenset({"k_apply_lr16_multi" if lr16 else group})
+    if lr16:
+        return frozenset({"k_apply_lr16<false>"})
+    if lr16_slices:
+        return frozenset({"k_apply_lr16<true>"})
+    if (ps >= 2 or (L.P == 1 and stash)) and L.P <= 64:
+        return frozenset({group})
+    return frozenset({"k_apply_generic"})
+
+
+def lazy_weights(eng, keys: np.ndarray) -> np.ndarray:
+    """[len(keys), P] float32: what the engine reads for a key that was never
+    pushed -- call it while none of ``keys`` is in the table (absent_weight:
+    the lazy init for latents, 0 for w; the same function a resident,
+    never-pushed key reads through state_weight)."""
+    return np.asarray(eng.pull(keys), dtype=F32).reshape(len(keys), -1).copy()
+
+
+class ApplyModel:
+    """The table over a fixed universe of keys (sorted, unique)."""
+
+    def __init__(self, L: Layout, optim: OptimConfig, keys: np.ndarray, lazy: np.ndarray):
+        self.L, self.o = L, optim
+        self.keys = np.asarray(keys, dtype=np.uint64)
+        assert (self.keys[1:] > self.keys[:-1]).all(), "sorted, unique keys"
+        K, P = len(self.keys), L.P
+        self.lazy = np.asarray(lazy, dtype=F32).reshape(K, P)
+        self.s0 = np.zeros((K, P), F32)      # FTRL n; SGD w
+        self.s1 = np.zeros((K, P), F32)      # FTRL z
+        self.flag = np.zeros(K, np.uint32)
+        self.pad = np.zeros((K, L.W), np.uint32)   # words the apply must never write
+        self.present = np.zeros(K, bool)
+        self.latent = np.arange(P) >= L.p_w if L.has_flag else np.zeros(P, bool)
+        self.log = []                        # (idx, g [m, Lmax, P], cnt) per launch, for explain()
+        self.ia = F32(1.0) / F32(optim.alpha)
+
+    # ---- bookkeeping -------------------------------------------------------
+    def index(self, keys) -> np.ndarray:
+        k = np.asarray(keys, dtype=np.uint64)
+        i = np.searchsorted(self.keys, k)
+        assert (self.keys[i] == k).all(), "key outside the model's universe"
+        return i
+
+    def plant(self, idx, words) -> None:
+        """import_table of rows ``words`` [m, W] for keys idx."""
+        L = self.L
+        w = np.asarray(words, dtype=np.uint32).reshape(len(idx), L.W)
+        st = w[:, :L.sp * L.P].view(F32).reshape(len(idx), L.P, L.sp)
+        self.s0[idx] = st[:, :, 0]
+        if L.ftrl:
+            self.s1[idx] = st[:, :, 1]
+        self.flag[idx] = w[:, L.flag_col] if L.has_flag else 1
+        self.pad[idx] = w
+        self.present[idx] = True
+
+    def insert(self, idx) -> None:
+        """An inserting pull: absent keys get a zeroed slot."""
+        self.present[idx] = True
+
+    def words(self, idx=None) -> np.ndarray:
+        L = self.L
+        idx = np.arange(len(self.keys)) if idx is None else idx
+        w = self.pad[idx].copy()
+        st = np.zeros((len(idx), L.P, L.sp), F32)
+        st[:, :, 0] = self.s0[idx]
+        if L.ftrl:
+            st[:, :, 1] = self.s1[idx]
+        w[:, :L.sp * L.P] = st.reshape(len(idx), -1).view(np.uint32)
+        if L.has_flag:
+            w[:, L.flag_col] = self.flag[idx]
+        return w
+
+    # ---- the recipe --------------------------------------------------------
+    def _ftrl_weight(self, z, n):
+        o = self.o
+        l1 = F32(o.lambda1)
+        with np.errstate(all="ignore"):
+            tmpr = np.where(z > 0, z - l1, np.where(z < 0, z + l1, F32(0.0))).astype(F32)
+            tmpl = F32(-1.0) * ((F32(o.beta) + np.sqrt(n)) * self.ia + F32(o.lambda2))
+            w = tmpr / tmpl
+        return np.where(np.abs(z) <= l1, F32(0.0), w).astype(F32)
+
+    def weights(self, idx=None) -> np.ndarray:
+        """Current weights [m, P]: what a pull reads (state_weight / absent_weight)."""
+        idx = np.arange(len(self.keys)) if idx is None else idx
+        w = self._ftrl_weight(self.s1[idx], self.s0[idx]) if self.L.ftrl else self.s0[idx].copy()
+        unpushed = (self.flag[idx] == 0)[:, None] & self.latent[None, :]
+        w = np.where(unpushed, self.lazy[idx], w)
+        absent = np.where(self.latent[None, :], self.lazy[idx], F32(0.0))
+        return np.where(self.present[idx][:, None], w, absent).astype(F32)
+
+    def launch(self, idx, g=None, cnt=None, bc=None, w_pre=None) -> None:
+        """One apply launch over entries idx (unique): entry i takes its first
+        cnt[i] pushes of g[i] ([m, Lmax, P]) in order.  bc [m, Lmax, 2] with
+        w_pre [m, P]: compact reference-FM rows, expanded per push."""
+        idx = np.asarray(idx)
+        assert len(np.unique(idx)) == len(idx), "an apply launch holds a key once"
+        cnt = np.asarray(cnt, dtype=np.int64)
+        if bc is not None:
+            B, C = bc[:, :, 0:1].astype(F32), bc[:, :, 1:2].astype(F32)
+            with np.errstate(all="ignore"):
+                g = (C - w_pre[:, None, :].astype(F32) * B).astype(F32)
+                g[:, :, 0] = F32(self.L.v_dim) * B[:, :, 0]
+        g = np.asarray(g, dtype=F32)
+        self.log.append((idx.copy(), g.copy(), cnt.copy()))
+        o, L = self.o, self.L
+        live = self.present[idx]
+        with np.errstate(all="ignore"):
+            for j in range(int(cnt.max()) if len(cnt) else 0):
+                act = live & (j < cnt)
+                if not act.any():
+                    continue
+                a = idx[act]
+                w = self.weights(a)
+                gj = g[act, j, :]
+                if L.ftrl:
+                    n, z = self.s0[a], self.s1[a]
+                    nn = n + gj * gj
+                    self.s1[a] = z + (gj - ((np.sqrt(nn) - np.sqrt(n)) * self.ia) * w)
+                    self.s0[a] = nn
+                else:
+                    self.s0[a] = w - F32(o.lr) * gj
+                if L.has_flag:
+                    self.flag[a] = 1
+
+    # ---- reading a failure -----------------------------------------------
+    def explain(self, start: "ApplyModel", key, p: int, dev_words: np.ndarray) -> str:
+        """Replays key's pushes from ``start`` (a copy taken before the launches)
+        and says where the device's final state of parameter p sits."""
+        i = int(self.index([key])[0])
+        m = start.copy()
+        m.log = []
+        L = self.L
+        dev = dev_words[L.sp * p:L.sp * (p + 1)]
+        states = [m.words(np.array([i]))[0][L.sp * p:L.sp * (p + 1)].copy()]
+        for idx, g, cnt in self.log[len(start.log):]:
+            hit = np.nonzero(idx == i)[0]
+            if not len(hit):
+                continue
+            h = int(hit[0])
+            for j in range(int(cnt[h])):
+                m.launch(np.array([i]), g[h:h + 1, j:j + 1, :], np.array([1]))
+                states.append(m.words(np.array([i]))[0][L.sp * p:L.sp * (p + 1)].copy())
+        at = [j for j, s in enumerate(states) if np.array_equal(s, dev)]
+        msg = f"key {int(key):#x} param {p}: {len(states) - 1} pushes, model {states[-1]} device {dev}"
+        if at:
+            return msg + f"; the device holds the model's state after {at[0]} pushes (first divergence at push {at[0]})"
+        return msg + "; the device state matches no prefix of the chain"
+
+    def copy(self) -> "ApplyModel":
+        m = ApplyModel(self.L, self.o, self.keys, self.lazy)
+        for a in ("s0", "s1", "flag", "pad", "present"):
+            setattr(m, a, getattr(self, a).copy())
+        m.log = list(self.log)
+        return m
