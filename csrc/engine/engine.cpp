@@ -543,6 +543,7 @@ StepInputs Engine::step_inputs() const {
   in.slice_cap = slice_cap_;
   in.kdim = cfg_.model.kernel_dim();
   in.lead_handoff = cfg_.lead_handoff;
+  in.red_rank = cfg_.red_rank;
   return in;
 }
 
@@ -644,6 +645,11 @@ StepPlan plan_step(const StepInputs& in, int S) {
   p.lead = in.lead_handoff && in.gpu && in.kind == kLR && S == 1 && in.red_pairs && !p.upos &&
            in.field_major && in.rows >= kLeadTile && std::fmod(in.rows, (double)kLeadTile) == 0.0 &&
            in.fields >= 1.0 && in.fields <= kLeadMaxFields && in.scratch_cap < 2147483648.0;
+  // Ranked reduction outputs: the one-slice steps whose bucket reduction
+  // (k_red_sum) writes unique-order outputs from slot positions -- LR with or
+  // without the handoff, reference FM's (B, C).  The dedup then writes no
+  // slot -> unique map.  Does not change the gradient layout.
+  p.red_rank = in.red_rank && in.gpu && S == 1 && in.red_pairs && !p.upos && (p.lr16 || p.fmu);
   return p;
 }
 
@@ -877,7 +883,7 @@ void Engine::train_step(const BatchView& b) {
   if (fm_keep_w) fm_w_.ensure(*be_, un * ps);
   if (uq) lr_mask_.ensure(*be_, un);
 
-  PullArgs pa = begin_fused_step(b, upos || uo.buf, upos, P.lead);
+  PullArgs pa = begin_fused_step(b, upos || (uo.buf && !P.red_rank), upos, P.lead);
   if (fm_keep_w) pa.out_w = fm_w_;
   pa.out_nz = nz;
   if (uo.buf && uo.pull_zeroes) {
@@ -917,7 +923,12 @@ void Engine::train_step(const BatchView& b) {
     if (uo.buf) {
       fa.red_out = uo.buf;
       // (unique-index positions: the outputs' rows are the dests' own)
-      fa.red_inv = upos ? nullptr : ws_->inv.get();
+      fa.red_inv = upos || P.red_rank ? nullptr : ws_->inv.get();
+      if (P.red_rank) {  // (the stamps and chunk offsets the dedup above left)
+        fa.red_rank_offs = block_counts_;
+        fa.red_rank_stamps = scratch_.stamps;
+        fa.red_rank_epoch = scratch_.epoch;
+      }
       if (uo.normalised) fa.red_rows = srk;
     }
     be_->forward_backward(fa);
@@ -1630,6 +1641,13 @@ int64_t Engine::scratch_capacity() {
   unsigned long long c = 0;
   be_->copy_d2h(&c, scratch_.ctl, sizeof(c));
   return (int64_t)c;  // ctl[0]: the capacity the next batch is deduplicated with
+}
+
+int64_t Engine::batch_capacity() {
+  if (!scratch_.ctl) return (int64_t)scratch_.cap;
+  unsigned long long c = 0;
+  be_->copy_d2h(&c, ws_->bcap, sizeof(c));
+  return (int64_t)c;  // (FwdArgs::red_bcap: the allocation when the batch spilled)
 }
 
 ScratchStats Engine::scratch_stats() {

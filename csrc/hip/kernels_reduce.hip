@@ -47,12 +47,53 @@ __global__ void __launch_bounds__(kBlock) k_red_scan(u32* __restrict__ hist, int
 template <int NV>
 __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
                                              const void* __restrict__ sorted, const RedFinal& f,
-                                             long long* acc, u32* pbits, u32* cbits) {
+                                             long long* acc, u32* pbits, u32* cbits, u32* rpre,
+                                             u32* rwt) {
   using T = typename RedRec<NV>::T;
   constexpr int kShift = red_shift(NV);
   constexpr u32 kR = 1u << kShift;
   constexpr int kFx = FxBits<NV>::kFx;
   if (beg == end) return;
+  // Unique-order outputs without the slot -> unique map (RedFinal::rk_offs;
+  // one slice, so dests are slots and pbits is free): lane w < kR / 32 turns
+  // the 32 stamps of slots [lo + 32 w, + 32) into bitmap word w (bit: the slot
+  // is in the batch) and takes the word's rank -- its chunk's compaction
+  // offset plus the set bits of the chunk's words before it.  A chunk is two
+  // waves' words: a wave scan, plus the even wave's total for the odd one
+  // (added after the first barrier below).  Slots at or past the capacity the
+  // compaction covered (the trash slot) have no bit.
+  constexpr u32 kRw = kR / 32;
+  constexpr u32 kChunkW = (1u << kCompactChunkLog2) / 32;
+  static_assert(kRw <= (u32)kRedBlock && kChunkW == 2 * kWave && kRw % kChunkW == 0,
+                "a unit is whole chunks, a chunk two waves of bitmap words");
+  const bool rank = f.out && f.rk_offs;  // (block-uniform)
+  u32 rk_pre = 0;
+  if (rank && threadIdx.x < kRw) {
+    const u32 w = threadIdx.x;
+    const u64 base = lo + 32ull * w;
+    u32 m = 0;
+    const u64 cap = (u64)*f.rk_cap;  // (a power of two >= 16: whole 16-slot groups)
+    if (base < cap) {
+      const uint4* sp = reinterpret_cast<const uint4*>(f.rk_stamps + base);
+      const uint4 q0 = sp[0], q1 = base + 16 < cap ? sp[1] : make_uint4(0u, 0u, 0u, 0u);
+      rk_pre = f.rk_offs[base >> kCompactChunkLog2];
+      const u32 sw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+      const u32 e = f.rk_epoch & 0xFFu;
+#pragma unroll
+      for (int j = 0; j < 32; ++j) m |= (u32)(((sw[j >> 2] >> (8 * (j & 3))) & 0xFFu) == e) << j;
+    }
+    pbits[w] = m;
+    const u32 c = (u32)__popc(m);
+    u32 incl = c;
+    const int lane = (int)(w % kWave);
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const u32 t = __shfl_up(incl, o);
+      if (lane >= o) incl += t;
+    }
+    rk_pre += incl - c;
+    if (lane == kWave - 1) rwt[w / kWave] = incl;
+  }
   // sparse units hold their records in registers across the three phases
   constexpr int kSp = 2 * kRedUnroll;
   const bool dense = end - beg > (u32)(kSp * kRedBlock);  // (block-uniform)
@@ -122,7 +163,23 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
     for (int q = 0; q < kSp; ++q)
       if (lr[q] < kR) add(pr[q], lr[q]);
   }
+  // (the waves' totals were stored before the barrier above)
+  if (rank && threadIdx.x < kRw) {
+    const u32 wv = threadIdx.x / kWave;
+    rpre[threadIdx.x] = rk_pre + ((wv & 1u) ? rwt[wv - 1] : 0u);
+  }
   lds_barrier();
+  // unique index of the unit's slot lo + l from the bitmap and the word ranks;
+  // none (0xFFFFFFFF) for a slot the batch did not stamp
+  auto rank_of = [&](u32 l) -> u32 {
+    const u32 word = pbits[l >> 5], bit = 1u << (l & 31);
+    if (!(word & bit)) {
+      // (a sum on a slot of the compacted range that is not in the batch)
+      XF_DASSERT(lo + l >= (u64)*f.rk_cap);
+      return 0xFFFFFFFFu;
+    }
+    return rpre[l >> 5] + (u32)__popc(word & (bit - 1u));
+  };
   // slice bits of a slot: one plain store per slot inside [lo, lo + kR), an
   // atomic OR for a slot that straddles its edge (S not dividing kR)
   auto put_mask = [&](u64 slot, u32 bits) {
@@ -146,7 +203,7 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
         // normalised like the gather would (lr_worker.cc:116-118, in double);
         // S > 1: [unique][slice], per-slice rows
         const u64 slot = dest / S, sl = dest - slot * S;
-        const u32 o = uix(f.inv, slot);
+        const u32 o = rank ? rank_of(l) : uix(f.inv, slot);
         if (o != 0xFFFFFFFFu)  // (not the trash slot)
           f.out[(u64)o * S + sl] = (float)(fx_to_double<kFx>(a) / (double)f.rows[sl]);
       } else {
@@ -161,7 +218,7 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
       if (f.compact) {  // expanded by the apply (k_apply_group)
         if (f.out) {    // unique (send) order; S > 1: [unique][slice]
           const u64 slot = dest / S, sl = dest - slot * S;
-          const u32 o0 = uix(f.inv, slot);
+          const u32 o0 = rank ? rank_of(l) : uix(f.inv, slot);
           if (o0 == 0xFFFFFFFFu) return;
           const u64 o = (u64)o0 * S + sl;
           if (f.rows) {  // normalised before the expansion (the send buffer, the fused step)
@@ -236,6 +293,8 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum(const void* __restrict__ 
   __shared__ long long acc[kR * NV];
   __shared__ u32 pbits[kR / 32];  // (f.masks) dests some record reached
   __shared__ u32 cbits[kR / 32];  // (sparse) dests whose sum is being stored
+  __shared__ u32 rpre[kR / 32];   // (f.rk_offs) unique index of the first stamped slot of a bitmap word
+  __shared__ u32 rwt[kR / 32 / kWave];
   const int shift = geom.shift(kShift);
   const u32 act = (u32)geom.active(shift, nb);
   const u32 units = act << (shift - kShift);
@@ -252,7 +311,7 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum(const void* __restrict__ 
       nend = start[nid % act + 1];
     }
     const u64 lo = ((u64)b << shift) + ((u64)sub << kShift);
-    red_sum_unit<NV>(lo, beg, end, sorted, f, acc, pbits, cbits);
+    red_sum_unit<NV>(lo, beg, end, sorted, f, acc, pbits, cbits, rpre, rwt);
     lds_barrier();  // the next unit reinitialises what this one read
   }
 }
@@ -510,6 +569,16 @@ void launch_reduction(const FwdArgs& a, int groups, int rows_per_group, hipStrea
   RedFinal f{a.grad, a.wpull, a.S, a.model.pstride(), a.model.v_dim,
              a.red_out, a.red_inv, a.red_rows, NV == 2 && a.fm_compact,
              a.S > 1 ? a.red_masks : nullptr};
+  if (a.red_rank_offs && a.red_out) {
+    // (dests are slots, the slice bits' bitmap is free for the stamps)
+    if (a.S != 1 || a.red_nuq || !a.red_rank_stamps || !a.red_bcap)
+      throw std::runtime_error("red_rank: one slice, slot positions, the batch's stamps and capacity");
+    f.rk_offs = a.red_rank_offs;
+    f.rk_stamps = a.red_rank_stamps;
+    f.rk_cap = a.red_bcap;
+    f.rk_epoch = a.red_rank_epoch;
+    f.inv = nullptr;
+  }
   const u32 grid = std::min<u32>((u32)(a.red_nb * a.red_nsub), (u32)device_cus());
   hipLaunchKernelGGL(k_red_sum<NV>, dim3(grid), dim3(kRedBlock), 0, st,
                      static_cast<const void*>(a.red_sorted), start, f, red_geom(a), a.red_nb);

@@ -286,6 +286,7 @@ __global__ void __launch_bounds__(kBlock) k_dedup_insert(const u64* __restrict__
 // its offset.  Output order = slot order: deterministic.
 constexpr int kCompactItems = 16;
 constexpr int kCompactChunk = kBlock * kCompactItems;
+static_assert(kCompactChunk == 1 << kCompactChunkLog2, "k_red_sum ranks slots by these chunks");
 constexpr int kScanBlock = 1024;
 
 // 16 consecutive byte stamps as one dwordx4 load (cap is a power of two >=

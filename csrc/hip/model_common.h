@@ -534,6 +534,12 @@ struct RedFinal {
   const int32_t* rows;
   bool compact;        // NV == 2: store (B, C) only (FwdArgs::fm_compact)
   u32* masks;          // slice-presence bits (FwdArgs::red_masks; unique order with out), or null
+  // (out, S == 1) the unique index from the compaction's chunk offsets and
+  // the stamps instead of inv (FwdArgs::red_rank_*); rk_offs null: through inv
+  const u32* rk_offs = nullptr;
+  const unsigned char* rk_stamps = nullptr;
+  const unsigned long long* rk_cap = nullptr;  // slots the compaction covered (FwdArgs::red_bcap)
+  u32 rk_epoch = 0;
 };
 
 // Slice bits of one slot from the presence bitmap: its dests slot*S + s that

@@ -145,6 +145,8 @@ constexpr u32 kStampEpochs = 255;
 constexpr u64 kScratchHeadroom = 4;      // active cap >= 4 x max unique keys per batch (A/B: 8 and 2 slower)
 constexpr u64 kScratchMinCap = 1ull << 16;
 constexpr int kScratchCtlWords = 8;      // ScratchView::ctl
+// slots per compaction chunk (HIP: one workgroup, one entry of DedupOut::block_counts)
+constexpr int kCompactChunkLog2 = 12;
 
 struct DedupOut {
   u32* pos = nullptr;          // [nnz] scratch slot of each occurrence
@@ -287,6 +289,16 @@ struct FwdArgs {
   float* red_out = nullptr;
   const u32* red_inv = nullptr;
   const int32_t* red_rows = nullptr;
+  // The same unique index without the map (StepPlan::red_rank; S == 1, slot
+  // positions): the unique list is in slot order, so slot s sits at the
+  // compaction's exclusive offset of its 4096-slot chunk (red_rank_offs =
+  // DedupOut::block_counts after the dedup) plus the slots of that chunk below
+  // s stamped with the batch's epoch (red_rank_stamps, red_rank_epoch).  Slots
+  // at or past red_bcap[0], the capacity the compaction covered -- the trash
+  // slot among them -- have no index.  Set: red_inv is not read.
+  const u32* red_rank_offs = nullptr;
+  const unsigned char* red_rank_stamps = nullptr;
+  u32 red_rank_epoch = 0;
   // Reference-math FM on the reduction path: keep only (B, C) = (Σ loss,
   // Σ loss*vsum) in the first two floats of each gradient row; the apply
   // expands them with the key's pre-step weights (ApplyArgs::fm_compact).

@@ -88,6 +88,11 @@ struct EngineConfig {
   // false: every rebuild frees the whole table (the A/B switch -- the results
   // are bit-equal either way).
   bool scratch_carry = true;
+  // Unique-order reduction outputs ranked from the dedup stamps
+  // (StepPlan::red_rank) on the steps that covers; false keeps the
+  // compaction's slot -> unique map everywhere (the A/B switch -- the results
+  // are bit-equal either way).
+  bool red_rank = true;
 };
 
 // The dedup scratch's counters (Engine::scratch_stats).  The CPU backend has
@@ -122,6 +127,7 @@ struct StepInputs {
   bool lead_handoff = true;  // EngineConfig::lead_handoff
   bool field_major = false;  // fixed width, col_stride == rows
   double rows = 0.0, fields = 0.0;
+  bool red_rank = true;  // EngineConfig::red_rank
 };
 
 // Where a step's gradients land, one per step:
@@ -157,6 +163,10 @@ struct StepPlan {
   // the leader handoff: the dedup writes leader-encoded positions
   // (DedupOut::lead) and k_lr_lead consumes them
   bool lead = false;
+  // one-slice LR / reference FM on slot positions: k_red_sum ranks its
+  // unique-order outputs from the stamps and the compaction's chunk offsets
+  // (FwdArgs::red_rank_*), the compaction writes no slot -> unique map
+  bool red_rank = false;
 };
 
 StepPlan plan_step(const StepInputs& in, int S);
@@ -305,6 +315,9 @@ class Engine {
   int64_t n_unique();            // unique keys of the last prepared batch (syncs)
   int64_t table_size();          // occupied slots (syncs)
   int64_t scratch_capacity();    // active dedup scratch capacity (adaptive on the GPU; syncs)
+  // slots the last batch's compaction and reduction covered: the capacity it
+  // was deduplicated with, or the whole allocation when it spilled (syncs)
+  int64_t batch_capacity();
   ScratchStats scratch_stats();  // (syncs: tests and tools only)
   uint64_t table_capacity() const { return table_.cap; }
   size_t table_bytes() const { return table_bytes_; }

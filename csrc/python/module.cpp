@@ -105,6 +105,7 @@ py::dict plan_dict(const StepPlan& p) {
   d["grpst"] = p.grpst;
   d["uq"] = p.uq;
   d["lead"] = p.lead;
+  d["red_rank"] = p.red_rank;
   return d;
 }
 
@@ -134,6 +135,7 @@ StepInputs inputs_from(py::dict d) {
   in.kdim = m.kernel_dim();
   // the leader handoff: the switch and the batch's shape
   in.lead_handoff = flag("lead_handoff", true);
+  in.red_rank = flag("red_rank", true);
   in.field_major = flag("field_major", false);
   in.rows = d.contains("rows") ? d["rows"].cast<double>() : 0.0;
   in.fields = d.contains("fields") ? d["fields"].cast<double>() : 0.0;
@@ -406,8 +408,9 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int device, bool table_grow, double grow_load, int max_log2_cap,
                        int monitor_lag, int owner_group, double grow_start, bool csr,
                        int admit_min_count, int admit_log2, bool lead_handoff,
-                       bool scratch_carry) {
+                       bool scratch_carry, bool red_rank) {
              EngineConfig c;
+             c.red_rank = red_rank;
              c.lead_handoff = lead_handoff;
              c.scratch_carry = scratch_carry;
              c.admit_min_count = admit_min_count;
@@ -437,7 +440,8 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("table_grow") = true, py::arg("grow_load") = 0.8, py::arg("max_log2_cap") = 0,
            py::arg("monitor_lag") = 2, py::arg("owner_group") = 0, py::arg("grow_start") = 0.6,
            py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
-           py::arg("lead_handoff") = true, py::arg("scratch_carry") = true)
+           py::arg("lead_handoff") = true, py::arg("scratch_carry") = true,
+           py::arg("red_rank") = true)
       .def_property_readonly("admit_bytes", &Engine::admit_bytes)
       .def_property_readonly("admit_log2", &Engine::admit_log2)
       .def("admit_counts",
@@ -711,6 +715,7 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def("n_unique", &Engine::n_unique)
       .def("table_size", &Engine::table_size)
       .def("scratch_capacity", &Engine::scratch_capacity)
+      .def("batch_capacity", &Engine::batch_capacity)
       .def("scratch_stats",
            [](Engine& e) {
              const ScratchStats s = e.scratch_stats();

@@ -119,6 +119,11 @@ class EngineConfig:
     # rebuild at an unchanged capacity keeps the batch's own keys; False frees
     # the whole table at every rebuild (bit-equal results, the A/B switch)
     scratch_carry: bool = True
+    # one-slice LR / reference FM on the GPU (docs/DESIGN.md §3): the gradient
+    # reduction ranks its unique-order outputs from the dedup's stamps, and
+    # the compaction writes no slot -> unique map; False keeps the map
+    # (bit-equal results, the A/B switch)
+    red_rank: bool = True
 
 
 @dataclass

@@ -159,7 +159,8 @@ class Engine:
                            admit_min_count=self.cfg.admit_min_count,
                            admit_log2=self.cfg.admit_log2,
                            lead_handoff=self.cfg.lead_handoff,
-                           scratch_carry=self.cfg.scratch_carry)
+                           scratch_carry=self.cfg.scratch_carry,
+                           red_rank=self.cfg.red_rank)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -501,6 +502,13 @@ class Engine:
         """Active dedup scratch capacity (device-adaptive on the GPU)."""
         self._sync_stream()
         return int(self._e.scratch_capacity())
+
+    def batch_capacity(self) -> int:
+        """Scratch slots the last batch's compaction and gradient reduction
+        covered: the capacity it was deduplicated with, or the whole
+        allocation when the batch spilled past it.  Synchronises."""
+        self._sync_stream()
+        return int(self._e.batch_capacity())
 
     def scratch_stats(self) -> dict:
         """The dedup scratch's counters: ``capacity`` (active), ``occupancy``
