@@ -483,6 +483,38 @@ class CpuBackend final : public Backend {
     }
     return n;
   }
+  void delta_mark(u32* bits, int L, const u64* keys, const int64_t* n_dev, int64_t n_host,
+                  int64_t n_max) override {
+    int64_t n = n_dev ? *n_dev : n_host;
+    if (n_dev && n > n_max) n = n_max;
+    for (int64_t i = 0; i < n; ++i) {
+      const u64 b = delta_bit(sanitize_key(keys[i]), L);
+      bits[b >> 5] |= 1u << (u32)(b & 31u);
+    }
+  }
+  int64_t table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
+                              u32* words_out, int64_t max_rows) override {
+    const int W = t.L.stride - 2;
+    int64_t n = 0;
+    for (u64 s = 0; s < t.cap; ++s) {
+      const u32* sp = t.words + s * (u64)t.L.stride;
+      u64 key = *reinterpret_cast<const u64*>(sp);
+      if (key == kEmptyKey) continue;
+      const u64 b = delta_bit(key, L);
+      if (!((bits[b >> 5] >> (u32)(b & 31u)) & 1u)) continue;
+      if (n < max_rows) {
+        keys_out[n] = key;
+        std::memcpy(words_out + n * W, sp + 2, sizeof(u32) * W);
+      }
+      ++n;
+    }
+    return n;
+  }
+  int64_t delta_popcount(const u32* bits, int L) override {
+    int64_t n = 0;
+    for (u64 i = 0; i < (1ull << (L - 5)); ++i) n += __builtin_popcount(bits[i]);
+    return n;
+  }
   void table_import(const TableView& t, const u64* keys, const u32* words, int64_t n) override {
     const int W = t.L.stride - 2;
     for (int64_t i = 0; i < n; ++i) {

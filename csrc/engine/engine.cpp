@@ -49,6 +49,8 @@ const EngineConfig& Engine::validated(const EngineConfig& cfg) {
     throw std::invalid_argument("admit_min_count must be in [1, 255]");
   if (cfg.admit_log2 != 0 && (cfg.admit_log2 < kAdmitBlockLog2 || cfg.admit_log2 > kAdmitMaxLog2))
     throw std::invalid_argument("admit_log2 must be 0 (automatic) or in [6, 32]");
+  if (cfg.delta_log2 != 0 && (cfg.delta_log2 < kDeltaMinLog2 || cfg.delta_log2 > kDeltaMaxLog2))
+    throw std::invalid_argument("delta_log2 must be 0 (automatic) or in [10, 34]");
   if (next_pow2((uint64_t)((double)cfg.max_nnz * cfg.scratch_factor) + 1) > (1ull << 31))
     throw std::invalid_argument("max_nnz too large");
   return cfg;
@@ -99,6 +101,14 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
     if (admit_.log2 < kAdmitBlockLog2) admit_.log2 = kAdmitBlockLog2;
     admit_.min_count = cfg_.admit_min_count;
     admit_.counters = admit_counters_.alloc_zero(be, (size_t)1 << admit_.log2);
+  }
+  // delta checkpoints: the touched-key filter (EngineConfig::delta_track)
+  if (cfg_.delta_track) {
+    const int top = cfg_.table_grow ? max_log2_cap_ : log2_cap_;
+    delta_log2_ = cfg_.delta_log2 ? cfg_.delta_log2
+                                  : (top + 2 < kDeltaMaxLog2 ? top + 2 : kDeltaMaxLog2);
+    if (delta_log2_ < kDeltaMinLog2) delta_log2_ = kDeltaMinLog2;
+    delta_bits_.alloc_zero(be, (size_t)1 << (delta_log2_ - 5));
   }
   std::memset(snaps_.alloc(be, kSnaps), 0, sizeof(HostSnap) * kSnaps);
 
@@ -793,6 +803,7 @@ void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* 
   const void* ent = csr_full_rows() ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get();
   const int64_t n = src_offsets.empty() ? 0 : src_offsets.back();
   if (n > sb.n) throw std::invalid_argument("s_apply_csr: offsets beyond pull");
+  mark_stale_buffer(sb, recv_keys, n);
   if (recv_cnt) {  // received entries: offsets by a scan of the counts
     csr_roff_.reserve(*be_, (size_t)n + 1, (size_t)(n + n / 4 + 1024));
     be_->scan_u32(recv_cnt, csr_roff_, nullptr, n);
@@ -969,6 +980,8 @@ PullArgs Engine::begin_fused_step(const BatchView& b, bool want_inv, bool upos, 
   ws_->inv_valid = false;  // (the sharded step's send order is not this one)
   if (upos) be_->remap_pos(ws_->pos, b.nnz, ws_->inv, (u32)scratch_.cap);
   guard_inserts(b.nnz);  // (<= nnz new keys; may grow the table first)
+  // (delta checkpoints: every apply of the step pushes these keys only)
+  delta_mark(uniq_keys_, ws_->n_uniq, b.nnz);
   PullArgs pa = pull_args(uniq_keys_, ws_->n_uniq, b.nnz, true, uniq_slot_);
   pa.admit = admit_;
   pa.out_vals = wpull_;
@@ -1007,6 +1020,7 @@ void Engine::push_host(const std::vector<u64>& keys, const std::vector<float>& g
   ensure_host_staging(n);
   be_->copy_h2d(host_keys_dev_, keys.data(), sizeof(u64) * n);
   be_->copy_h2d(host_vals_dev_, grads.data(), sizeof(float) * n * P);
+  delta_mark(host_keys_dev_, nullptr, n);
   // (no admission filter: explicit pushes insert regardless; no values read)
   be_->table_pull(pull_args(host_keys_dev_, nullptr, n, true, host_slots_dev_));
   // Pushes of one call are applied one key at a time in order; duplicate keys
@@ -1026,6 +1040,7 @@ void Engine::prefill(int64_t n, uint64_t seed) {
   if (n < 0 || (uint64_t)n > table_.cap - table_.cap / 16)
     throw std::invalid_argument("prefill: at most 15/16 of the table's slots");
   stale_stashes();
+  if (n > 0) delta_needs_full_ = true;  // (inserts that bypass marking)
   be_->table_prefill(table_, n, seed);
   be_->synchronize();
   (void)table_size();  // (re-bases the capacity monitor)
@@ -1130,7 +1145,11 @@ void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool inser
   if (insert) {
     guard_inserts(n);
     group_entries(recv_keys, n, buf, src_offsets);
+    // (delta checkpoints: the buffer's applies push these keys; one that runs
+    // after a delta_clear marks them again, mark_stale_buffer)
+    delta_mark(recv_keys, nullptr, n);
   }
+  sb.delta_gen = insert ? delta_gen_ : ~0ull;
   PullArgs pa = pull_args(recv_keys, nullptr, n, insert, sb.slots);
   if (insert) pa.admit = admit_;
   pa.out_vals = out_vals;
@@ -1291,6 +1310,7 @@ void Engine::s_apply(const u64* recv_keys, const float* recv_grads, const u32* r
   // valid; source by source only the first launch takes it, apply_by_source)
   bool stash = sb.nz_fresh;
   stale_stashes();
+  mark_stale_buffer(sb, recv_keys, src_offsets.empty() ? 0 : src_offsets.back());
   ApplyArgs base = apply_args(recv_keys, sb.slots, nullptr, 0, S);
   base.grads = const_cast<float*>(recv_grads);
   base.masks = recv_masks;
@@ -1601,6 +1621,7 @@ int64_t Engine::prune(float max_n) {
   remap_server_slots();
   const int64_t dropped = (int64_t)total - pruned_keys_;
   pruned_keys_ = (int64_t)total;
+  if (dropped > 0) delta_needs_full_ = true;  // (a delta cannot say "this key left")
   return dropped;
 }
 
@@ -1846,6 +1867,7 @@ void Engine::export_table(std::vector<u64>& keys, std::vector<u32>& words) {
 
 // device arrays of n (key, state) pairs -> the table
 void Engine::table_from_device(const u64* dk, const u32* dw, int64_t n) {
+  delta_needs_full_ = true;  // (import_from / load: states set without marking)
   be_->table_import(table_, dk, dw, n);
   be_->synchronize();
   (void)table_size();  // (re-bases the capacity monitor)
@@ -1903,6 +1925,83 @@ void Engine::save(const std::string& path) {
   }
   ok = (std::fclose(f) == 0) && ok;
   if (!ok) throw std::runtime_error("write failed: " + path);
+}
+
+// ---------------------------------------------------------------------------
+// delta checkpoints (EngineConfig::delta_track)
+// ---------------------------------------------------------------------------
+int64_t Engine::delta_count() {
+  if (!delta_bits_) throw std::runtime_error("delta_count: delta tracking is off");
+  return be_->table_export_marked(table_, delta_bits_, delta_log2_, nullptr, nullptr, 0);
+}
+
+int64_t Engine::delta_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<u32>& dw) {
+  const int64_t n = delta_count();
+  if (n == 0) return 0;
+  dk.alloc(*be_, (size_t)n);
+  dw.alloc(*be_, (size_t)n * state_words());
+  if (be_->table_export_marked(table_, delta_bits_, delta_log2_, dk, dw, n) != n)
+    throw std::runtime_error("delta_export: marked key count changed between the passes");
+  return n;
+}
+
+void Engine::delta_export(std::vector<u64>& keys, std::vector<u32>& words) {
+  if (!delta_bits_) throw std::runtime_error("delta_export: delta tracking is off");
+  const int W = state_words();
+  DeviceBuffer<u64> dk;
+  DeviceBuffer<u32> dw;
+  const int64_t n = delta_to_device(dk, dw);
+  keys.resize((size_t)n);
+  words.resize((size_t)n * W);
+  if (n == 0) return;
+  d2h_stream(dk, sizeof(u64) * n, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)keys.data() + o, c, b);
+  });
+  d2h_stream(dw, sizeof(u32) * n * W, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)words.data() + o, c, b);
+  });
+}
+
+// Engine::save's format with hdr[7] = 1; the device buffers hold the delta only.
+void Engine::save_delta(const std::string& path) {
+  if (!delta_bits_) throw std::runtime_error("save_delta: delta tracking is off");
+  const int W = state_words();
+  DeviceBuffer<u64> dk;
+  DeviceBuffer<u32> dw;
+  const int64_t n = delta_to_device(dk, dw);
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot open " + path);
+  int32_t hdr[8] = {1, cfg_.model.kind, cfg_.model.v_dim, table_.L.P,
+                    table_.L.p_w, table_.L.opt, table_.L.stride, 1};
+  const uint64_t un = (uint64_t)n;
+  bool ok = std::fwrite(kMagic, 1, 8, f) == 8;
+  ok = ok && std::fwrite(hdr, sizeof(hdr), 1, f) == 1;
+  ok = ok && std::fwrite(&un, sizeof(un), 1, f) == 1;
+  if (n > 0 && ok) {
+    auto put = [&](const void* c, size_t, size_t b) {
+      ok = ok && std::fwrite(c, 1, b, f) == b;
+    };
+    d2h_stream(dk, sizeof(u64) * n, put);
+    d2h_stream(dw, sizeof(u32) * n * W, put);
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  if (!ok) throw std::runtime_error("write failed: " + path);
+}
+
+void Engine::delta_clear() {
+  delta_needs_full_ = false;
+  if (!delta_bits_) return;
+  be_->memset(delta_bits_, 0, sizeof(u32) * ((size_t)1 << (delta_log2_ - 5)));
+  ++delta_gen_;
+}
+
+DeltaStats Engine::delta_stats() {
+  DeltaStats s;
+  if (!delta_bits_) return s;
+  s.log2 = delta_log2_;
+  s.bits_set = be_->delta_popcount(delta_bits_, delta_log2_);
+  s.needs_full = delta_needs_full_;
+  return s;
 }
 
 void Engine::load(const std::string& path) {

@@ -94,6 +94,8 @@ Trainer::Trainer(const TrainerConfig& cfg) : cfg_(cfg) {
   ec.table_log2_cap = cfg_.table_log2_cap;
   ec.admit_min_count = cfg_.admit_min_count;
   ec.admit_log2 = cfg_.admit_log2;
+  ec.delta_track = cfg_.delta_track;
+  ec.delta_log2 = cfg_.delta_log2;
   int64_t maxb = std::max(cfg_.train_block_bytes, cfg_.test_block_bytes);
   ec.max_rows = maxb / 2 + 16;   // a row needs >= 2 bytes ("0\t")
   ec.max_nnz = maxb / 2 + 16;    // a token needs >= 2 bytes ("a:")

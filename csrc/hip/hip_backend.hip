@@ -416,6 +416,23 @@ class HipBackend final : public Backend {
     copy_d2h(&n, counter_, sizeof(n));
     return (int64_t)n;
   }
+  void delta_mark(u32* bits, int L, const u64* keys, const int64_t* n_dev, int64_t n_host,
+                  int64_t n_max) override {
+    hip::launch_delta_mark(bits, L, keys, n_dev, n_host, n_max, stream_);
+  }
+  int64_t table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
+                              u32* words_out, int64_t max_rows) override {
+    hip::launch_table_export_marked(t, bits, L, keys_out, words_out, max_rows, counter_, stream_);
+    unsigned long long n = 0;
+    copy_d2h(&n, counter_, sizeof(n));
+    return (int64_t)n;
+  }
+  int64_t delta_popcount(const u32* bits, int L) override {
+    hip::launch_delta_popcount(bits, L, counter_, stream_);
+    unsigned long long n = 0;
+    copy_d2h(&n, counter_, sizeof(n));
+    return (int64_t)n;
+  }
 
  private:
   int device_;

@@ -50,6 +50,13 @@ void launch_table_prune_finish(unsigned long long* size, unsigned long long* tot
                                const unsigned long long* count, hipStream_t st);
 void launch_table_nonzero(const TableView& t, const OptSpec& o, unsigned long long* counter,
                           hipStream_t st);
+// delta checkpoints: the touched-key filter of 2^L bits (delta_bit, common.h)
+void launch_delta_mark(u32* bits, int L, const u64* keys, const int64_t* n_dev, int64_t n_host,
+                       int64_t n_max, hipStream_t st);
+void launch_table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
+                                u32* words_out, int64_t max_rows, unsigned long long* counter,
+                                hipStream_t st);
+void launch_delta_popcount(const u32* bits, int L, unsigned long long* counter, hipStream_t st);
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

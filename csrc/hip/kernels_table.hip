@@ -2603,5 +2603,113 @@ void launch_table_nonzero(const TableView& t, const OptSpec& o, unsigned long lo
   XF_HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// delta checkpoints (EngineConfig::delta_track, docs/DESIGN.md §2): the
+// touched-key filter, one bit per key at delta_bit(key, L) of 2^L bits
+// ---------------------------------------------------------------------------
+// Shaped like k_admit_count: each lane owns kDeltaItems entries one block
+// apart and issues their key loads, then their filter-word loads, before it
+// resolves any.  The word is read first and the atomicOr issued only when the
+// bit is clear: bits only ever go from 0 to 1 between two clears, so a stale
+// read can only cost a redundant OR, and after an epoch's first steps the hot
+// head of the key distribution is marked and the kernel mostly reads.  A pure
+// OR: the filter depends on the set of keys alone, never on lane order.
+constexpr int kDeltaItems = 4;
+constexpr int kDeltaChunk = kBlock * kDeltaItems;
+
+__global__ void __launch_bounds__(kBlock) k_delta_mark(u32* __restrict__ bits, int L,
+                                                       const u64* __restrict__ keys,
+                                                       const int64_t* n_dev, int64_t n_host,
+                                                       int64_t n_max) {
+  const int64_t n = dev_count(n_dev, n_host, n_max);
+  if ((int64_t)blockIdx.x * kDeltaChunk >= n) return;  // (grid sized by capacity)
+  const int64_t base = (int64_t)blockIdx.x * kDeltaChunk + threadIdx.x;
+  bool on[kDeltaItems];
+  u64 bit[kDeltaItems];
+  u32 w[kDeltaItems];
+#pragma unroll
+  for (int j = 0; j < kDeltaItems; ++j) {
+    const int64_t i = base + (int64_t)j * kBlock;
+    on[j] = i < n;
+    bit[j] = delta_bit(on[j] ? sanitize_key(keys[i]) : 0ull, L);
+  }
+#pragma unroll
+  for (int j = 0; j < kDeltaItems; ++j) {
+    if (!on[j]) continue;
+    XF_DASSERT((bit[j] >> 5) < (1ull << (L - 5)));
+    w[j] = bits[bit[j] >> 5];
+  }
+#pragma unroll
+  for (int j = 0; j < kDeltaItems; ++j) {
+    if (!on[j]) continue;
+    const u32 m = 1u << (u32)(bit[j] & 31u);
+    if (!(w[j] & m)) atomicOr(bits + (bit[j] >> 5), m);
+  }
+}
+
+void launch_delta_mark(u32* bits, int L, const u64* keys, const int64_t* n_dev, int64_t n_host,
+                       int64_t n_max, hipStream_t st) {
+  if (L < kDeltaMinLog2 || L > kDeltaMaxLog2) throw std::runtime_error("delta_mark: log2");
+  const int64_t nm = n_dev ? n_max : n_host;
+  if (nm <= 0) return;
+  const int64_t g = (nm + kDeltaChunk - 1) / kDeltaChunk;
+  hipLaunchKernelGGL(k_delta_mark, dim3((unsigned)g), dim3(kBlock), 0, st, bits, L, keys, n_dev,
+                     n_host, n_dev ? n_max : n_host);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
+// k_table_export with one more predicate: the key's filter bit is set.
+// max_rows = 0 only counts (the outputs are not touched).
+__global__ void __launch_bounds__(kBlock) k_table_export_marked(
+    TableView t, const u32* __restrict__ bits, int L, u64* __restrict__ keys_out,
+    u32* __restrict__ words_out, int64_t max_rows, unsigned long long* counter) {
+  const int W = t.L.stride - 2;
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s < t.cap; s += stride) {
+    const u32* sp = t.words + s * (u64)t.L.stride;
+    const u64 key = *reinterpret_cast<const u64*>(sp);
+    bool live = key != kEmptyKey;
+    if (live) {
+      const u64 b = delta_bit(key, L);
+      live = (bits[b >> 5] >> (u32)(b & 31u)) & 1u;
+    }
+    unsigned long long idx = wave_append(counter, live);
+    if (live && (int64_t)idx < max_rows) {
+      keys_out[idx] = key;
+      for (int w = 0; w < W; ++w) words_out[idx * W + w] = sp[2 + w];
+    }
+  }
+}
+
+void launch_table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
+                                u32* words_out, int64_t max_rows, unsigned long long* counter,
+                                hipStream_t st) {
+  if (L < kDeltaMinLog2 || L > kDeltaMaxLog2) throw std::runtime_error("table_export_marked: log2");
+  XF_HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_table_export_marked, dim3(grid_for((int64_t)t.cap)), dim3(kBlock), 0, st,
+                     t, bits, L, keys_out, words_out, max_rows, counter);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
+// set bits of the filter's 2^(L - 5) words, one atomic per workgroup
+__global__ void __launch_bounds__(kBlock) k_delta_popcount(const u32* __restrict__ bits,
+                                                           u64 words,
+                                                           unsigned long long* counter) {
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  unsigned int cnt = 0;  // (<= 2^29 words over 2048 x 256 lanes: 2^15 bits a lane)
+  for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride)
+    cnt += __popc(bits[i]);
+  block_count_add<kBlock>(counter, cnt);
+}
+
+void launch_delta_popcount(const u32* bits, int L, unsigned long long* counter, hipStream_t st) {
+  if (L < kDeltaMinLog2 || L > kDeltaMaxLog2) throw std::runtime_error("delta_popcount: log2");
+  const u64 words = 1ull << (L - 5);
+  XF_HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_delta_popcount, dim3(grid_for((int64_t)words)), dim3(kBlock), 0, st, bits,
+                     words, counter);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace hip
 }  // namespace xflow

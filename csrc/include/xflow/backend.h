@@ -879,6 +879,17 @@ class Backend {
   virtual int64_t table_nonzero(const TableView& t, const OptSpec& o) = 0;
   virtual void table_import(const TableView& t, const u64* keys, const u32* words,
                             int64_t n) = 0;
+  // Delta checkpoints (EngineConfig::delta_track): the touched-key filter,
+  // 2^L bits in backend memory, bit delta_bit(key, L) per key (common.h).
+  // delta_mark sets the bit of every entry's sanitized key (*n_dev entries, at
+  // most n_max, when n_dev is set, else n_host) -- a pure OR, stream-ordered.
+  // table_export_marked is table_export restricted to the keys whose bit is
+  // set (max_rows = 0 only counts); delta_popcount counts the set bits.
+  virtual void delta_mark(u32* bits, int L, const u64* keys, const int64_t* n_dev,
+                          int64_t n_host, int64_t n_max) = 0;
+  virtual int64_t table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
+                                      u32* words_out, int64_t max_rows) = 0;
+  virtual int64_t delta_popcount(const u32* bits, int L) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

@@ -123,6 +123,19 @@ XF_HD AdmitPos admit_pos(u64 key, int log2_bytes) {
   return p;
 }
 
+// Delta checkpoints (EngineConfig::delta_track, docs/DESIGN.md §2): the bit of
+// a key in the touched-key filter of 2^log2 bits.  Indexed by a salted hash
+// of the key, not by its slot -- splits and prune re-pack slots -- and
+// independent of the key's table home, owner and admission counters.  One bit
+// per key: a collision can only add an untouched key to a delta.  Mirrored in
+// xflow_amd/testing/hashing.py.
+constexpr u64 kDeltaSalt = 0xe7037ed1a0b428dbull;
+constexpr int kDeltaMinLog2 = 10;
+constexpr int kDeltaMaxLog2 = 34;
+XF_HD u64 delta_bit(u64 key, int log2_bits) {
+  return fmix64(key ^ kDeltaSalt) & ((1ull << log2_bits) - 1);
+}
+
 // Reference sigmoid: clamp at |x|>30, otherwise e^x/(1+e^x) evaluated in
 // double with the literal base 2.718281828 (base.h:54-63).
 XF_HD float sigmoid_ref(float x) {

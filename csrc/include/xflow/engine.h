@@ -93,6 +93,24 @@ struct EngineConfig {
   // compaction's slot -> unique map everywhere (the A/B switch -- the results
   // are bit-equal either way).
   bool red_rank = true;
+  // Delta checkpoints (docs/DESIGN.md §2): a filter of 2^delta_log2 bits in
+  // device memory, indexed by key hash (delta_bit, common.h), in which every
+  // key whose state may have changed is marked -- by a launch of its own
+  // behind every inserting pull (the fused step, s_pull(insert), push_host);
+  // save_delta / delta_export write only the table's keys whose bit is set.
+  // A collision can only add an untouched key; a touched key is never
+  // missed.  Lookups never mark.  delta_log2: 10..34, 0 = min(34, the
+  // table's largest log2 capacity + 2).  The filter is allocated once and
+  // never grows.  false: no filter exists and no launch is added.
+  bool delta_track = false;
+  int delta_log2 = 0;
+};
+
+// Engine::delta_stats
+struct DeltaStats {
+  int log2 = 0;            // log2 of the filter's bits (0: tracking off)
+  int64_t bits_set = 0;    // popcount of the filter
+  bool needs_full = false; // the table changed in a way a delta cannot carry
 };
 
 // The dedup scratch's counters (Engine::scratch_stats).  The CPU backend has
@@ -414,6 +432,24 @@ class Engine {
   // Binary shard file: header + keys + state words.
   void save(const std::string& path);
   void load(const std::string& path);
+  // ---- delta checkpoints (EngineConfig::delta_track) ----------------------
+  // The table's keys whose filter bit is set: their number (a count pass;
+  // syncs), host copies of them and their state words (count pass, device
+  // buffers of exactly that size, the staged transfer of export_into), and
+  // the same as a shard file in save's format whose spare header word
+  // hdr[7] = 1 marks a delta.  All three throw with tracking off.
+  int64_t delta_count();
+  void delta_export(std::vector<u64>& keys, std::vector<u32>& words);
+  void save_delta(const std::string& path);
+  // zero the filter and reset needs_full: the next delta holds what changes
+  // from here on (no-op with tracking off)
+  void delta_clear();
+  // needs_full: set by what a delta cannot express or what bypasses marking
+  // -- a prune that dropped a key, import_from / import_table / load, prefill
+  DeltaStats delta_stats();
+  // (the two host-side fields of delta_stats, without its popcount pass)
+  int delta_log2() const { return delta_log2_; }
+  bool delta_needs_full() const { return delta_bits_ && delta_needs_full_; }
 
   // libffm text block (backend memory, 16-byte aligned) -> CSR arrays in
   // backend memory, on the device (Backend::parse_text).  Returns {rows,
@@ -456,6 +492,17 @@ class Engine {
   size_t table_bytes_ = 0;
   ScratchView scratch_;
   DeviceBuffer<unsigned char> admit_counters_;
+  // delta checkpoints: the touched-key filter (null: tracking off)
+  DeviceBuffer<u32> delta_bits_;
+  int delta_log2_ = 0;
+  bool delta_needs_full_ = false;
+  uint64_t delta_gen_ = 0;  // delta_clear() calls so far
+  // queue the marks of n keys (*n_dev when set) behind the stream's work
+  void delta_mark(const u64* keys, const int64_t* n_dev, int64_t n) {
+    if (delta_bits_) be_->delta_mark(delta_bits_, delta_log2_, keys, n_dev, n, n);
+  }
+  // count pass, then the marked keys into device buffers of exactly that size
+  int64_t delta_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<u32>& dw);
   DeviceBuffer<u64> scratch_keys_;
   DeviceBuffer<unsigned char> scratch_stamps_;
   DeviceBuffer<unsigned long long> scratch_claims_, scratch_ctl_;
@@ -629,10 +676,20 @@ class Engine {
     DeviceBuffer<u32> own_pos;    // owner grouping of the buffer's entries
     DeviceBuffer<u64> own_idx;
     SrcGroups grp;                // grp.oidx != null: s_pull grouped this buffer
+    uint64_t delta_gen = 0;       // delta_gen_ when s_pull marked the buffer's keys
   };
   SrvBuf srv_[kSrvBufs];
   void stale_stashes() {
     for (SrvBuf& b : srv_) b.nz_fresh = false;
+  }
+  // Delta checkpoints: every apply follows an inserting s_pull of the same
+  // keys into the same buffer, which marked them -- unless delta_clear ran in
+  // between (a save between a pipelined step's pull and its apply) or the
+  // pull did not insert: then the apply marks its n keys itself.
+  void mark_stale_buffer(SrvBuf& sb, const u64* keys, int64_t n) {
+    if (!delta_bits_ || sb.delta_gen == delta_gen_ || n <= 0) return;
+    delta_mark(keys, nullptr, n < sb.n ? n : sb.n);
+    sb.delta_gen = delta_gen_;
   }
   bool lr16_layout() const;
 

@@ -41,6 +41,8 @@ struct TrainerConfig {
   int table_log2_cap = 22;
   int admit_min_count = 1;         // EngineConfig::admit_min_count / admit_log2
   int admit_log2 = 0;
+  bool delta_track = false;       // EngineConfig::delta_track / delta_log2
+  int delta_log2 = 0;
   int prune_every = 0;             // Engine::prune at the end of every N-th epoch (0: never)
   float prune_max_n = -1.0f;       // ... of keys with every FTRL n <= this (negative: no bound)
   ModelSpec model_spec;            // v_dim, math modes (kind is taken from `model`)

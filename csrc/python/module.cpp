@@ -408,8 +408,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int device, bool table_grow, double grow_load, int max_log2_cap,
                        int monitor_lag, int owner_group, double grow_start, bool csr,
                        int admit_min_count, int admit_log2, bool lead_handoff,
-                       bool scratch_carry, bool red_rank) {
+                       bool scratch_carry, bool red_rank, bool delta_track, int delta_log2) {
              EngineConfig c;
+             c.delta_track = delta_track;
+             c.delta_log2 = delta_log2;
              c.red_rank = red_rank;
              c.lead_handoff = lead_handoff;
              c.scratch_carry = scratch_carry;
@@ -441,7 +443,37 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("monitor_lag") = 2, py::arg("owner_group") = 0, py::arg("grow_start") = 0.6,
            py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
            py::arg("lead_handoff") = true, py::arg("scratch_carry") = true,
-           py::arg("red_rank") = true)
+           py::arg("red_rank") = true, py::arg("delta_track") = false,
+           py::arg("delta_log2") = 0)
+      // delta checkpoints (EngineConfig::delta_track)
+      .def("delta_count", &Engine::delta_count, py::call_guard<py::gil_scoped_release>())
+      .def("delta_export",
+           [](Engine& e) {
+             std::vector<u64> k;
+             std::vector<u32> w;
+             {
+               py::gil_scoped_release nogil;
+               e.delta_export(k, w);
+             }
+             return py::make_tuple(to_np(k), to_np(w));
+           })
+      .def("save_delta", &Engine::save_delta, py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("delta_log2", &Engine::delta_log2)
+      .def_property_readonly("delta_needs_full", &Engine::delta_needs_full)
+      .def("delta_clear", &Engine::delta_clear, py::call_guard<py::gil_scoped_release>())
+      .def("delta_stats",
+           [](Engine& e) {
+             DeltaStats s;
+             {
+               py::gil_scoped_release nogil;
+               s = e.delta_stats();
+             }
+             py::dict d;
+             d["log2"] = s.log2;
+             d["bits_set"] = s.bits_set;
+             d["needs_full"] = s.needs_full;
+             return d;
+           })
       .def_property_readonly("admit_bytes", &Engine::admit_bytes)
       .def_property_readonly("admit_log2", &Engine::admit_log2)
       .def("admit_counts",
@@ -866,6 +898,8 @@ PYBIND11_MODULE(_xflow_native, m) {
         if (d.contains("table_log2_cap")) c.table_log2_cap = d["table_log2_cap"].cast<int>();
         if (d.contains("admit_min_count")) c.admit_min_count = d["admit_min_count"].cast<int>();
         if (d.contains("admit_log2")) c.admit_log2 = d["admit_log2"].cast<int>();
+        if (d.contains("delta_track")) c.delta_track = d["delta_track"].cast<bool>();
+        if (d.contains("delta_log2")) c.delta_log2 = d["delta_log2"].cast<int>();
         if (d.contains("prune_every")) c.prune_every = d["prune_every"].cast<int>();
         if (d.contains("prune_max_n")) c.prune_max_n = d["prune_max_n"].cast<float>();
         if (d.contains("sum_slices")) c.sum_slices = d["sum_slices"].cast<bool>();

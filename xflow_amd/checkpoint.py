@@ -11,6 +11,18 @@ Layout of ``<dir>/``:
                                  counting filter, its raw bytes; meta.json then
                                  also records admit_min_count and admit_log2
 
+  delta-<rank>-of-<world>.xftb   instead of the shard, in a delta version
+                                 (meta.json "delta_base": "<version dir name>"):
+                                 only the keys touched since that version was
+                                 saved (Engine.save_delta, the shard format with
+                                 header word 7 = 1)
+
+A delta version (``save(..., delta_base=...)``, EngineConfig.delta_track) is
+loaded by resolving its chain of bases back to a full version, loading that
+one and importing each delta on top, oldest first -- an import overwrites the
+state of a key that is present.  ``publish`` never deletes a version that a
+kept version's chain needs.
+
 Resume is world-size agnostic: with the same world size each rank loads its
 own shard; otherwise every rank scans all shards and imports exactly the keys
 it owns under the new hash sharding (owner = fmix64(key) >> 32 mod world).
@@ -48,6 +60,10 @@ def shard_name(rank: int, world: int) -> str:
 
 def admit_name(rank: int, world: int) -> str:
     return f"admit-{rank:05d}-of-{world:05d}.xfad"
+
+
+def delta_name(rank: int, world: int) -> str:
+    return f"delta-{rank:05d}-of-{world:05d}.xftb"
 
 
 def shard_keys(path: str) -> int:
@@ -97,18 +113,57 @@ def _default_barrier() -> None:
         dist.barrier()
 
 
+def _tip(ckpt_dir: str) -> str:
+    return os.path.abspath(ckpt_dir)
+
+
+def _can_delta(engine, ckpt_dir: str, world: int, delta_base: Optional[str]) -> bool:
+    """Whether this save may be a delta on ``delta_base``: tracking on, nothing
+    happened that a delta cannot carry, the base is a complete version under
+    the same root, written with the same world size -- and it is the version
+    the engine's filter was last cleared at (its last save or load)."""
+    if not delta_base or engine.delta_log2 == 0 or engine.delta_needs_full:
+        return False
+    base = os.path.join(os.path.dirname(_tip(ckpt_dir)), delta_base)
+    if getattr(engine, "_delta_tip", None) != _tip(base):
+        return False
+    try:
+        return int(load_meta(base)["world"]) == world
+    except (OSError, ValueError, KeyError):
+        return False
+
+
 def save(engine, ckpt_dir: str, rank: int, world: int, meta: Optional[dict] = None,
-         barrier: Optional[Callable[[], None]] = None) -> str:
+         barrier: Optional[Callable[[], None]] = None, delta_base: Optional[str] = None) -> str:
     """Write this rank's shard (fsync'd), wait for every rank (``barrier``,
     default: the torch.distributed group when one is initialised), then rank 0
     writes meta.json -- so a valid meta.json only ever sits next to a complete
-    set of shards of one save."""
+    set of shards of one save.  Returns the shard's path.
+
+    ``delta_base``: the name of the previous version's directory under the
+    same root.  The rank then writes only the keys touched since that version
+    (``delta-*.xftb``) and meta.json names the base -- when the engine tracks
+    deltas, its ``needs_full`` is unset, and the base exists with this world
+    size; otherwise the version is a full one.  Ranks of one job must decide
+    alike: ``needs_full`` is per rank, so a multi-rank caller passes a base
+    only when no rank needs a full save (Trainer.save_versioned).  Once its
+    file is durable the rank clears its filter (delta_clear), after a full
+    save too: the next delta holds what changes from here on."""
     os.makedirs(ckpt_dir, exist_ok=True)
-    path = os.path.join(ckpt_dir, shard_name(rank, world))
+    delta = _can_delta(engine, ckpt_dir, world, delta_base)
+    name, other = delta_name(rank, world), shard_name(rank, world)
+    if not delta:
+        name, other = other, name
+    path = os.path.join(ckpt_dir, name)
     tmp = path + ".tmp"
-    engine.save(tmp)
+    (engine.save_delta if delta else engine.save)(tmp)
     _fsync_file(tmp)
     os.replace(tmp, path)
+    stale = os.path.join(ckpt_dir, other)  # (an interrupted save of the other kind)
+    if os.path.exists(stale):
+        os.remove(stale)
+    engine.delta_clear()
+    engine._delta_tip = _tip(ckpt_dir)
     admit = engine.admit_bytes() > 0
     if admit:  # the admission filter next to the shard
         apath = os.path.join(ckpt_dir, admit_name(rank, world))
@@ -122,6 +177,14 @@ def save(engine, ckpt_dir: str, rank: int, world: int, meta: Optional[dict] = No
         m = dict(meta or {})
         m.update(world=world, model=dataclasses.asdict(engine.model),
                  optim=dataclasses.asdict(engine.optim))
+        m.pop("delta_base", None)
+        if delta:
+            m["delta_base"] = delta_base
+        kinds = [len(glob.glob(os.path.join(ckpt_dir, pat % world)))
+                 for pat in ("delta-*-of-%05d.xftb", "shard-*-of-%05d.xftb")]
+        if kinds[0] and kinds[1]:
+            raise RuntimeError(f"{ckpt_dir}: the ranks did not agree on a full or a delta save "
+                               f"(delta, full files: {kinds}, world {world})")
         if admit:
             m.update(admit_min_count=int(engine.cfg.admit_min_count),
                      admit_log2=int(engine.admit_log2))
@@ -193,23 +256,79 @@ def _load_admit(engine, ckpt_dir: str, rank: int, world: int, meta: dict) -> Non
                 meta.get("admit_log2"))
 
 
-def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
-    meta = load_meta(ckpt_dir)
-    check_compatible(engine, meta)
-    saved_world = int(meta["world"])
-    _load_admit(engine, ckpt_dir, rank, world, meta)
+def chain(ckpt_dir: str) -> list:
+    """The version directories ``ckpt_dir`` is made of, oldest first: the full
+    version its chain of ``delta_base`` links ends at, then every delta up to
+    ``ckpt_dir`` itself ([ckpt_dir] for a full version).  A link that is
+    missing raises FileNotFoundError naming it."""
+    tip = _tip(ckpt_dir)
+    out, d = [], tip
+    while True:
+        if not os.path.exists(os.path.join(d, "meta.json")):
+            raise FileNotFoundError(
+                f"{d}: no meta.json" if d == tip else
+                f"{tip}: its delta chain needs the version {d}, which is missing")
+        if d in out:
+            raise ValueError(f"{tip}: delta chain loops at {d}")
+        out.append(d)
+        base = load_meta(d).get("delta_base")
+        if not base:
+            return out[::-1]
+        d = os.path.join(os.path.dirname(d), base)
+
+
+def chain_files(ckpt_dir: str) -> list:
+    """Every table file of the chain, in loading order: the full version's
+    shards, then each delta version's.  Raises FileNotFoundError when a
+    version does not hold one file per saved rank."""
+    files = []
+    for i, d in enumerate(chain(ckpt_dir)):
+        w = int(load_meta(d)["world"])
+        pat = ("shard-*-of-%05d.xftb" if i == 0 else "delta-*-of-%05d.xftb") % w
+        got = sorted(glob.glob(os.path.join(d, pat)))
+        if len(got) != w:
+            raise FileNotFoundError(f"{d}: expected {w} files {pat}, found {len(got)}")
+        files += got
+    return files
+
+
+def _load_version(engine, d: str, rank: int, world: int, delta: bool) -> None:
+    """One version's table files into the engine: this rank's own file when
+    the world size is the saved one, else the keys it now owns of every file.
+    An import overwrites the state of a present key, so a delta lands on top
+    of what its bases loaded."""
+    saved_world = int(load_meta(d)["world"])
+    name = delta_name if delta else shard_name
     if saved_world == world:
-        engine.load(os.path.join(ckpt_dir, shard_name(rank, world)))
-        return meta
-    shards = sorted(glob.glob(os.path.join(ckpt_dir, "shard-*-of-%05d.xftb" % saved_world)))
+        p = os.path.join(d, name(rank, world))
+        if not os.path.exists(p):
+            raise FileNotFoundError(f"{p}: missing")
+        engine.load(p)
+        return
+    pat = ("delta-*-of-%05d.xftb" if delta else "shard-*-of-%05d.xftb") % saved_world
+    shards = sorted(glob.glob(os.path.join(d, pat)))
     if len(shards) != saved_world:
-        raise FileNotFoundError(f"{ckpt_dir}: expected {saved_world} shards, found {len(shards)}")
+        raise FileNotFoundError(f"{d}: expected {saved_world} shards, found {len(shards)}")
     for p in shards:
         hdr, keys, words = read_shard(p)
         _check_header(engine, p, hdr)
         mine = owner_of(keys, world) == rank
         if mine.any():
             engine.import_table(keys[mine], words[mine].reshape(-1))
+
+
+def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
+    """Load the version (resolving a delta's chain, see ``chain``) and leave
+    the engine's touched-key filter clean: its state equals the chain's tip,
+    so the next save may be a delta on ``ckpt_dir``."""
+    links = chain(ckpt_dir)
+    meta = load_meta(ckpt_dir)
+    check_compatible(engine, meta)
+    _load_admit(engine, ckpt_dir, rank, world, meta)
+    for i, d in enumerate(links):
+        _load_version(engine, d, rank, world, delta=i > 0)
+    engine.delta_clear()
+    engine._delta_tip = _tip(ckpt_dir)
     return meta
 
 
@@ -222,7 +341,8 @@ def version_dir(root: str, epoch: int) -> str:
 
 def publish(root: str, epoch: int, keep: int = 2) -> None:
     """Rank 0, after every rank saved the epoch's shards: point LATEST at the
-    version atomically and drop all but the newest ``keep`` versions."""
+    version atomically and drop all but the newest ``keep`` versions -- and
+    the versions those are deltas on (``chain``)."""
     tmp = os.path.join(root, LATEST + ".tmp")
     with open(tmp, "w") as f:
         f.write(os.path.basename(version_dir(root, epoch)) + "\n")
@@ -230,8 +350,16 @@ def publish(root: str, epoch: int, keep: int = 2) -> None:
         os.fsync(f.fileno())
     os.replace(tmp, os.path.join(root, LATEST))
     _fsync_dir(root)
-    for d in sorted(glob.glob(os.path.join(root, "epoch-*")))[:-keep]:
-        shutil.rmtree(d, ignore_errors=True)
+    vers = sorted(glob.glob(os.path.join(root, "epoch-*")))
+    needed = set()
+    for d in vers[-keep:]:  # the kept versions and every link of their chains
+        try:
+            needed.update(chain(d))
+        except (OSError, ValueError):
+            needed.add(_tip(d))
+    for d in vers[:-keep]:
+        if _tip(d) not in needed:
+            shutil.rmtree(d, ignore_errors=True)
 
 
 def latest(root: str) -> Optional[str]:

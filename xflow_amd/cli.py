@@ -107,6 +107,15 @@ def build_parser() -> argparse.ArgumentParser:
                          "exists (epochs = total for the run) and write periodic saves there")
     ap.add_argument("--save-every", type=int, default=0,
                     help="versioned checkpoint every N epochs under --resume (or --save) root")
+    ap.add_argument("--save-delta", action="store_true",
+                    help="versioned checkpoints (--save-every) write only the keys touched since "
+                         "the previous version; loading resolves the chain of deltas")
+    ap.add_argument("--delta-full-every", type=int, default=8,
+                    help="--save-delta: every K-th version of a chain is a full one (bounds the "
+                         "chain's length and the restart time)")
+    ap.add_argument("--delta-log2", type=int, default=0,
+                    help="--save-delta: bits of the touched-key filter per rank = 2^N (10..34; 0: "
+                         "min(34, the table's largest log2 capacity + 2))")
     ap.add_argument("--metrics", default="", help="JSON-lines metrics file (rank 0)")
     ap.add_argument("--trace-dir", default="", help="torch.profiler chrome trace directory")
     return ap
@@ -124,6 +133,7 @@ def config_from_args(a) -> TrainConfig:
         init_push=not a.no_init_push, pred_dir=a.pred_dir, write_pred=not a.no_pred_file,
         checkpoint_dir=a.save,
         save_every=a.save_every, resume_dir=a.resume,
+        save_delta=a.save_delta, delta_full_every=a.delta_full_every,
         prune_every=a.prune_every, prune_max_n=a.prune_max_n, gauc_field=a.gauc_field,
         metrics_file=a.metrics, async_p2p=a.async_p2p, async_ps=a.async_ps,
         staleness=a.staleness,
@@ -133,7 +143,8 @@ def config_from_args(a) -> TrainConfig:
                           lambda2=a.lambda2, lr=a.lr),
         engine=EngineConfig(table_log2_cap=a.log2_cap, sum_slices=a.sum_slices,
                             max_log2_cap=a.max_log2_cap, table_grow=not a.no_table_grow,
-                            admit_min_count=a.admit_min_count, admit_log2=a.admit_log2))
+                            admit_min_count=a.admit_min_count, admit_log2=a.admit_log2,
+                            delta_track=a.save_delta, delta_log2=a.delta_log2))
 
 
 def main(argv=None) -> int:

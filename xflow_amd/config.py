@@ -124,6 +124,13 @@ class EngineConfig:
     # the compaction writes no slot -> unique map; False keeps the map
     # (bit-equal results, the A/B switch)
     red_rank: bool = True
+    # delta checkpoints (docs/DESIGN.md §2): mark every key whose state may
+    # have changed in a filter of 2^delta_log2 bits indexed by key hash, so
+    # that Engine.save_delta writes only those keys.  delta_log2: 10..34,
+    # 0 = min(34, the table's largest log2 capacity + 2).  False: no filter,
+    # no extra launch.  csrc/include/xflow/engine.h
+    delta_track: bool = False
+    delta_log2: int = 0
 
 
 @dataclass
@@ -154,6 +161,12 @@ class TrainConfig:
     checkpoint_dir: str = ""
     save_every: int = 0          # versioned checkpoint every N epochs (checkpoint.publish)
     resume_dir: str = ""         # versioned checkpoint root: resume from LATEST, save there
+    # versioned saves write only the keys touched since the previous version
+    # (checkpoint.save delta_base; turns engine.delta_track on); every
+    # delta_full_every-th version of a chain is a full one, which bounds the
+    # chain's length and the restart time
+    save_delta: bool = False
+    delta_full_every: int = 8
     # prune the table (Engine.prune: drop keys whose weights are all exactly
     # zero) at the end of every N-th epoch, 0: never; prune_max_n: with FTRL
     # only keys with every n <= it (negative: no bound)

@@ -160,7 +160,9 @@ class Engine:
                            admit_log2=self.cfg.admit_log2,
                            lead_handoff=self.cfg.lead_handoff,
                            scratch_carry=self.cfg.scratch_carry,
-                           red_rank=self.cfg.red_rank)
+                           red_rank=self.cfg.red_rank,
+                           delta_track=self.cfg.delta_track,
+                           delta_log2=self.cfg.delta_log2)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -280,6 +282,50 @@ class Engine:
     def admit_import(self, counters: np.ndarray) -> None:
         self._sync_stream()
         self._e.admit_import(np.ascontiguousarray(counters, dtype=np.uint8))
+
+    # ---- delta checkpoints (EngineConfig.delta_track) ------------------------
+    def delta_stats(self) -> dict:
+        """{log2, bits_set, needs_full}: log2 of the touched-key filter's bits
+        (0: tracking off), its popcount (synchronises), and whether the table
+        changed in a way a delta cannot carry (a prune that dropped a key,
+        import_table / load, prefill) so that the next save must be full."""
+        self._sync_stream()
+        d = self._e.delta_stats()
+        return {"log2": int(d["log2"]), "bits_set": int(d["bits_set"]),
+                "needs_full": bool(d["needs_full"])}
+
+    @property
+    def delta_log2(self) -> int:
+        """log2 of the touched-key filter's bits as allocated (0: tracking off)."""
+        return int(self._e.delta_log2)
+
+    @property
+    def delta_needs_full(self) -> bool:
+        """delta_stats()["needs_full"] without the popcount pass (no sync)."""
+        return bool(self._e.delta_needs_full)
+
+    def delta_count(self) -> int:
+        """Keys of the table whose filter bit is set (a count pass; syncs)."""
+        self._sync_stream()
+        return int(self._e.delta_count())
+
+    def delta_export(self):
+        """(keys u64 [n], words u32 [n * state_words]) of the table's keys
+        whose filter bit is set: every key touched since the last
+        delta_clear(), plus the untouched keys that share a bit with one."""
+        self._sync_stream()
+        return self._e.delta_export()
+
+    def save_delta(self, path: str) -> None:
+        """delta_export() as a shard file (Engine.save's format, header word
+        7 = 1)."""
+        self._sync_stream()
+        self._e.save_delta(path)
+
+    def delta_clear(self) -> None:
+        """Zero the filter and reset needs_full (no-op with tracking off)."""
+        self._sync_stream()
+        self._e.delta_clear()
 
     def server_slots(self, buf: int = 0) -> np.ndarray:
         """Table slots the last s_pull into server buffer ``buf`` recorded

@@ -58,7 +58,8 @@ PULL, PUSH, EVAL = 0, 1, 2
 def worker_config(cfg: EngineConfig) -> EngineConfig:
     """The worker engine's config: the same model / batch limits, a token
     table (the worker never owns keys)."""
-    return dataclasses.replace(cfg, table_log2_cap=min(cfg.table_log2_cap, 16), table_grow=False)
+    return dataclasses.replace(cfg, table_log2_cap=min(cfg.table_log2_cap, 16), table_grow=False,
+                               delta_track=False)
 
 
 class AsyncParameterServer:

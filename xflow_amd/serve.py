@@ -25,7 +25,6 @@ at a time (a lock around the device work).
 from __future__ import annotations
 
 import argparse
-import glob
 import math
 import os
 import threading
@@ -65,9 +64,10 @@ class Predictor:
         self.model = _fields(ModelConfig, meta["model"])
         self.optim = _fields(OptimConfig, meta["optim"])
         self.meta = meta
-        # (key counts from the shard headers: nothing else is read twice)
-        n_keys = sum(checkpoint.shard_keys(p) for p in glob.glob(
-            os.path.join(self.ckpt, "shard-*-of-%05d.xftb" % int(meta["world"]))))
+        # (key counts from the shard headers: nothing else is read twice; a
+        # delta version: its full base's shards plus every delta's of its
+        # chain, an upper bound -- a delta repeats keys its bases hold)
+        n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(self.ckpt))
         # every shard's keys in one table at load <= 0.5 (no growth while serving)
         lg = max(16, int(math.ceil(math.log2(max(2 * n_keys, 1)))))
         if device is None:

@@ -105,3 +105,13 @@ def admit_pos(keys: np.ndarray, log2_bytes: int):
     block = (h >> np.uint64(12)) & np.uint64((1 << (log2_bytes - 6)) - 1)
     base = block << np.uint64(6)
     return (base | o0).astype(np.int64), (base | o1).astype(np.int64)
+
+
+DELTA_SALT = 0xE7037ED1A0B428DB
+
+
+def delta_bit(keys: np.ndarray, log2_bits: int) -> np.ndarray:
+    """Bit index of each key in the touched-key filter of 2^log2_bits bits
+    (common.h delta_bit): one salted fmix64 of the sanitized key, its low bits."""
+    h = fmix64(sanitize_keys(keys) ^ np.uint64(DELTA_SALT))
+    return (h & np.uint64((1 << log2_bits) - 1)).astype(np.int64)

@@ -123,6 +123,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="versioned checkpoint root for per-epoch saves and recovery "
                          "(required with --max-restarts > 0)")
     ap.add_argument("--save-every", type=int, default=1, help="epochs between checkpoints")
+    ap.add_argument("--save-delta", action="store_true",
+                    help="delta checkpoints: forwarded to every rank (xflow_amd.cli --save-delta)")
     ap.add_argument("--timeout", type=float, default=0.0, help="seconds per attempt (0: none)")
     ap.add_argument("--grace", type=float, default=5.0,
                     help="seconds between SIGTERM and SIGKILL when stopping ranks")
@@ -143,6 +145,8 @@ def main(argv=None) -> int:
     cmd = [sys.executable, "-m", "xflow_amd.cli", *args]
     if a.ckpt:
         cmd += ["--resume", a.ckpt, "--save-every", str(a.save_every)]
+        if a.save_delta:
+            cmd += ["--save-delta"]
     rc = 1
     for attempt in range(a.max_restarts + 1):
         t0 = time.monotonic()

@@ -97,6 +97,14 @@ class Trainer:
                 ecfg.max_rows = max(ecfg.max_rows, rows)
                 ecfg.max_nnz = max(ecfg.max_nnz, nnz)
         ecfg.max_slices = max(ecfg.max_slices, self.S)
+        if cfg.save_delta:
+            if cfg.delta_full_every < 1:
+                raise ValueError("--delta-full-every must be >= 1")
+            ecfg.delta_track = True
+        # delta checkpoints: the version last saved or resumed from (the base of
+        # the next delta) and the deltas written since its chain's full version
+        self._delta_base = None
+        self._delta_links = 0
         self.sharded = None
         self.aps = None
         if self.world > 1 and cfg.async_ps:
@@ -462,11 +470,11 @@ class Trainer:
             if self.cfg.optim.lambda1 > 0 and os.environ.get("XFLOW_REPORT_NNZ"):
                 rec["nonzero_weights"] = int(xdist.all_sum([self.table.nonzero_weights()],
                                                            self.device)[0])
-            self.metrics.log(**rec)
             root = cfg.resume_dir or cfg.checkpoint_dir
             every = cfg.save_every or (1 if os.environ.get("XFLOW_CKPT_EVERY_EPOCH") else 0)
             if root and every and self.epoch % every == 0:
-                self.save_versioned(root)
+                rec["ckpt_kind"], rec["ckpt_keys"] = self.save_versioned(root)
+            self.metrics.log(**rec)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
 
@@ -605,27 +613,52 @@ class Trainer:
         return res
 
     # ------------------------------------------------------------ checkpoint
-    def save(self, ckpt_dir: str) -> None:
+    def save(self, ckpt_dir: str, delta_base: Optional[str] = None) -> str:
+        """Returns the path of this rank's table file (a delta-* file when
+        the version was written as a delta on ``delta_base``)."""
         if hasattr(self.sharded, "flush"):
             self.sharded.flush()
-        checkpoint.save(self.table, ckpt_dir, self.rank, self.world,
-                        meta={"epoch": self.epoch, "steps": self.steps}, barrier=xdist.barrier)
+        path = checkpoint.save(self.table, ckpt_dir, self.rank, self.world,
+                               meta={"epoch": self.epoch, "steps": self.steps},
+                               barrier=xdist.barrier, delta_base=delta_base)
         xdist.barrier()
+        return path
 
     def load(self, ckpt_dir: str) -> dict:
         meta = checkpoint.load(self.table, ckpt_dir, self.rank, self.world)
         self.epoch = int(meta.get("epoch", 0))
         self.steps = int(meta.get("steps", 0))
+        self._delta_base = os.path.abspath(ckpt_dir)
+        self._delta_links = len(checkpoint.chain(ckpt_dir)) - 1
         xdist.barrier()
         return meta
 
-    def save_versioned(self, root: str) -> None:
+    def save_versioned(self, root: str):
         """Periodic checkpoint: every rank writes its shard of this epoch's
-        version, then rank 0 publishes it as LATEST (checkpoint.publish)."""
-        self.save(checkpoint.version_dir(root, self.epoch))
+        version, then rank 0 publishes it as LATEST (checkpoint.publish).
+        With ``save_delta`` the version holds only the keys touched since the
+        version last saved or resumed from, when that one lies under ``root``,
+        fewer than ``delta_full_every`` - 1 deltas were written since the
+        chain's full version and no rank needs a full save.  Returns
+        ("full" | "delta", keys written by all ranks)."""
+        d = checkpoint.version_dir(root, self.epoch)
+        base = None
+        b = self._delta_base
+        if (self.cfg.save_delta and b and b != os.path.abspath(d)
+                and os.path.dirname(b) == os.path.abspath(root)
+                and self._delta_links < self.cfg.delta_full_every - 1):
+            # (needs_full is per rank: a delta only when no rank needs a full save)
+            if xdist.all_sum([float(self.table.delta_needs_full)], self.device)[0] == 0:
+                base = os.path.basename(b)
+        path = self.save(d, delta_base=base)
+        delta = os.path.basename(path).startswith("delta-")
+        self._delta_base = os.path.abspath(d)
+        self._delta_links = self._delta_links + 1 if delta else 0
+        nkeys = int(xdist.all_sum([float(checkpoint.shard_keys(path))], self.device)[0])
         if self.rank == 0:
             checkpoint.publish(root, self.epoch)
         xdist.barrier()
+        return ("delta" if delta else "full"), nkeys
 
     def resume(self, root: str) -> Optional[dict]:
         """Continue from root's newest complete versioned checkpoint, if any
