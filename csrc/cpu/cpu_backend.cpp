@@ -666,13 +666,16 @@ class CpuBackend final : public Backend {
   size_t table_committed() const override { return mm_bytes_ ? committed_ : fb_bytes_; }
   bool table_in_place() const override { return mm_bytes_ != 0; }
   EvalMetrics eval_metrics(const float* pctr, const float* labels, int64_t n) override {
-    // same definition as the HIP kernels: stable order by pctr descending
+    // same definition as the HIP kernels: stable order by the key bits
+    // (eval_key_bits, backend.h) descending -- integers, so a strict weak
+    // order for every input, NaN included
     EvalMetrics m;
     m.n = n;
     std::vector<int64_t> idx((size_t)n);
     for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = i;
-    std::stable_sort(idx.begin(), idx.end(),
-                     [&](int64_t a, int64_t b) { return pctr[a] > pctr[b]; });
+    std::stable_sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {
+      return eval_key_bits(pctr[a]) > eval_key_bits(pctr[b]);
+    });
     uint64_t tp = 0;
     for (int64_t i : idx) {
       if (labels[i] > 0.5f) ++tp;
@@ -694,12 +697,7 @@ class CpuBackend final : public Backend {
     GroupedEval r;
     r.n = n;
     if (table) *table = GroupTable();
-    auto bits = [&](int64_t i) {
-      const float p = pctr[i] > 0.0f ? pctr[i] : 0.0f;
-      u32 b;
-      std::memcpy(&b, &p, sizeof(b));
-      return b;
-    };
+    auto bits = [&](int64_t i) { return eval_key_bits(pctr[i]); };
     std::vector<int64_t> idx((size_t)n);
     for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = i;
     std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {

@@ -7,7 +7,8 @@
 // stay in HBM:
 //
 //   1. stable LSD radix sort of (key = ~bits(pctr), label) pairs, 4 passes of
-//      8 bits (pctr > 0, so the float bits order like the values; ~ makes it
+//      8 bits (the key is eval_key_bits, backend.h: pctr > 0 keeps its float
+//      bits, which order like the values, everything else is +0; ~ makes it
 //      descending; ties keep prediction order), each pass
 //        k_rs_hist     per-tile digit histograms (LDS)
 //        k_rs_scan     per-digit exclusive scan over tiles (one workgroup per digit)
@@ -127,7 +128,7 @@ __global__ void __launch_bounds__(kBlock) k_auc_keys(const float* __restrict__ p
                                                      u32* __restrict__ keys, u32* __restrict__ vals) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    keys[i] = ~__float_as_uint(fmaxf(pctr[i], 0.0f));  // descending pctr
+    keys[i] = ~eval_key_bits(pctr[i]);  // descending pctr
     vals[i] = labels[i] > 0.5f ? 1u : 0u;
   }
 }
@@ -313,7 +314,7 @@ void launch_eval_metrics(const float* pctr, const float* labels, int64_t n, Eval
 
 // ---- grouped evaluation (GroupedEval, backend.h) ---------------------------
 //
-//   1. k_grp_init      gk = group key, pv = bits(fmaxf(pctr, 0)) << 1 | label per
+//   1. k_grp_init      gk = group key, pv = eval_key_bits(pctr) << 1 | label per
 //                      row; OR / AND of all group keys (which key bytes vary)
 //   2. stable LSD radix sort of the (gk, pv) pairs, 8 bits a pass: 4 passes on
 //      ~bits(pctr) (descending pctr), then one per byte of the group key that
@@ -382,7 +383,7 @@ __global__ void __launch_bounds__(kBlock) k_grp_init(const float* __restrict__ p
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const u64 g = groups[i];
     gk[i] = g;
-    pv[i] = (__float_as_uint(fmaxf(pctr[i], 0.0f)) << 1) | (labels[i] > 0.5f ? 1u : 0u);
+    pv[i] = (eval_key_bits(pctr[i]) << 1) | (labels[i] > 0.5f ? 1u : 0u);
     o |= g;
     na |= ~g;
   }

@@ -663,6 +663,22 @@ struct SynthArgs {                 // synthetic Criteo-shaped batch generator
 
 // Evaluation sums of a prediction set (Backend::eval_metrics): the inputs of
 // the reference's calculate_auc print (base.h:84-110).
+//
+// The order of the predictions, here and in GroupedEval, on both backends:
+// the sort key of a prediction p is the bit pattern of (p > 0 ? p : +0.0f),
+// compared as an unsigned integer, descending, stable in prediction order.
+// NaN, -0.0, 0.0 and every negative value (-inf included) are therefore one
+// tie class equal to +0.0 and rank last; +inf and values above 1 keep their
+// own bits.  A label is positive iff > 0.5f (a NaN label is negative).  The
+// logloss terms use p itself: for p outside (0, 1) log2_sum may be
+// non-finite, as in the reference's printer; ln_sum clips p first and is
+// finite for every p that is not NaN.
+XF_HD u32 eval_key_bits(float p) {
+  const float k = p > 0.0f ? p : 0.0f;
+  u32 b;
+  __builtin_memcpy(&b, &k, sizeof(b));
+  return b;
+}
 struct EvalMetrics {
   int64_t n = 0;          // predictions
   int64_t tp = 0;         // positives
@@ -680,10 +696,11 @@ struct EvalMetrics {
 //   n_g     rows, pos_g positive rows
 //   area2_g sum over (positive i, negative j) of g of 2*[p_i > p_j] + [p_i == p_j]
 //           (the Mann-Whitney count doubled, ties worth 1/2), compared on the
-//           float bits of fmaxf(p, 0).  Unlike EvalMetrics::area, which breaks
+//           key bits above (eval_key_bits).  Unlike EvalMetrics::area, which breaks
 //           ties by prediction order to match the reference's printer, it
 //           does not depend on the order of the rows.
-//   sump_g  sum of llrint(fmaxf(p, 0) * 2^32) (fixed point: order-free)
+//   sump_g  sum of llrint((p > 0 ? p : 0) * 2^32) (fixed point: order-free; a
+//           NaN or negative p adds 0)
 // A group is used iff 0 < pos_g < n_g.  gauc_num and cal_abs are double sums
 // over the groups in ascending key order (fixed, so identical run to run).
 constexpr u64 kNoGroup = ~0ull;

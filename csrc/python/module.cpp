@@ -580,6 +580,7 @@ PYBIND11_MODULE(_xflow_native, m) {
              d["tp"] = m.tp;
              d["area"] = m.area;
              d["log2_sum"] = m.log2_sum;
+             d["ln_sum"] = m.ln_sum;
              d["logloss_printed"] = r.logloss_printed;
              d["ln_logloss"] = r.ln_logloss;
              d["auc"] = r.auc;

@@ -39,8 +39,15 @@ def _engine(devname):
     return _engines[devname]
 
 
+def _key(p):
+    """p > 0 ? p : +0.0f -- the value both the order and the fixed-point sum use
+    (eval_key_bits, backend.h): NaN, -0.0 and negatives are +0.0."""
+    with np.errstate(invalid="ignore"):
+        return np.where(p > 0, p, np.float32(0)).astype(np.float32)
+
+
 def _bits(p):
-    return np.maximum(p, np.float32(0)).astype(np.float32).view(np.uint32).astype(np.int64)
+    return _key(p).view(np.uint32).astype(np.int64)
 
 
 def _sorted_order(p, g):
@@ -52,8 +59,9 @@ def _reference(p, y, g, brute=True):
     ascending key order, integers as Python-exact int64 / uint64 arrays."""
     n = len(p)
     b = _bits(p)
-    lab = y > 0.5
-    fx = np.rint(np.maximum(p, np.float32(0)).astype(np.float64) * 2.0 ** 32).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        lab = y > 0.5
+    fx = np.rint(_key(p).astype(np.float64) * 2.0 ** 32).astype(np.int64)
     ing = g != NOGROUP
     keys, rank = np.unique(g[ing], return_inverse=True)
     G = len(keys)
@@ -157,6 +165,32 @@ def _power_law_case(seed=11):
     return p[perm], y[perm], g[perm]
 
 
+OUTSIDE = (-0.0, 0.0, -0.5, -0.2, -np.inf, np.nan)
+OUTSIDE_KEY = np.uint64(0x7000000000000001)  # a group of such rows only
+
+
+def _outside_case(seed=13):
+    """Predictions that are not > 0 inside the groups: -0.0, 0.0, negatives,
+    -inf and NaN next to quantised p in (0, 1], in 40 groups over a tile
+    boundary, one group made of such rows only, and rows without a group."""
+    rng = np.random.default_rng(seed)
+    n = TILE + 500
+    keys = rng.integers(0, 1 << 62, 40, dtype=np.uint64)
+    assert len(np.unique(keys)) == 40
+    g = keys[rng.integers(0, 40, n)]
+    g[rng.random(n) < 0.03] = NOGROUP
+    special = np.array(OUTSIDE, np.float32)
+    p = np.where(rng.random(n) < 0.4, special[rng.integers(0, len(special), n)],
+                 np.round(rng.random(n) * 20) / 20).astype(np.float32)
+    g[:300] = OUTSIDE_KEY
+    p[:300] = special[np.arange(300) % len(special)]
+    y = (rng.random(n) < 0.4).astype(np.float32)
+    for v in special:  # bit for bit: -0.0 is not 0.0
+        assert (p.view(np.uint32) == v.view(np.uint32)).sum() > 50
+    perm = rng.permutation(n)
+    return p[perm], y[perm], g[perm]
+
+
 _cases = {}
 
 
@@ -179,6 +213,8 @@ def _case(name):
             g = rng.permutation(np.arange(3000, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15))
         elif name == "power_law":
             p, y, g = _power_law_case()
+        elif name == "outside":
+            p, y, g = _outside_case()
         else:
             raise KeyError(name)
         for a in (p, y, g):
@@ -188,11 +224,39 @@ def _case(name):
 
 
 @pytest.mark.parametrize("devname", DEVS)
-@pytest.mark.parametrize("name", ["empty", "one", "one_group", "singletons", "power_law"])
+@pytest.mark.parametrize("name", ["empty", "one", "one_group", "singletons", "power_law",
+                                  "outside"])
 def test_grouped_exact_integers_and_sums(devname, name):
     p, y, g, sc, tab = _case(name)
     r = _run(devname, p, y, g)
     _check(r, sc, tab)
+    if name == "outside":
+        # rows that are not > 0 tie with each other (a pair of them is worth 1
+        # in area2, whatever their values) and add 0 to sump
+        t = r["per_group"]
+        k = int(np.flatnonzero(t["key"] == OUTSIDE_KEY)[0])
+        assert t["n"][k] == 300 and 0 < t["pos"][k] < 300
+        assert int(t["area2"][k]) == int(t["pos"][k]) * int(300 - t["pos"][k])
+        assert t["sump"][k] == 0
+        with np.errstate(invalid="ignore"):
+            low = ~(p > 0)
+        for kk in (0, 7, 39):  # mixed groups: the same from the definition
+            rows = g == t["key"][kk] if t["key"][kk] != OUTSIDE_KEY else None
+            if rows is None:
+                continue
+            pos, neg = rows & (y > 0.5), rows & ~(y > 0.5)
+            a2 = 0
+            for i in np.flatnonzero(pos):
+                for j in np.flatnonzero(neg):
+                    if low[i] and low[j]:
+                        a2 += 1
+                    elif low[j] or (not low[i] and p[i] > p[j]):
+                        a2 += 2
+                    elif not low[i] and p[i] == p[j]:
+                        a2 += 1
+            assert int(t["area2"][kk]) == a2, kk
+            assert int(t["sump"][kk]) == int(np.rint(p[rows & ~low].astype(np.float64)
+                                                     * 2.0 ** 32).sum())
     if name == "one_group":
         assert len(np.unique(p)) == len(p) and sc["groups"] == 1
         m = _engine(devname).eval_metrics(torch.from_numpy(p.copy()).to(_dev(devname)),
@@ -264,6 +328,65 @@ def test_grouped_large_gpu():
     sc, tab = _reference(p, y, g, brute=False)
     assert tab["n"].max() > 2 * TILE and sc["groups"] > 40_000
     _check(_run("cuda", p, y, g), sc, tab)
+
+
+CHUNK = 256 * TILE  # rows (or runs) one round of the one-workgroup scans over the tiles covers
+
+
+@pytest.mark.gpu
+def test_grouped_chunks_gpu():
+    """n = 2 097 153 rows (513 tiles) in 120 000 power-law groups with ties:
+    past the point where the one-workgroup scans over the tiles (k_rs_scan of
+    the sort passes, k_gr_carry, k_gr_carry64) take a second and a third round
+    of 256 tiles with a running carry.  The smallest n that reaches each loop:
+    the scans over row tiles at n = 256 * 4096 + 1 = 1 048 577; the run-level
+    scan (k_gr_runs / k_gr_carry64 / k_gr_runscan tile the RUNS by 4096) needs
+    more than 256 * 4096 tie runs -- this case has 1.35 M (0.65 a row); the
+    least n with that many runs is 1 048 577 rows, each a run of its own;
+    k_gr_groups has no such loop (one lane per group, 4096 groups per
+    workgroup, partials summed in order by k_gr_final): more than one
+    workgroup of it from 4097 groups on."""
+    rng = np.random.default_rng(37)
+    n, G = 2 * CHUNK + 1, 120_000
+    keys = np.unique(rng.integers(0, 1 << 64, G + 16, dtype=np.uint64))
+    keys = rng.permutation(keys[keys != NOGROUP])[:G]
+    gi = np.minimum((G * rng.random(n) ** 3).astype(np.int64), G - 1)  # power-law sizes
+    g = keys[gi]
+    g[rng.random(n) < 0.01] = NOGROUP
+    p = np.clip(np.round(rng.random(n) * 50) / 50, 0.02, 0.98).astype(np.float32)
+    y = (rng.random(n) < 0.3).astype(np.float32)
+    sc, tab = _reference(p, y, g, brute=False)
+    o = _sorted_order(p, g)
+    gs, bs = g[o], _bits(p)[o]
+    runs = 1 + int(((gs[1:] != gs[:-1]) | (bs[1:] != bs[:-1])).sum())
+    assert (n + TILE - 1) // TILE > 512
+    assert runs / TILE > 256, runs
+    assert sc["groups"] / TILE > 1 and 0.005 * n < sc["n_nogroup"] < 0.015 * n
+    assert gs[CHUNK - 1] == gs[CHUNK] != NOGROUP, "no group straddles row 256 * 4096"
+    assert bs[CHUNK - 1] == bs[CHUNK], "no tie run straddles row 256 * 4096"
+    _check(_run("cuda", p, y, g), sc, tab)
+
+
+@pytest.mark.gpu
+def test_one_group_past_a_chunk_gpu():
+    """All n = 1 048 577 rows (257 tiles) in one group: area2 is the tie-aware
+    pair count of the whole set (rank-formula reference), and with all p
+    distinct it is twice eval_metrics' area."""
+    rng = np.random.default_rng(41)
+    n = CHUNK + 1
+    g = np.full(n, 0x0123456789ABCDEF, np.uint64)
+    y = (rng.random(n) < 0.3).astype(np.float32)
+    tied = np.clip(np.round(rng.random(n) * 50) / 50, 0.02, 0.98).astype(np.float32)
+    distinct = ((rng.permutation(n) + 1) / 2.0 ** 21).astype(np.float32)  # exact in float32
+    assert len(np.unique(distinct)) == n and distinct.min() > 0 and distinct.max() < 1
+    for p in (tied, distinct):
+        sc, tab = _reference(p, y, g, brute=False)
+        assert sc["groups"] == 1 and tab["n"][0] == n
+        r = _run("cuda", p, y, g)
+        _check(r, sc, tab)
+    dev = _dev("cuda")
+    m = _engine("cuda").eval_metrics(torch.from_numpy(distinct).to(dev), torch.from_numpy(y).to(dev))
+    assert int(r["per_group"]["area2"][0]) == 2 * m["area"] and m["tp"] == int(tab["pos"][0])
 
 
 # ---- row_group_keys ---------------------------------------------------------

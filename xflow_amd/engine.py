@@ -591,7 +591,9 @@ class Engine:
         """AUC / logloss of predictions on this engine's device, computed there
         (GPU: radix sort + rank sums; only scalars come back).  Returns the
         reference's printed line (base.h:84-110) with auc / logloss_printed /
-        ln_logloss / n / tp."""
+        ln_logloss / n / tp, and the exact sums area / log2_sum / ln_sum.  The
+        predictions are ranked by the bits of ``p > 0 ? p : +0`` (descending,
+        stable): NaN, zeros and negative values tie and rank last."""
         if pctr.device != self.device or labels.device != self.device:
             raise ValueError("eval_metrics: tensors must be on the engine's device")
         p = pctr.contiguous().float()
