@@ -467,6 +467,44 @@ class CpuBackend final : public Backend {
       if (s.row_ptr) a.row_ptr[i + 1] = (int32_t)(o += sp.len);
     }
   }
+  void cross_rows(const CrossArgs& a) override {
+    check_cross_args(a);
+    BatchView s = a.src;
+    const CrossSpec& x = a.spec;
+    const int C = x.n;
+    std::vector<u64> wide;  // compact u32 keys: the operands are the zero-extended keys
+    if (a.key_bytes == 4) {
+      const u32* k32 = reinterpret_cast<const u32*>(s.keys);
+      wide.assign(k32, k32 + s.nnz);
+      s.keys = wide.data();
+    }
+    const ShufflePerm pi = shuffle_perm((u64)s.rows, a.seed);
+    const int64_t stride = cross_out_stride(a);
+    const bool in_place = a.keys == a.src.keys;
+    if (s.row_ptr) a.row_ptr[0] = s.row_ptr[0];
+    for (int64_t i = 0; i < s.rows; ++i) {
+      const int64_t p = a.has_seed ? (int64_t)pi.at((u64)i) : i;
+      if (a.labels != s.labels) a.labels[i] = s.labels[p];
+      const RowSpan sp = row_span(s, p);
+      const int64_t W = sp.len + C;
+      const int64_t o = s.row_ptr ? (int64_t)s.row_ptr[i] + (int64_t)C * i : 0;
+      auto to = [&](int64_t j) {
+        return s.row_ptr ? o + j : (a.field_major_out ? j * stride + i : i * W + j);
+      };
+      if (!in_place)
+        for (int j = 0; j < sp.len; ++j) {
+          a.keys[to(j)] = s.keys[sp.at(j)];
+          if (a.fgid) a.fgid[to(j)] = s.fgid[sp.at(j)];
+        }
+      u64 ck[kMaxCrosses];
+      row_cross_keys(s, p, x, ck);
+      for (int c = 0; c < C; ++c) {
+        a.keys[to(sp.len + c)] = ck[c];
+        if (a.fgid) a.fgid[to(sp.len + c)] = x.fgid_base + c;
+      }
+      if (s.row_ptr) a.row_ptr[i + 1] = (int32_t)(s.row_ptr[i + 1] + (int64_t)C * (i + 1));
+    }
+  }
   int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                        int64_t max_rows) override {
     const int W = t.L.stride - 2;

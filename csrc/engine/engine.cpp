@@ -297,6 +297,14 @@ void Engine::shuffle_rows(const BatchView& src, u64 seed, u64* keys, int32_t* fg
   be_->shuffle_rows(a);
 }
 
+void Engine::cross_rows(const CrossArgs& a) {
+  const int64_t out_nnz = a.src.nnz + (int64_t)(a.spec.n > 0 ? a.spec.n : 0) * a.src.rows;
+  if (a.src.rows > cfg_.max_rows) throw std::invalid_argument("cross_rows: batch rows exceed max_rows");
+  if (out_nnz > cfg_.max_nnz)
+    throw std::invalid_argument("cross_rows: nnz + crosses * rows exceeds max_nnz");
+  be_->cross_rows(a);  // (check_cross_args: the spec, the layouts, int32)
+}
+
 void Engine::count_records(bool on) {
   if (on && !rec_count_) rec_count_.alloc_zero(*be_, 1);
   rec_on_ = on;

@@ -257,6 +257,12 @@ class HipBackend final : public Backend {
     scan_u32(a.len, reinterpret_cast<u32*>(a.row_ptr), nullptr, a.src.rows);
     hip::launch_shuffle_gather(a, stream_);
   }
+  void cross_rows(const CrossArgs& a) override {
+    check_cross_args(a);
+    if (a.src.row_ptr) hip::launch_cross_csr(a, stream_);
+    else if (a.src.col_stride > 0) hip::launch_cross_cols(a, stream_);
+    else hip::launch_cross_fixed(a, stream_);
+  }
   int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                        int64_t max_rows) override {
     hip::launch_table_export(t, keys_out, words_out, max_rows, counter_, stream_);

@@ -69,6 +69,12 @@ void launch_shuffle_fixed(const ShuffleArgs& a, hipStream_t st);
 void launch_shuffle_len(const ShuffleArgs& a, hipStream_t st);
 void launch_shuffle_gather(const ShuffleArgs& a, hipStream_t st);
 
+// kernels_cross.hip (CrossArgs, one launch each): a row-major fixed-width
+// source, a field-major one, a CSR one
+void launch_cross_fixed(const CrossArgs& a, hipStream_t st);
+void launch_cross_cols(const CrossArgs& a, hipStream_t st);
+void launch_cross_csr(const CrossArgs& a, hipStream_t st);
+
 // kernels_model.hip (the kernels: kernels_lr / _fm / _mvm / _reduce / _reduce_vec .hip)
 void launch_forward_backward(const FwdArgs& a, hipStream_t st);
 void launch_slice_masks(const BatchView& b, const u32* pos, u32* tmask, hipStream_t st);

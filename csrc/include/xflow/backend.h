@@ -741,6 +741,113 @@ XF_HD u64 row_group_key(const BatchView& b, int64_t r, int field) {
   return kNoGroup;
 }
 
+// Feature crosses (Backend::cross_rows, docs/DESIGN.md §9).  A cross is an
+// ordered tuple of 2..kMaxCrossArity field ids; a spec holds up to kMaxCrosses
+// of them.  Every row of the batch gains exactly spec.n keys, appended behind
+// its own entries in spec order: cross c of row r is
+//   cross_key(spec.field[c], ops, spec.arity[c]),  ops[i] = row_group_key(src, r, spec.field[c][i])
+// (common.h; the operand rule of row_group_keys: with fgid the key of the
+// row's first occurrence of that field id, without fgid -- fixed width only --
+// occurrence field[c][i] of the row, kNoGroup = ~0 when the row has none: a
+// missing operand is hashed as ~0, not skipped, and a raw key equal to ~0
+// reads as missing).  The operands are the batch's raw keys (compact u32 keys
+// zero-extended).  Passed to kernels by value.
+constexpr int kMaxCrosses = 16;
+constexpr int kMaxCrossArity = 4;
+constexpr int kCrossMaxFields = 64;  // fixed width, row-major source: F + C (the HIP tile)
+struct CrossSpec {
+  int n = 0;                                       // crosses C
+  int arity[kMaxCrosses] = {};                     // 2..kMaxCrossArity
+  int32_t field[kMaxCrosses][kMaxCrossArity] = {};
+  int32_t fgid_base = 0;                           // cross c's field id in the fgid output
+};
+// The source (all pointers backend memory; nothing syncs, the source is left
+// as it is) and what comes out:
+//   fixed width, row-major (col_stride == 0; keys of key_bytes 4 or 8): width
+//     F becomes F + C <= kCrossMaxFields, field-major ([F + C][col_stride_out],
+//     the layout the step reads) or row-major.  has_seed: destination row i is
+//     source row shuffle_index(i, rows, seed) -- Backend::shuffle_rows fused in.
+//   fixed width, field-major (col_stride > 0; u64 keys, no fgid, no seed):
+//     field-major out; keys == src.keys with the same stride is the in-place
+//     form -- only columns F .. F + C - 1 are written, behind the input's.
+//   CSR (u64 keys, needs fgid, no seed: shuffle_rows first): row_ptr[r] =
+//     src.row_ptr[r] + C * r for r = 0 .. rows, written too.
+// fgid (optional, needs src.fgid): the entries' field ids in the output's
+// layout, cross c as spec.fgid_base + c.  Labels are copied (permuted with a
+// seed) unless labels == src.labels.
+struct CrossArgs {
+  BatchView src;
+  int key_bytes = 8;
+  CrossSpec spec;
+  bool has_seed = false;
+  u64 seed = 0;
+  u64* keys = nullptr;             // out [nnz + C * rows] ([F + C][col_stride_out])
+  int32_t* fgid = nullptr;         // out, optional
+  float* labels = nullptr;         // out [rows]
+  int32_t* row_ptr = nullptr;      // out [rows + 1] (CSR)
+  bool field_major_out = false;
+  int64_t col_stride_out = 0;      // field-major out: 0 => rows (field-major source: its stride)
+};
+inline int64_t cross_out_stride(const CrossArgs& a) {
+  return a.col_stride_out > 0 ? a.col_stride_out
+                              : (a.src.col_stride > 0 ? a.src.col_stride : a.src.rows);
+}
+// what both backends refuse
+inline void check_cross_args(const CrossArgs& a) {
+  const BatchView& s = a.src;
+  const CrossSpec& x = a.spec;
+  if (x.n < 1 || x.n > kMaxCrosses) throw std::invalid_argument("cross_rows: 1 to 16 crosses");
+  for (int c = 0; c < x.n; ++c) {
+    if (x.arity[c] < 2 || x.arity[c] > kMaxCrossArity)
+      throw std::invalid_argument("cross_rows: a cross has 2 to 4 fields");
+    for (int i = 0; i < x.arity[c]; ++i)
+      if (x.field[c][i] < 0) throw std::invalid_argument("cross_rows: a negative field id");
+  }
+  if (s.rows < 0 || s.nnz < 0 || s.nnz + (int64_t)x.n * s.rows > 0x7fffffffll)
+    throw std::invalid_argument("cross_rows: bad batch size (nnz + crosses * rows must fit int32)");
+  // (a batch without entries may come without arrays)
+  if (a.fgid && !s.fgid && s.nnz > 0) throw std::invalid_argument("cross_rows: field ids out need field ids in");
+  if (s.row_ptr) {
+    if (!s.fgid && s.nnz > 0)
+      throw std::invalid_argument("cross_rows: a CSR batch needs its field ids (fgid)");
+    if (a.key_bytes != 8) throw std::invalid_argument("cross_rows: CSR keys are 8 bytes");
+    if (a.field_major_out) throw std::invalid_argument("cross_rows: a CSR batch stays CSR");
+    if (a.has_seed) throw std::invalid_argument("cross_rows: a CSR batch is shuffled by shuffle_rows first");
+    if (!a.row_ptr) throw std::invalid_argument("cross_rows: a CSR batch needs row_ptr out");
+  } else {
+    if (s.nnz_per_row <= 0 || s.nnz != s.rows * s.nnz_per_row)
+      throw std::invalid_argument("cross_rows: fixed width needs nnz == rows * nnz_per_row");
+    if (s.col_stride > 0) {
+      if (s.col_stride < s.rows) throw std::invalid_argument("cross_rows: col_stride < rows");
+      if (s.fgid || a.has_seed || a.key_bytes != 8 || !a.field_major_out)
+        throw std::invalid_argument("cross_rows: a field-major source has u64 keys, no fgid and "
+                                    "no seed, and stays field-major");
+      if (s.rows > 0 && a.keys == s.keys && cross_out_stride(a) != s.col_stride)
+        throw std::invalid_argument("cross_rows: in place needs the source's col_stride");
+    } else {
+      if (a.key_bytes != 8 && a.key_bytes != 4)
+        throw std::invalid_argument("cross_rows: 4- or 8-byte keys");
+      if (s.rows > 0 && s.nnz_per_row + x.n > kCrossMaxFields)
+        throw std::invalid_argument("cross_rows: fields + crosses exceed 64");
+      if (s.rows > 0 && (const void*)a.keys == (const void*)s.keys)
+        throw std::invalid_argument("cross_rows: a row-major source is not crossed in place");
+    }
+    if (a.field_major_out && cross_out_stride(a) < s.rows)
+      throw std::invalid_argument("cross_rows: col_stride_out < rows");
+  }
+  if ((s.rows > 0 && (!s.labels || !a.labels)) || (s.nnz > 0 && !s.keys) ||
+      (s.rows > 0 && !a.keys))
+    throw std::invalid_argument("cross_rows: null array");
+}
+// one row's cross keys (both backends' definition; out[c], c < spec.n)
+XF_HD void row_cross_keys(const BatchView& b, int64_t r, const CrossSpec& x, u64* out) {
+  for (int c = 0; c < x.n; ++c) {
+    u64 ops[kMaxCrossArity];
+    for (int i = 0; i < x.arity[c]; ++i) ops[i] = row_group_key(b, r, x.field[c][i]);
+    out[c] = cross_key(x.field[c], ops, x.arity[c]);
+  }
+}
+
 class Backend {
  public:
   virtual ~Backend() = default;
@@ -888,6 +995,8 @@ class Backend {
   virtual void unpack_block(const UnpackArgs& a) = 0;
   // the batch with its rows permuted by shuffle_index (see ShuffleArgs)
   virtual void shuffle_rows(const ShuffleArgs& a) = 0;
+  // the batch with spec.n cross keys appended to every row (see CrossArgs)
+  virtual void cross_rows(const CrossArgs& a) = 0;
   // count occupied slots / dump table rows (checkpointing); returns rows written
   virtual int64_t table_export(const TableView& t, u64* keys_out, u32* words_out,
                                int64_t max_rows) = 0;

@@ -88,6 +88,23 @@ XF_HD ShufflePerm shuffle_perm(u64 n, u64 seed) {
 // pi(i): the source row of destination row i
 XF_HD u64 shuffle_index(u64 i, u64 n, u64 seed) { return shuffle_perm(n, seed).at(i); }
 
+// Feature crosses (Backend::cross_rows, docs/DESIGN.md §9): the key of the
+// cross of m fields (2..4, in the spec's order) whose operands in a row are
+// ops[i] -- the row's raw key of field fields[i], or ~0 when the row has none:
+// a missing operand is hashed like any other value, so every row gets a key.
+// The salt keeps cross keys apart from every other use of fmix64 here; the
+// arity and the field ids are hashed in, so 3x7, 7x3 and 3x7x1 never share
+// keys by construction.  Mirrored in xflow_amd/engine.py (cross_keys).
+constexpr u64 kCrossSalt = 0xC3A5C85C97CB3127ull;
+XF_HD u64 cross_key(const int32_t* fields, const u64* ops, int m) {
+  u64 h = fmix64(kCrossSalt + (u64)m);
+  for (int i = 0; i < m; ++i) {
+    h = fmix64(h ^ (u64)(u32)fields[i]);
+    h = fmix64(h ^ ops[i]);
+  }
+  return sanitize_key(h);
+}
+
 // Synthetic "historic" key i of a prefilled table (Backend::table_prefill):
 // bit 62 set, so it never equals a hashed feature below 2^62.
 XF_HD u64 prefill_key(u64 seed, u64 i) {

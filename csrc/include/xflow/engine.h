@@ -327,6 +327,12 @@ class Engine {
   void shuffle_rows(const BatchView& src, u64 seed, u64* keys, int32_t* fgid, float* labels,
                     int32_t* row_ptr, bool field_major_out, int key_bytes = 8);
 
+  // Feature crosses (Backend::cross_rows, CrossArgs): every row of the source
+  // gains a.spec.n cross keys.  rows and nnz + crosses * rows must lie within
+  // max_rows / max_nnz (and int32).  Queued on the engine's stream: one
+  // launch, no allocation, no host sync.
+  void cross_rows(const CrossArgs& a);
+
   // ---- stats / introspection -------------------------------------------
   // which = 0: training forward passes, 1: eval_step passes.
   LossStats read_stats(bool reset, int which = 0);

@@ -632,6 +632,37 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("batch"), py::arg("seed"), py::arg("keys"), py::arg("fgid"), py::arg("labels"),
            py::arg("row_ptr"), py::arg("field_major_out"), py::arg("key_bytes") = 8,
            py::call_guard<py::gil_scoped_release>())
+      .def("cross_rows",
+           [](Engine& e, const BatchView& b, const std::vector<std::vector<int32_t>>& crosses,
+              int32_t fgid_base, py::object seed, uintptr_t keys, uintptr_t fgid, uintptr_t labels,
+              uintptr_t row_ptr, bool field_major_out, int key_bytes, int64_t col_stride_out) {
+             CrossArgs a;
+             a.src = b;
+             a.key_bytes = key_bytes;
+             if (crosses.size() > (size_t)kMaxCrosses)
+               throw std::invalid_argument("cross_rows: 1 to 16 crosses");
+             a.spec.n = (int)crosses.size();
+             for (size_t c = 0; c < crosses.size(); ++c) {
+               if (crosses[c].size() > (size_t)kMaxCrossArity)
+                 throw std::invalid_argument("cross_rows: a cross has 2 to 4 fields");
+               a.spec.arity[c] = (int)crosses[c].size();
+               for (size_t i = 0; i < crosses[c].size(); ++i) a.spec.field[c][i] = crosses[c][i];
+             }
+             a.spec.fgid_base = fgid_base;
+             a.has_seed = !seed.is_none();
+             if (a.has_seed) a.seed = seed.cast<uint64_t>();
+             a.keys = P<u64>(keys);
+             a.fgid = P<int32_t>(fgid);
+             a.labels = P<float>(labels);
+             a.row_ptr = P<int32_t>(row_ptr);
+             a.field_major_out = field_major_out;
+             a.col_stride_out = col_stride_out;
+             py::gil_scoped_release nogil;
+             e.cross_rows(a);
+           },
+           py::arg("batch"), py::arg("crosses"), py::arg("fgid_base"), py::arg("seed"),
+           py::arg("keys"), py::arg("fgid"), py::arg("labels"), py::arg("row_ptr"),
+           py::arg("field_major_out"), py::arg("key_bytes") = 8, py::arg("col_stride_out") = 0)
       .def("download_small",
            [](Engine& e, uintptr_t dst, uintptr_t src, size_t bytes) {
              e.download_small(P<void>(dst), P<const void>(src), bytes);

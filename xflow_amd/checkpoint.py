@@ -3,7 +3,10 @@ reference keeps weights only in server RAM and loses them at exit,
 src/optimizer/ftrl.h:84,151).
 
 Layout of ``<dir>/``:
-  meta.json                      model/optimizer config, world size, epoch, step
+  meta.json                      model/optimizer config, world size, epoch, step;
+                                 "crosses" / "cross_field_base" when the table
+                                 was trained with feature crosses (cross_meta;
+                                 absent: none)
   shard-<rank>-of-<world>.xftb   native binary shard (csrc/engine/engine.cpp
                                  Engine::save): header + keys + state words
   admit-<rank>-of-<world>.xfad   only with feature admission on
@@ -237,6 +240,37 @@ def _check_header(engine, path: str, hdr) -> None:
 def load_meta(ckpt_dir: str) -> dict:
     with open(os.path.join(ckpt_dir, "meta.json")) as f:
         return json.load(f)
+
+
+def cross_meta(crosses, field_base) -> dict:
+    """meta.json's record of the feature crosses a table was trained with
+    (TrainConfig.crosses): ``crosses`` (lists of field ids) and
+    ``cross_field_base`` (-1: the crosses carry no field id).  Nothing when
+    there are none -- the file of an uncrossed model is what it always was."""
+    if not crosses:
+        return {}
+    return {"crosses": [[int(f) for f in c] for c in crosses],
+            "cross_field_base": -1 if field_base is None else int(field_base)}
+
+
+def crosses_of(meta: dict):
+    """(crosses as a list of tuples, field base or None) of a checkpoint's
+    meta.json; absent keys (every checkpoint written before crosses existed):
+    no crosses."""
+    crosses = [tuple(int(f) for f in c) for c in meta.get("crosses") or []]
+    base = int(meta.get("cross_field_base", -1))
+    return crosses, (base if crosses and base >= 0 else None)
+
+
+def check_crosses_match(meta: dict, crosses, field_base, where: str = "checkpoint") -> None:
+    """A table holds the keys of the crosses it was trained with: continuing
+    or serving it under another spec would look up keys it never saw."""
+    saved, sbase = crosses_of(meta)
+    now = [tuple(int(f) for f in c) for c in crosses or []]
+    nbase = field_base if now else None
+    if saved != now or sbase != nbase:
+        raise ValueError(f"{where}: trained with crosses {saved} (field base {sbase}), the "
+                         f"running configuration has {now} (field base {nbase})")
 
 
 def _load_admit(engine, ckpt_dir: str, rank: int, world: int, meta: dict) -> None:

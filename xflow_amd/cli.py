@@ -17,7 +17,7 @@ import sys
 import torch
 
 from xflow_amd.config import (EngineConfig, ModelConfig, OptimConfig, TrainConfig,
-                              MODEL_NAMES, model_kind)
+                              MODEL_NAMES, model_kind, parse_crosses)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -88,6 +88,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--shuffle-seed", type=int, default=0,
                     help="--shuffle: the run's seed (a block's order depends only on it, the "
                          "epoch, the block and the rank)")
+    ap.add_argument("--cross", default="",
+                    help="feature crosses computed on the device: 3x7,1x2x5 adds to every row one "
+                         "key per cross, hashed from its keys of those field ids in that order "
+                         "(2..4 fields, at most 16 crosses; a missing field still gives a key); "
+                         "not for packed shards or --serial-slices")
+    ap.add_argument("--cross-field-base", type=int, default=-1,
+                    help="--cross: cross c enters the model as field id N + c (required for MVM, "
+                         "whose products run over field ids)")
     ap.add_argument("--csr-only", action="store_true",
                     help="train fixed-width blocks through the CSR path as well")
     ap.add_argument("--block-rows", type=int, default=0,
@@ -128,6 +136,7 @@ def config_from_args(a) -> TrainConfig:
         threads=a.threads, train_block_bytes=a.train_block_bytes, block_rows=a.block_rows,
         resident=a.resident, fixed_width=not a.csr_only, gpu_parse=a.gpu_parse,
         shuffle=a.shuffle, shuffle_seed=a.shuffle_seed,
+        crosses=parse_crosses(a.cross), cross_field_base=a.cross_field_base,
         test_block_bytes=a.test_block_bytes, serial_slices=a.serial_slices,
         keep_remainder=a.keep_remainder, mvm_predict_compat=a.mvm_predict_compat,
         init_push=not a.no_init_push, pred_dir=a.pred_dir, write_pred=not a.no_pred_file,

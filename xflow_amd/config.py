@@ -41,6 +41,47 @@ def model_kind(m) -> int:
     return MODEL_KINDS[m]
 
 
+MAX_CROSSES = 16       # kMaxCrosses, csrc/include/xflow/backend.h
+MAX_CROSS_ARITY = 4    # kMaxCrossArity
+
+
+def check_crosses(crosses) -> list:
+    """``crosses`` as a list of tuples of ints, or ValueError: 1..16 crosses of
+    2..4 distinct non-negative field ids each, no cross twice (3x7 and 7x3 are
+    two crosses: the order is part of the feature)."""
+    out = [tuple(int(f) for f in c) for c in crosses]
+    if not 1 <= len(out) <= MAX_CROSSES:
+        raise ValueError(f"crosses: 1 to {MAX_CROSSES} crosses, got {len(out)}")
+    for c in out:
+        if not 2 <= len(c) <= MAX_CROSS_ARITY:
+            raise ValueError(f"cross {c}: a cross has 2 to {MAX_CROSS_ARITY} fields")
+        if min(c) < 0 or max(c) >= 1 << 31:
+            raise ValueError(f"cross {c}: field ids are non-negative int32")
+        if len(set(c)) != len(c):
+            raise ValueError(f"cross {c}: a field is repeated")
+    if len(set(out)) != len(out):
+        raise ValueError(f"crosses {out}: a cross is given twice")
+    return out
+
+
+def parse_crosses(text: str) -> list:
+    """``--cross 3x7,1x2x5`` -> [(3, 7), (1, 2, 5)] (check_crosses' rules; an
+    empty string: no crosses)."""
+    text = (text or "").strip()
+    if not text:
+        return []
+    try:
+        raw = [tuple(int(f) for f in c.split("x")) for c in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--cross {text!r}: crosses are field ids joined by 'x', separated by "
+                         f"commas (3x7,1x2x5)") from None
+    return check_crosses(raw)
+
+
+def format_crosses(crosses) -> str:
+    return ",".join("x".join(str(f) for f in c) for c in crosses)
+
+
 @dataclass
 class ModelConfig:
     kind: str = "lr"             # lr | fm | mvm
@@ -176,6 +217,14 @@ class TrainConfig:
     # predict pass, grouping the test rows by their key of this field id
     # (Engine.eval_grouped); -1: off
     gauc_field: int = -1
+    # feature crosses computed on the device (Engine.cross_batch, docs/DESIGN.md
+    # §9): tuples of 2..4 field ids; every row gains one key per cross, hashed
+    # from its raw keys of those fields (a missing field still gives a key).
+    # cross_field_base: cross c enters the model as field id base + c -- MVM
+    # needs it (its products run over field ids); -1: LR / FM, which drop the
+    # field ids after the cross
+    crosses: list = field(default_factory=list)
+    cross_field_base: int = -1
     metrics_file: str = ""
     async_p2p: bool = False      # lock-step staleness-k steps, pushes riding the next exchange
     # the asynchronous parameter server (parallel/async_ps.py): per-rank server

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from xflow_amd import native
-from xflow_amd.config import EngineConfig, ModelConfig, OptimConfig
+from xflow_amd.config import EngineConfig, ModelConfig, OptimConfig, check_crosses
 
 
 @dataclass
@@ -124,6 +124,51 @@ def shuffle_permutation(n: int, seed: int) -> np.ndarray:
     [0, n) (shuffle_index, csrc/include/xflow/common.h) computed by the
     native host function both backends share; the seed is taken modulo 2^64."""
     return native.load().shuffle_permutation(int(n), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+CROSS_SALT = 0xC3A5C85C97CB3127
+_M64 = (1 << 64) - 1
+
+
+def _fmix64(h: int) -> int:
+    h &= _M64
+    h ^= h >> 33
+    h = (h * 0xFF51AFD7ED558CCD) & _M64
+    h ^= h >> 33
+    h = (h * 0xC4CEB9FE1A85EC53) & _M64
+    h ^= h >> 33
+    return h
+
+
+def cross_keys(fields, ops) -> np.ndarray:
+    """The definition of a cross key (cross_key, csrc/include/xflow/common.h)
+    in Python ints: ``fields`` the m crossed field ids in order, ``ops`` a
+    [rows, m] array (or one row) of the rows' raw u64 keys of those fields,
+    all ones (2^64 - 1) where a row has none -- a missing operand is hashed,
+    not skipped.  Returns uint64 [rows]; the all-ones key is remapped to
+    2^64 - 2 like every key (sanitize_key)."""
+    fields = [int(f) for f in fields]
+    if isinstance(ops, np.ndarray):  # (int64 bit patterns, as batches hold them, are u64)
+        a = ops if ops.dtype == np.uint64 else ops.astype(np.int64).view(np.uint64)
+    else:
+        flat = np.array(ops, dtype=object).reshape(-1)
+        a = np.array([int(v) & _M64 for v in flat], dtype=np.uint64)
+    a = a.reshape(-1, len(fields))
+    out = np.empty(len(a), dtype=np.uint64)
+    h0 = _fmix64(CROSS_SALT + len(fields))
+    for r, row in enumerate(a.tolist()):
+        h = h0
+        for f, v in zip(fields, row):
+            h = _fmix64(h ^ (f & 0xFFFFFFFF))
+            h = _fmix64(h ^ v)
+        out[r] = sanitize_key(h)
+    return out
+
+
+def sanitize_key(k: int) -> int:
+    """The all-ones key is the tables' empty-slot mark: it is stored as
+    2^64 - 2 (sanitize_key, csrc/include/xflow/common.h)."""
+    return _M64 - 1 if k == _M64 else k
 
 
 def _device_index(device: torch.device) -> int:
@@ -695,6 +740,66 @@ class Engine:
                              batch.keys.element_size())
         return Batch(keys=keys, labels=labels, row_ptr=row_ptr, fgid=fgid,
                      nnz_per_row=batch.nnz_per_row, slice_rows=batch.slice_rows, field_major=fm)
+
+    def cross_batch(self, batch: Batch, crosses, seed: int | None = None,
+                    field_major: bool | None = None, fgid_base: int | None = None) -> Batch:
+        """``batch`` with one cross key per cross appended to every row, as new
+        tensors, computed on the device (Backend::cross_rows,
+        csrc/hip/kernels_cross.hip).  ``crosses``: tuples of 2..4 field ids
+        (check_crosses).  Cross c of a row is ``cross_keys(crosses[c], ops)``
+        with ops the row's raw keys of those fields by the rule of
+        ``row_group_keys`` -- with fgid the first occurrence of the field id,
+        without it (fixed width) the occurrence's index, all ones when the row
+        has none: a missing field still gives a key.  A fixed-width batch of
+        width F comes out with width F + C (at most 64 from a row-major
+        source), field-major unless ``field_major`` is False; a field-major
+        source (no fgid) stays field-major; a CSR batch (needs fgid) stays CSR.
+        ``seed``: the rows are also permuted as ``shuffle_batch(batch, seed)``
+        does, in the same pass for fixed-width batches.  The result carries
+        field ids only when ``fgid_base`` is given (the batch needs them
+        then): cross c gets ``fgid_base + c``.  Compact u32 keys come out as
+        u64; labels and slice_rows carry over."""
+        batch.check(self.device, compact_ok=True)
+        X = check_crosses(crosses)
+        C = len(X)
+        fixed = batch.row_ptr is None
+        fm = fixed if field_major is None else bool(field_major)
+        if fm and not fixed:
+            raise ValueError("cross_batch: only fixed-width batches have a field-major form")
+        if fgid_base is not None and batch.fgid is None:
+            raise ValueError("cross_batch: fgid_base needs a batch with field ids")
+        if not fixed and batch.fgid is None:
+            raise ValueError("cross_batch: a CSR batch needs its field ids (fgid)")
+        rows, F, dev = batch.rows, batch.nnz_per_row, self.device
+        if rows > self.cfg.max_rows or batch.nnz + C * rows > self.cfg.max_nnz:
+            raise ValueError("cross_batch: the crossed batch exceeds max_rows / max_nnz")
+        if batch.field_major:
+            if batch.fgid is not None or seed is not None or not fm:
+                raise ValueError("cross_batch: a field-major source has no fgid, takes no seed "
+                                 "and stays field-major")
+        elif fixed and F + C > 64:
+            raise ValueError(f"cross_batch: fields + crosses exceed 64 ({F} + {C})")
+        if seed is not None:
+            seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            if not fixed:  # CSR: the shuffle's three launches, then the cross
+                batch, seed = self.shuffle_batch(batch, seed), None
+        if not fixed and batch.keys.dtype == torch.int32:
+            batch = Batch(keys=widen_keys(batch.keys), labels=batch.labels, row_ptr=batch.row_ptr,
+                          fgid=batch.fgid, slice_rows=batch.slice_rows)
+        keys = torch.empty(batch.nnz + C * rows, dtype=torch.int64, device=dev)
+        labels = torch.empty(rows, dtype=torch.float32, device=dev)
+        fgid = (torch.empty(batch.nnz + C * rows, dtype=torch.int32, device=dev)
+                if fgid_base is not None else None)
+        row_ptr = None if fixed else torch.empty(rows + 1, dtype=torch.int32, device=dev)
+        self._sync_stream()
+        self._e.cross_rows(batch.view(), [list(c) for c in X],
+                           int(fgid_base) if fgid_base is not None else 0, seed, keys.data_ptr(),
+                           fgid.data_ptr() if fgid is not None else 0, labels.data_ptr(),
+                           row_ptr.data_ptr() if row_ptr is not None else 0, fm,
+                           batch.keys.element_size())
+        return Batch(keys=keys, labels=labels, row_ptr=row_ptr, fgid=fgid,
+                     nnz_per_row=F + C if fixed else 0, slice_rows=batch.slice_rows,
+                     field_major=fm)
 
     def export_table(self):
         self._sync_stream()

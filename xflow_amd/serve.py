@@ -64,6 +64,9 @@ class Predictor:
         self.model = _fields(ModelConfig, meta["model"])
         self.optim = _fields(OptimConfig, meta["optim"])
         self.meta = meta
+        # the feature crosses the model was trained with (absent: none): every
+        # request is crossed the same way before it is scored
+        self.crosses, self.cross_field_base = checkpoint.crosses_of(meta)
         # (key counts from the shard headers: nothing else is read twice; a
         # delta version: its full base's shards plus every delta's of its
         # chain, an upper bound -- a delta repeats keys its bases hold)
@@ -76,7 +79,8 @@ class Predictor:
         self.max_rows = int(max_rows)
         self.engine = Engine(self.model, self.optim,
                              EngineConfig(table_log2_cap=lg, max_rows=self.max_rows,
-                                          max_nnz=self.max_rows * int(max_nnz_per_row),
+                                          max_nnz=self.max_rows * (int(max_nnz_per_row)
+                                                                   + len(self.crosses)),
                                           table_grow=False),
                              device=device)
         checkpoint.load(self.engine, self.ckpt, 0, 1)
@@ -95,6 +99,10 @@ class Predictor:
         if rows < 0 or row_ptr[0] != 0 or row_ptr[-1] != len(keys):
             raise ValueError("row_ptr must hold rows+1 offsets from 0 to len(keys)")
         if fgid is None:
+            if self.crosses:
+                raise ValueError("this model was trained with feature crosses "
+                                 f"{self.crosses}: their operands are looked up by field id, so "
+                                 "give the field ids (fgid / 'fields') with the keys")
             if self.model.kind == "mvm":
                 raise ValueError("an MVM model groups features by field: give the field ids "
                                  "(fgid / 'fields') with the keys")
@@ -102,7 +110,8 @@ class Predictor:
         elif len(fgid) != len(keys):
             raise ValueError("fgid must hold one field id per key")
         out = np.empty(rows, np.float32)
-        cap_nnz = self.engine.cfg.max_nnz
+        # (the engine's max_nnz also holds the rows' cross keys)
+        cap_nnz = self.engine.cfg.max_nnz - len(self.crosses) * self.max_rows
         r = 0
         with self._lock:
             while r < rows:
@@ -118,6 +127,8 @@ class Predictor:
                           row_ptr=torch.from_numpy((row_ptr[r:r1 + 1] - k0).astype(np.int32)).to(dev),
                           fgid=torch.from_numpy(np.ascontiguousarray(fgid[k0:k1], np.int32)).to(dev),
                           slice_rows=r1 - r)
+                if self.crosses:
+                    b = self.engine.cross_batch(b, self.crosses, fgid_base=self.cross_field_base)
                 out[r:r1] = self.engine.eval_step(b).cpu().numpy()
                 r = r1
         return out
@@ -136,7 +147,8 @@ class Predictor:
     def predict_keys(self, rows: Sequence[Sequence[int]],
                      fields: Optional[Sequence[Sequence[int]]] = None) -> np.ndarray:
         """pctr of rows given as lists of (already hashed) u64 keys, with the
-        keys' field ids (same shape; required for MVM)."""
+        keys' field ids (same shape; required for MVM and for a model trained
+        with feature crosses)."""
         lens = np.array([len(r) for r in rows], np.int64)
         rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         keys = (np.array([k for r in rows for k in r], dtype=np.uint64) if len(rp) > 1 and rp[-1]

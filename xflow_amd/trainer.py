@@ -37,7 +37,7 @@ import torch
 
 from xflow_amd import checkpoint
 from xflow_amd import native as _native
-from xflow_amd.config import TrainConfig, model_kind
+from xflow_amd.config import TrainConfig, check_crosses, model_kind
 from xflow_amd.data import binfmt
 from xflow_amd.data.textstream import TextStream
 from xflow_amd.data.upload import BlockStream
@@ -70,8 +70,31 @@ class Trainer:
         self.cfg = cfg
         if cfg.shuffle and cfg.serial_slices:
             raise ValueError("--shuffle trains with concurrent slices (not --serial-slices)")
+        # feature crosses (Engine.cross_batch): every block is crossed on the
+        # device in its layout pass (_laid_out), the test blocks included
+        self.crosses = check_crosses(cfg.crosses) if cfg.crosses else []
+        mvm = model_kind(cfg.model.kind) == 2
+        if self.crosses and cfg.serial_slices:
+            raise ValueError("--cross trains with concurrent slices (not --serial-slices)")
+        if self.crosses and mvm and cfg.cross_field_base < 0:
+            raise ValueError("--cross with MVM needs --cross-field-base: its products run over "
+                             "field ids, so every cross needs one")
+        # the crosses' field ids in the model's batch (None: LR / FM drop the
+        # field ids after the cross)
+        self._cross_base = int(cfg.cross_field_base) if self.crosses and mvm else None
         self.world = xdist.start(device)
         self.rank = xdist.my_rank()
+        if self.crosses:
+            # a packed block is expanded straight to field-major columns, and a
+            # column is a position, not a field id (UnpackArgs::fgid_col): the
+            # operands of a cross are looked up by field id in the row
+            for p in (shard_path(cfg.train_prefix, self.rank), shard_path(cfg.test_prefix, 0)):
+                xfb = binfmt.shard_file(p)
+                if xfb and binfmt.version_of(xfb) == binfmt.VERSION_PACKED:
+                    raise ValueError("--cross: packed (version 3) .xfb shards are expanded straight "
+                                     "to field-major on the device, without the rows' field ids "
+                                     "the crosses look their operands up by; convert the shard "
+                                     "without --packed")
         if cfg.shuffle:
             xfb = binfmt.shard_file(shard_path(cfg.train_prefix, self.rank))
             if xfb and binfmt.version_of(xfb) == binfmt.VERSION_PACKED:
@@ -97,6 +120,8 @@ class Trainer:
                 ecfg.max_rows = max(ecfg.max_rows, rows)
                 ecfg.max_nnz = max(ecfg.max_nnz, nnz)
         ecfg.max_slices = max(ecfg.max_slices, self.S)
+        # (every row gains one key per cross)
+        ecfg.max_nnz += len(self.crosses) * ecfg.max_rows
         if cfg.save_delta:
             if cfg.delta_full_every < 1:
                 raise ValueError("--delta-full-every must be >= 1")
@@ -141,6 +166,10 @@ class Trainer:
         self.samples = 0
         self.resumed = False
         self._with_fgid = model_kind(cfg.model.kind) == 2
+        # the blocks' arrays carry the field ids: the model reads them, or the
+        # crosses do (a fixed-width block only has uniform row lengths: column
+        # j is not field j)
+        self._block_fgid = self._with_fgid or bool(self.crosses)
         self._resident = None
 
     # ------------------------------------------------------------------ data
@@ -156,6 +185,8 @@ class Trainer:
             # a packed (v3 .xfb) block: its bytes, expanded on the device
             if seed is not None or raw:
                 raise ValueError("--shuffle: packed .xfb blocks cannot be shuffled")
+            if self.crosses:
+                raise ValueError("--cross: packed .xfb blocks cannot be crossed")
             p = blk["packed"]
             if not isinstance(p, torch.Tensor):
                 p = torch.from_numpy(np.array(p)).to(dev)
@@ -185,7 +216,7 @@ class Trainer:
         k = np.asarray(blk["keys"][:nnz])
         # (compact u32 .xfb keys upload as int32 and widen on the device)
         keys = up(k.view(np.int32) if k.dtype == np.uint32 else k.view(np.int64))
-        fgid = up(blk["fgid"][:nnz]) if with_fgid else None
+        fgid = up(blk["fgid"][:nnz]) if with_fgid or self.crosses else None
         if F:
             return self._laid_out(Batch(keys=keys, labels=up(blk["labels"][:used]), fgid=fgid,
                                         nnz_per_row=F, slice_rows=slice_rows), seed, raw)
@@ -196,10 +227,15 @@ class Trainer:
         """The batch the step trains from a block's device arrays (CSR, or
         fixed-width row-major with possibly compact keys): fixed-width blocks
         field-major; with a seed, the rows shuffled in that same pass
-        (Engine.shuffle_batch).  raw: the arrays as they are (what --resident
-        --shuffle keeps, to lay out again every epoch)."""
+        (Engine.shuffle_batch); with crosses, their keys appended in that
+        pass too (Engine.cross_batch).  raw: the arrays as they are (what
+        --resident --shuffle keeps, to lay out again every epoch)."""
         if raw:
             return b
+        if self.crosses:
+            # the same pass also appends the crosses' keys (and shuffles, with a
+            # seed); the field ids stay only where the model reads them
+            return self.engine.cross_batch(b, self.crosses, seed=seed, fgid_base=self._cross_base)
         if seed is not None:
             return self.engine.shuffle_batch(b, seed)
         return b.to_field_major(self.engine) if b.row_ptr is None else b
@@ -223,7 +259,7 @@ class Trainer:
             if used != blk["rows"] - blk["rows"] % (1 if self.cfg.keep_remainder else self.threads):
                 raise ValueError("text-stream block: used rows differ from the parse's")
             nnz = int(blk["nnz_used"])
-        fgid = blk["fgid"][:nnz] if with_fgid else None
+        fgid = blk["fgid"][:nnz] if with_fgid or self.crosses else None
         F = blk["nnz_per_row"] if self.cfg.fixed_width else 0
         if F:
             return self._laid_out(Batch(keys=blk["keys"][:nnz], labels=blk["labels"][:used],
@@ -355,7 +391,7 @@ class Trainer:
                     # events, reported in the epoch record (overlap evidence)
                     tl = (StreamTimeline(self.device)
                           if os.environ.get("XFLOW_STREAM_TIMELINE") else None)
-                    stream = BlockStream(reader.next, self.device, self._with_fgid,
+                    stream = BlockStream(reader.next, self.device, self._block_fgid,
                                          copy_threads=cfg.copy_threads, timeline=tl)
                     nxt = stream.next
                 record = [] if cfg.resident else None
@@ -441,6 +477,8 @@ class Trainer:
                        monitor_waits=self.table.monitor_waits)
             rec["shuffle"] = bool(cfg.shuffle)
             rec["shuffle_seed"] = int(cfg.shuffle_seed)
+            if self.crosses:
+                rec["crosses"] = [list(c) for c in self.crosses]
             if cfg.engine.admit_min_count > 1:
                 rec["admit_min_count"] = cfg.engine.admit_min_count
             if pruned is not None:
@@ -524,7 +562,13 @@ class Trainer:
                     break
             if self.sharded is None and blk is None:
                 break
-            if gfield >= 0:
+            if gfield >= 0 and self.crosses:
+                # the group keys come from the block's own arrays, the model's
+                # batch from the same arrays crossed
+                bg = self._to_batch(blk, used, sr, with_fgid=True, raw=True)
+                b = bg if bg.rows == 0 else self._laid_out(bg, None)
+                bg = dataclasses.replace(bg, keys=widen_keys(bg.keys))
+            elif gfield >= 0:
                 # the grouped figures read the rows' field ids, under every
                 # model; a model that does not read them predicts on the batch
                 # it gets with the option off
@@ -619,12 +663,17 @@ class Trainer:
         if hasattr(self.sharded, "flush"):
             self.sharded.flush()
         path = checkpoint.save(self.table, ckpt_dir, self.rank, self.world,
-                               meta={"epoch": self.epoch, "steps": self.steps},
+                               meta=dict({"epoch": self.epoch, "steps": self.steps},
+                                         **checkpoint.cross_meta(self.crosses, self._cross_base)),
                                barrier=xdist.barrier, delta_base=delta_base)
         xdist.barrier()
         return path
 
     def load(self, ckpt_dir: str) -> dict:
+        # (before anything is loaded: a table trained with other crosses holds
+        # other keys)
+        checkpoint.check_crosses_match(checkpoint.load_meta(ckpt_dir), self.crosses,
+                                       self._cross_base, ckpt_dir)
         meta = checkpoint.load(self.table, ckpt_dir, self.rank, self.world)
         self.epoch = int(meta.get("epoch", 0))
         self.steps = int(meta.get("steps", 0))
