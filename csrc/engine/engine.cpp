@@ -562,6 +562,7 @@ StepInputs Engine::step_inputs() const {
   in.kdim = cfg_.model.kernel_dim();
   in.lead_handoff = cfg_.lead_handoff;
   in.red_rank = cfg_.red_rank;
+  in.red_local = cfg_.red_local;
   return in;
 }
 
@@ -668,6 +669,10 @@ StepPlan plan_step(const StepInputs& in, int S) {
   // without the handoff, reference FM's (B, C).  The dedup then writes no
   // slot -> unique map.  Does not change the gradient layout.
   p.red_rank = in.red_rank && in.gpu && S == 1 && in.red_pairs && !p.upos && (p.lr16 || p.fmu);
+  // Bucket-sorted producer regions: exactly the handoff steps (k_lr_lead is
+  // the one producer that holds every record's bucket before its backward).
+  // Does not change the gradient layout.
+  p.red_local = in.red_local && p.lead;
   return p;
 }
 
@@ -930,6 +935,7 @@ void Engine::train_step(const BatchView& b) {
     fa.agg_ok = key_bound * Sg * ps < 4294967295.0;  // (32-bit dest * ps, see rows_ok)
     if (upos) fa.red_nuq = ws_->n_uniq;
     fa.lead = P.lead;  // (one group, one slice: the whole batch's positions)
+    fa.red_local = P.red_local;
     // slice bits from the reduction (unique order with the outputs, else
     // slot-indexed), else per occurrence
     if (uq) fa.red_masks = lr_mask_;

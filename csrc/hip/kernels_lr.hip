@@ -190,6 +190,19 @@ __global__ void __launch_bounds__(BLOCK) k_lr(FwdArgs a) {
 //             record (slot, sum) exactly as ListAgg's claimer does, so the
 //             workgroup's region holds the same record set in another order.
 // Rows of at most kLrRegCols features, S = 1, every row of the grid live.
+//
+// kLocal (FwdArgs::red_local): the region is written sorted by bucket, so the
+// reduction needs neither k_red_scan nor k_red_scatter (k_red_sum_local reads
+// the (workgroup, bucket) segments in place).  Every leader's slot is in pv
+// before the forward's first use of a gathered weight, so the leaders are
+// counted per bucket under that latency; a scan of the counts gives each
+// bucket's first record of the region, and in the backward a leader takes its
+// record index from its bucket's cursor (a returning LDS add before the
+// column's barrier) instead of the workgroup's running count.  The tail writes
+// start << 16 | count per bucket to red_hist (lead_seg).  The record set is
+// what the other form writes; their order inside a segment is a race, as their
+// order in the region already was.
+template <bool kLocal>
 __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
   XF_KT_DECL;
   constexpr int BLOCK = kLeadTile;
@@ -200,7 +213,9 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
   __shared__ float s_w[2][Q][BLOCK];
   __shared__ long long s_acc[2][BLOCK];
   __shared__ u32 s_hist[kRedMaxBuckets];
+  __shared__ u32 s_cur[kLocal ? kRedMaxBuckets : 1];  // (kLocal) next record of each bucket
   __shared__ u32 s_n;
+  static_assert(kRedMaxBuckets % BLOCK == 0, "the cursor scan: whole lanes");
   const BatchView& b = a.batch;
   const u32* __restrict__ pos = a.pos;
   const float* __restrict__ wp = a.wpull;
@@ -216,6 +231,7 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
   s_acc[1][t] = 0ll;
   for (int i = t; i < nb; i += BLOCK) s_hist[i] = 0u;
   if (t == 0) s_n = 0u;
+  if constexpr (kLocal) lds_barrier();  // (s_hist is zero before the first count below)
   XF_KT(0);
   // every position load, then every leader's gather, in flight at once
   u32 pv[C];
@@ -226,6 +242,16 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
   for (int j = 0; j < C; ++j) {
     XF_DASSERT((pv[j] & kLeadBit) || pv[j] <= a.trash_pos);
     wv[j] = pv[j] & kLeadBit ? 0.0f : wp[pv[j]];
+  }
+  if constexpr (kLocal) {
+    // the emitting leaders per bucket, counted while the gathers are in flight
+    // (a column past the row's length holds kLeadBit)
+#pragma unroll
+    for (int j = 0; j < C; ++j)
+      if (!(pv[j] & kLeadBit) && pv[j] != a.trash_pos) {
+        XF_DASSERT((int)(pv[j] >> shift) < nb);
+        atomicAdd(&s_hist[pv[j] >> shift], 1u);
+      }
   }
 #pragma unroll
   for (int j0 = 0; j0 < C; j0 += Q) {
@@ -241,6 +267,25 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
     for (int q = 0; q < Q; ++q)
       if (j0 + q < len && (pv[j0 + q] & kLeadBit)) wv[j0 + q] = s_w[buf][q][pv[j0 + q] & kIdx];
   }
+  u32 nrec = 0;  // (kLocal) the workgroup's records
+  if constexpr (kLocal) {
+    // the counts are complete (the forward has had a barrier): each bucket's
+    // first record index, lane t scanning buckets [kPer t, kPer t + kPer)
+    constexpr int kPer = kRedMaxBuckets / BLOCK;
+    u32 c[kPer], sum = 0;
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      c[q] = kPer * t + q < nb ? s_hist[kPer * t + q] : 0u;
+      sum += c[q];
+    }
+    u32 ex = block_exclusive_scan<BLOCK>(sum, &nrec);
+#pragma unroll
+    for (int q = 0; q < kPer; ++q) {
+      if (kPer * t + q < nb) s_cur[kPer * t + q] = ex;
+      ex += c[q];
+    }
+    XF_DASSERT(nrec <= (u32)BLOCK * (u32)len);
+  }
   StatAcc st;
   float wx = 0.0f;
 #pragma unroll
@@ -255,6 +300,7 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
   u32 bad = 0;
   const long long v = fx_from<kFx>(fx_clamp<kFx>(loss, bad));
   // (the init's s_acc / s_hist / s_n stores are ordered by the forward's barrier)
+  if constexpr (kLocal) lds_barrier();  // (the cursors, before the first column takes one)
 #pragma unroll
   for (int j = 0; j < C; ++j) {
     if (j >= len) continue;  // (block-uniform)
@@ -265,18 +311,22 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
     const bool emits = !follows && pj != a.trash_pos;
     if (follows)
       atomicAdd(reinterpret_cast<unsigned long long*>(&s_acc[tb][pj & kIdx]), (unsigned long long)v);
-    const unsigned long long m = __ballot(emits);
     u32 idx = 0;
-    if (m) {
-      const int lane = lane_id();
-      const int first = __ffsll((long long)m) - 1;
-      u32 base = 0;
-      if (lane == first) base = atomicAdd(&s_n, (u32)__popcll(m));
-      idx = __shfl(base, first) + (u32)__popcll(m & ((1ull << lane) - 1ull));
-    }
-    if (emits) {
-      XF_DASSERT((int)(pj >> shift) < kRedMaxBuckets);
-      atomicAdd(&s_hist[pj >> shift], 1u);
+    if constexpr (kLocal) {
+      if (emits) idx = atomicAdd(&s_cur[pj >> shift], 1u);
+    } else {
+      const unsigned long long m = __ballot(emits);
+      if (m) {
+        const int lane = lane_id();
+        const int first = __ffsll((long long)m) - 1;
+        u32 base = 0;
+        if (lane == first) base = atomicAdd(&s_n, (u32)__popcll(m));
+        idx = __shfl(base, first) + (u32)__popcll(m & ((1ull << lane) - 1ull));
+      }
+      if (emits) {
+        XF_DASSERT((int)(pj >> shift) < kRedMaxBuckets);
+        atomicAdd(&s_hist[pj >> shift], 1u);
+      }
     }
     XF_KT(4);
     lds_barrier();
@@ -292,11 +342,17 @@ __global__ void __launch_bounds__(kLeadTile) k_lr_lead(FwdArgs a) {
     XF_KT(6);
   }
   __syncthreads();
+  if constexpr (!kLocal) nrec = s_n;
   if (t == 0) {
-    a.red_count[blockIdx.x] = s_n;
-    if (a.red_records) atomicAdd(a.red_records, (unsigned long long)s_n);
+    a.red_count[blockIdx.x] = nrec;
+    if (a.red_records) atomicAdd(a.red_records, (unsigned long long)nrec);
   }
-  for (int i = t; i < nb; i += BLOCK) a.red_hist[(size_t)i * gridDim.x + blockIdx.x] = s_hist[i];
+  for (int i = t; i < nb; i += BLOCK) {
+    // (kLocal: the bucket's cursor has passed its last record)
+    u32 h = s_hist[i];
+    if constexpr (kLocal) h = lead_seg(s_cur[i] - h, h);
+    a.red_hist[(size_t)i * gridDim.x + blockIdx.x] = h;
+  }
   st.bad |= bad;
   flush_stats<BLOCK>(st, a.stats, a.fx_bad);
   XF_KT(3);
@@ -314,6 +370,8 @@ void dispatch_lr(const FwdArgs& a, hipStream_t st) {
     throw std::runtime_error("red_out needs the LR bucket reduction (S > 1: with slice bits)");
   if (a.red_masks && a.S > 1 && !red)
     throw std::runtime_error("red_masks need the LR bucket reduction");
+  if (a.red_local && !a.lead)
+    throw std::runtime_error("red_local: the LR leader handoff only (plan_step)");
   if (a.lead) {
     // leader-encoded positions (DedupOut::lead): one workgroup per dedup
     // tile row block, whatever the batch size (no narrow_rows)
@@ -323,7 +381,8 @@ void dispatch_lr(const FwdArgs& a, hipStream_t st) {
         b.nnz_per_row < 1 || a.trash_pos >= kLeadBit)
       throw std::runtime_error("LR leader handoff: not a step it covers (plan_step)");
     const int gr = (int)(b.rows / kLeadTile);
-    hipLaunchKernelGGL(k_lr_lead, dim3(gr), dim3(kLeadTile), 0, st, a);
+    if (a.red_local) hipLaunchKernelGGL(k_lr_lead<true>, dim3(gr), dim3(kLeadTile), 0, st, a);
+    else hipLaunchKernelGGL(k_lr_lead<false>, dim3(gr), dim3(kLeadTile), 0, st, a);
 #ifdef XFLOW_KTIMING
     ktime_dump("lr lead (init forward - tail add barrier flush)", 7, st);
 #endif

@@ -17,6 +17,8 @@ namespace hip {
 //   2. k_red_scatter  per producing workgroup: bucket starts (scan of the
 //                     bucket totals), then its pairs to their bucket ranges
 //   3. k_red_sum      per bucket: LDS sums, one plain store per non-zero dest
+// The LR handoff step (FwdArgs::red_local) runs 3 alone, on the segments of
+// the producers' bucket-sorted regions (k_red_sum_local).
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_red_scan(u32* __restrict__ hist, int groups,
                                                      u32* __restrict__ tot, RedGeom geom,
@@ -44,16 +46,24 @@ __global__ void __launch_bounds__(kBlock) k_red_scan(u32* __restrict__ hist, int
 // One (bucket, sub) unit of k_red_sum: records [beg, end) of bucket b, dests
 // [lo, lo + kR).  Barriers are LDS-only: a unit's global stores need not land
 // before the next unit starts.
-template <int NV>
+//
+// kSeg (k_red_sum_local): the bucket's records are not a range of `sorted`
+// but one segment per producer workgroup, in the producers' bucket-sorted
+// regions (LeadSegs).  Wave w takes the workgroups [w per, w per + per), per =
+// ceil(groups / waves), their lead_seg words held one per lane; a segment is
+// read 64 records at a time, its lanes' loads coalesced.  The sums, the rank
+// machinery and the outputs are the range form's.
+template <int NV, bool kSeg = false>
 __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
                                              const void* __restrict__ sorted, const RedFinal& f,
                                              long long* acc, u32* pbits, u32* cbits, u32* rpre,
-                                             u32* rwt) {
+                                             u32* rwt, const LeadSegs& sg = LeadSegs{}) {
   using T = typename RedRec<NV>::T;
   constexpr int kShift = red_shift(NV);
   constexpr u32 kR = 1u << kShift;
   constexpr int kFx = FxBits<NV>::kFx;
-  if (beg == end) return;
+  static_assert(!kSeg || NV == 1, "segments: LR records");
+  if (kSeg ? !sg.any : beg == end) return;
   // Unique-order outputs without the slot -> unique map (RedFinal::rk_offs;
   // one slice, so dests are slots and pbits is free): lane w < kR / 32 turns
   // the 32 stamps of slots [lo + 32 w, + 32) into bitmap word w (bit: the slot
@@ -96,7 +106,14 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
   }
   // sparse units hold their records in registers across the three phases
   constexpr int kSp = 2 * kRedUnroll;
-  const bool dense = end - beg > (u32)(kSp * kRedBlock);  // (block-uniform)
+  // (kSeg: a wave's slots are rows of 64 records, one segment each -- sparse
+  // when every wave's segments fit its kSp rows, k_red_sum_local)
+  const bool dense = kSeg ? sg.dense : end - beg > (u32)(kSp * kRedBlock);  // (block-uniform)
+  constexpr u32 kWaves = kRedBlock / kWave;
+  const u32 lane = threadIdx.x % kWave;
+  const u32 sper = kSeg ? (sg.groups + kWaves - 1) / kWaves : 0u;
+  const u32 sgb = (threadIdx.x / kWave) * sper;
+  const u32 sge = sgb + sper < sg.groups ? sgb + sper : sg.groups;
   const T* src = static_cast<const T*>(sorted);
   const u64 S = (u64)f.S;
   auto add = [&](const T& r, u32 l) {
@@ -118,28 +135,92 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
     if (f.masks)
       for (u32 i = threadIdx.x; i < kR / 32; i += kRedBlock) pbits[i] = 0u;
     lds_barrier();
-    for (u32 i0 = beg + threadIdx.x; i0 < end; i0 += kRedUnroll * kRedBlock) {
+    if constexpr (kSeg) {
+      // kRedUnroll segments' first rows in flight, then their adds, then the
+      // rest of a segment longer than a row
+      for (u32 c0 = sgb; c0 < sge; c0 += kWave) {
+        const u32 mine = c0 + lane < sge ? sg.row[c0 + lane] : 0u;
+        const u32 n = sge - c0 < (u32)kWave ? sge - c0 : (u32)kWave;
+        for (u32 k0 = 0; k0 < n; k0 += kRedUnroll) {
+          u32 off[kRedUnroll], cnt[kRedUnroll];
+          const T* reg[kRedUnroll];
 #pragma unroll
-      for (int q = 0; q < kRedUnroll; ++q) {
-        const u32 i = i0 + (u32)q * kRedBlock;
-        if (i < end) pr[q] = src[i];
+          for (int q = 0; q < kRedUnroll; ++q) {
+            // (lanes at or past n hold no segment: k0 + q < kWave)
+            sg.seg(__shfl(mine, (int)k0 + q), off[q], cnt[q]);
+            reg[q] = reinterpret_cast<const T*>(sg.pairs) + (u64)(c0 + k0 + q) * sg.gcap + off[q];
+            if (lane < cnt[q]) pr[q] = reg[q][lane];
+          }
+#pragma unroll
+          for (int q = 0; q < kRedUnroll; ++q) {
+            if (lane >= cnt[q]) continue;
+            const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
+            if (l < kR) add(pr[q], (u32)l);  // (else another unit's dest)
+          }
+#pragma unroll
+          for (int q = 0; q < kRedUnroll; ++q) {
+            for (u32 i0 = kWave + lane; i0 < cnt[q]; i0 += kRedUnroll * kWave) {
+              T tr[kRedUnroll];
+#pragma unroll
+              for (int e = 0; e < kRedUnroll; ++e)
+                if (i0 + (u32)e * kWave < cnt[q]) tr[e] = reg[q][i0 + (u32)e * kWave];
+#pragma unroll
+              for (int e = 0; e < kRedUnroll; ++e) {
+                if (i0 + (u32)e * kWave >= cnt[q]) continue;
+                const u64 d = (u64)RedRec<NV>::dest(tr[e]), l = d - lo;
+                if (l < kR) add(tr[e], (u32)l);
+              }
+            }
+          }
+        }
       }
+    } else {
+      for (u32 i0 = beg + threadIdx.x; i0 < end; i0 += kRedUnroll * kRedBlock) {
 #pragma unroll
-      for (int q = 0; q < kRedUnroll; ++q) {
-        if (i0 + (u32)q * kRedBlock >= end) continue;
-        const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
-        if (l < kR) add(pr[q], (u32)l);  // (else another unit's dest)
+        for (int q = 0; q < kRedUnroll; ++q) {
+          const u32 i = i0 + (u32)q * kRedBlock;
+          if (i < end) pr[q] = src[i];
+        }
+#pragma unroll
+        for (int q = 0; q < kRedUnroll; ++q) {
+          if (i0 + (u32)q * kRedBlock >= end) continue;
+          const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
+          if (l < kR) add(pr[q], (u32)l);  // (else another unit's dest)
+        }
       }
     }
   } else {
+    if constexpr (kSeg) {
+      // slot q: the wave's q-th row of 64 records, walking its segments in
+      // order (sparse: at most kWave segments, at most kSp rows in all)
+      const u32 mine = sgb + lane < sge ? sg.row[sgb + lane] : 0u;
+      u32 k = 0, i0 = 0, off, cnt;
+      sg.seg(__shfl(mine, 0), off, cnt);
 #pragma unroll
-    for (int q = 0; q < kSp; ++q) {
-      const u32 i = beg + threadIdx.x + (u32)q * kRedBlock;
-      lr[q] = kR;
-      if (i < end) {
-        pr[q] = src[i];
-        const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
-        if (l < kR) lr[q] = (u32)l;
+      for (int q = 0; q < kSp; ++q) {
+        while (i0 >= cnt && k + 1 < (u32)kWave) {  // (wave-uniform)
+          ++k;
+          i0 = 0;
+          sg.seg(__shfl(mine, (int)k), off, cnt);
+        }
+        lr[q] = kR;
+        if (i0 + lane < cnt) {
+          pr[q] = (reinterpret_cast<const T*>(sg.pairs) + (u64)(sgb + k) * sg.gcap + off)[i0 + lane];
+          const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
+          if (l < kR) lr[q] = (u32)l;
+        }
+        i0 += kWave;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < kSp; ++q) {
+        const u32 i = beg + threadIdx.x + (u32)q * kRedBlock;
+        lr[q] = kR;
+        if (i < end) {
+          pr[q] = src[i];
+          const u64 d = (u64)RedRec<NV>::dest(pr[q]), l = d - lo;
+          if (l < kR) lr[q] = (u32)l;
+        }
       }
     }
     // zero what the records touch (same-value plain stores), and for the
@@ -312,6 +393,57 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum(const void* __restrict__ 
     }
     const u64 lo = ((u64)b << shift) + ((u64)sub << kShift);
     red_sum_unit<NV>(lo, beg, end, sorted, f, acc, pbits, cbits, rpre, rwt);
+    lds_barrier();  // the next unit reinitialises what this one read
+  }
+}
+
+// k_red_sum<1> on the producers' bucket-sorted regions (FwdArgs::red_local):
+// no k_red_scan, no k_red_scatter, no red_sorted.  Per unit the workgroup
+// reads its bucket's row of lead_seg words once to decide the form: every
+// wave counts the 64-record rows of its segments; the unit is sparse when no
+// wave has more than the 2 kRedUnroll rows its lanes have record slots for
+// (and at most kWave segments), else dense.  Nothing here depends on another
+// workgroup of this launch.
+__global__ void __launch_bounds__(kRedBlock) k_red_sum_local(LeadSegs sg, RedFinal f, RedGeom geom,
+                                                             int nb) {
+  constexpr int kShift = red_shift(1);
+  constexpr u32 kR = 1u << kShift;
+  constexpr u32 kWaves = kRedBlock / kWave;
+  constexpr u32 kSp = 2 * kRedUnroll;
+  __shared__ long long acc[kR];
+  __shared__ u32 pbits[kR / 32];
+  __shared__ u32 cbits[kR / 32];
+  __shared__ u32 rpre[kR / 32];
+  __shared__ u32 rwt[kR / 32 / kWave];
+  __shared__ u32 s_rows[kWaves];  // 64-record rows of each wave's segments
+  const int shift = geom.shift(kShift);
+  const u32 act = (u32)geom.active(shift, nb);
+  const u32 units = act << (shift - kShift);
+  const u32 lane = threadIdx.x % kWave, w = threadIdx.x / kWave;
+  const u32 per = (sg.groups + kWaves - 1) / kWaves;
+  const u32 gb = w * per, ge = gb + per < sg.groups ? gb + per : sg.groups;
+  for (u32 id = blockIdx.x; id < units; id += gridDim.x) {
+    const u32 b = id % act, sub = id / act;
+    sg.row = sg.hist + (size_t)b * sg.groups;
+    u32 rows = 0;
+    for (u32 c0 = gb; c0 < ge; c0 += kWave) {
+      u32 off, cnt;
+      sg.seg(c0 + lane < ge ? sg.row[c0 + lane] : 0u, off, cnt);
+      rows += (cnt + kWave - 1) / kWave;
+    }
+    rows = wave_sum_u32(rows);
+    if (lane == 0) s_rows[w] = rows;
+    lds_barrier();
+    u32 tot = 0, most = 0;
+#pragma unroll
+    for (u32 i = 0; i < kWaves; ++i) {
+      tot += s_rows[i];
+      most = most > s_rows[i] ? most : s_rows[i];
+    }
+    sg.any = tot != 0u;
+    sg.dense = most > kSp || per > (u32)kWave;
+    const u64 lo = ((u64)b << shift) + ((u64)sub << kShift);
+    red_sum_unit<1, true>(lo, 0u, 0u, nullptr, f, acc, pbits, cbits, rpre, rwt, sg);
     lds_barrier();  // the next unit reinitialises what this one read
   }
 }
@@ -545,23 +677,9 @@ __global__ void __launch_bounds__(kCsrBlock) k_red_csr(const void* __restrict__ 
   }
 }
 
+// the outputs of k_red_sum / k_red_sum_local
 template <int NV>
-void launch_reduction(const FwdArgs& a, int groups, int rows_per_group, hipStream_t st) {
-  u32* start = a.red_tot + a.red_nb + 1;
-  hipLaunchKernelGGL(k_red_scan, dim3(a.red_nb), dim3(kBlock), 0, st, a.red_hist, groups,
-                     a.red_tot, red_geom(a), red_shift(NV));
-  hipLaunchKernelGGL(k_red_scatter<NV>, dim3(groups), dim3(kRedBlock), 0, st, a.batch,
-                     rows_per_group, static_cast<const void*>(a.red_pairs), a.red_count,
-                     a.red_hist, a.red_tot, start, a.red_nb, static_cast<void*>(a.red_sorted),
-                     red_geom(a));
-  if (a.red_csr.cnt) {
-    if (!a.red_nuq || a.red_out || a.S != (1 << a.red_csr.slog2) ||
-        a.red_csr.slog2 > red_shift(NV) || (NV == 2 && !a.fm_compact))
-      throw std::runtime_error("CSR reduction: unique positions, S = 2^slog2 <= 2^shift, no other outputs");
-    hipLaunchKernelGGL(k_red_csr<NV>, dim3(a.red_nb), dim3(kCsrBlock), 0, st,
-                       static_cast<const void*>(a.red_sorted), start, a.red_csr, red_geom(a), a.red_nb);
-    return;
-  }
+static RedFinal red_final(const FwdArgs& a) {
   if (a.red_out && (NV == 2 ? !a.fm_compact : false))
     throw std::runtime_error("red_out: compact rows (reference FM)");
   if (a.red_out && a.S != 1 && !a.red_masks)
@@ -579,6 +697,45 @@ void launch_reduction(const FwdArgs& a, int groups, int rows_per_group, hipStrea
     f.rk_epoch = a.red_rank_epoch;
     f.inv = nullptr;
   }
+  return f;
+}
+
+template <int NV>
+void launch_reduction(const FwdArgs& a, int groups, int rows_per_group, hipStream_t st) {
+  if (a.red_local) {
+    // the producer (k_lr_lead<true>) left each bucket's records as one segment
+    // per workgroup region: the sums read them in place
+    const BatchView& b = a.batch;
+    if (NV != 1 || !a.lead || a.S != 1 || a.red_masks || a.red_nuq || a.red_csr.cnt || b.row_ptr ||
+        rows_per_group != kLeadTile || b.nnz_per_row < 1 || b.nnz_per_row > kLeadMaxFields ||
+        (int64_t)groups * kLeadTile != b.rows)
+      throw std::runtime_error("red_local: the LR leader handoff step only (plan_step)");
+    LeadSegs sg;
+    sg.pairs = a.red_pairs;
+    sg.hist = a.red_hist;
+    sg.groups = (u32)groups;
+    sg.gcap = (u32)(kLeadTile * b.nnz_per_row);
+    const u32 grid = std::min<u32>((u32)(a.red_nb * a.red_nsub), (u32)device_cus());
+    hipLaunchKernelGGL(k_red_sum_local, dim3(grid), dim3(kRedBlock), 0, st, sg, red_final<1>(a),
+                       red_geom(a), a.red_nb);
+    return;
+  }
+  u32* start = a.red_tot + a.red_nb + 1;
+  hipLaunchKernelGGL(k_red_scan, dim3(a.red_nb), dim3(kBlock), 0, st, a.red_hist, groups,
+                     a.red_tot, red_geom(a), red_shift(NV));
+  hipLaunchKernelGGL(k_red_scatter<NV>, dim3(groups), dim3(kRedBlock), 0, st, a.batch,
+                     rows_per_group, static_cast<const void*>(a.red_pairs), a.red_count,
+                     a.red_hist, a.red_tot, start, a.red_nb, static_cast<void*>(a.red_sorted),
+                     red_geom(a));
+  if (a.red_csr.cnt) {
+    if (!a.red_nuq || a.red_out || a.S != (1 << a.red_csr.slog2) ||
+        a.red_csr.slog2 > red_shift(NV) || (NV == 2 && !a.fm_compact))
+      throw std::runtime_error("CSR reduction: unique positions, S = 2^slog2 <= 2^shift, no other outputs");
+    hipLaunchKernelGGL(k_red_csr<NV>, dim3(a.red_nb), dim3(kCsrBlock), 0, st,
+                       static_cast<const void*>(a.red_sorted), start, a.red_csr, red_geom(a), a.red_nb);
+    return;
+  }
+  const RedFinal f = red_final<NV>(a);
   const u32 grid = std::min<u32>((u32)(a.red_nb * a.red_nsub), (u32)device_cus());
   hipLaunchKernelGGL(k_red_sum<NV>, dim3(grid), dim3(kRedBlock), 0, st,
                      static_cast<const void*>(a.red_sorted), start, f, red_geom(a), a.red_nb);

@@ -577,6 +577,29 @@ __device__ __forceinline__ void unit_masks(const u32* pbits, u64 lo, u64 S, u32*
   }
 }
 
+// Bucket-sorted producer regions (FwdArgs::red_local, k_lr_lead<true> ->
+// k_red_sum_local): red_hist[bucket][workgroup] holds the bucket's segment of
+// the workgroup's region, first record << 16 | records.  A region has at most
+// kLeadTile x kLeadMaxFields records.
+static_assert(kLeadTile * kLeadMaxFields < (1 << 16), "lead_seg packs two 16-bit fields");
+__device__ __forceinline__ u32 lead_seg(u32 start, u32 count) { return start << 16 | count; }
+struct LeadSegs {
+  const u64* pairs = nullptr;  // the producers' regions, gcap records apart
+  const u32* hist = nullptr;   // [nb][groups] lead_seg words
+  u32 groups = 0, gcap = 0;
+  // per unit (k_red_sum_local): the bucket's row of hist, whether it has
+  // records at all, and the form of the sums (block-uniform)
+  const u32* row = nullptr;
+  bool any = false, dense = false;
+  // segment g of the row, clamped to the region
+  __device__ __forceinline__ void seg(u32 word, u32& off, u32& cnt) const {
+    off = word >> 16;
+    cnt = word & 0xFFFFu;
+    off = off < gcap ? off : gcap;
+    cnt = cnt < gcap - off ? cnt : gcap - off;
+  }
+};
+
 struct SegSrc {
   const u32* hist;   // [nb][groups] exclusive prefix (k_red_scan)
   const u32* tot;    // [nb]

@@ -218,6 +218,12 @@ struct FwdArgs {
   const u32* pos = nullptr;        // [nnz]
   // pos is leader-encoded (DedupOut::lead): only k_lr_lead reads it
   bool lead = false;
+  // HIP, with lead (StepPlan::red_local): k_lr_lead writes its region sorted
+  // by bucket and red_hist[bucket][workgroup] = first record << 16 | records
+  // of the bucket's segment there; the sums read the segments in place
+  // (k_red_sum_local) -- no k_red_scan, no k_red_scatter; red_sorted and
+  // red_tot are not used
+  bool red_local = false;
   // dedup slot of overflowed occurrences (the scratch's trash slot, == cap):
   // read as zero weights, never reduced (none: ~0)
   u32 trash_pos = 0xFFFFFFFFu;
@@ -238,7 +244,7 @@ struct FwdArgs {
   // which are partitioned by dest >> kRedShift and summed per bucket in LDS.
   u64* red_pairs = nullptr;        // [nnz] per-workgroup pair regions
   u64* red_sorted = nullptr;       // [nnz] pairs in bucket order
-  u32* red_hist = nullptr;         // [red_nb][workgroups] pairs per (bucket, workgroup)
+  u32* red_hist = nullptr;         // [red_nb][workgroups] pairs per (bucket, workgroup) (red_local: segments)
   u32* red_tot = nullptr;          // [red_nb + 1] pairs per bucket, then bucket starts
   u32* red_count = nullptr;        // [workgroups] pairs per workgroup
   int red_nb = 0;                  // buckets allocated (<= the bucket cap)

@@ -93,6 +93,11 @@ struct EngineConfig {
   // compaction's slot -> unique map everywhere (the A/B switch -- the results
   // are bit-equal either way).
   bool red_rank = true;
+  // Bucket-sorted producer regions (StepPlan::red_local) on the
+  // leader-handoff steps: the reduction runs without its scan and scatter
+  // passes.  false keeps them everywhere (the A/B switch -- the results are
+  // bit-equal either way).
+  bool red_local = true;
   // Delta checkpoints (docs/DESIGN.md §2): a filter of 2^delta_log2 bits in
   // device memory, indexed by key hash (delta_bit, common.h), in which every
   // key whose state may have changed is marked -- by a launch of its own
@@ -146,6 +151,7 @@ struct StepInputs {
   bool field_major = false;  // fixed width, col_stride == rows
   double rows = 0.0, fields = 0.0;
   bool red_rank = true;  // EngineConfig::red_rank
+  bool red_local = true;  // EngineConfig::red_local
 };
 
 // Where a step's gradients land, one per step:
@@ -185,6 +191,9 @@ struct StepPlan {
   // unique-order outputs from the stamps and the compaction's chunk offsets
   // (FwdArgs::red_rank_*), the compaction writes no slot -> unique map
   bool red_rank = false;
+  // with lead: k_lr_lead writes its records sorted by bucket and the sums read
+  // them in place (FwdArgs::red_local): no k_red_scan, no k_red_scatter
+  bool red_local = false;
 };
 
 StepPlan plan_step(const StepInputs& in, int S);

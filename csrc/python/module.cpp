@@ -136,6 +136,7 @@ StepInputs inputs_from(py::dict d) {
   // the leader handoff: the switch and the batch's shape
   in.lead_handoff = flag("lead_handoff", true);
   in.red_rank = flag("red_rank", true);
+  in.red_local = flag("red_local", true);
   in.field_major = flag("field_major", false);
   in.rows = d.contains("rows") ? d["rows"].cast<double>() : 0.0;
   in.fields = d.contains("fields") ? d["fields"].cast<double>() : 0.0;
@@ -408,8 +409,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int device, bool table_grow, double grow_load, int max_log2_cap,
                        int monitor_lag, int owner_group, double grow_start, bool csr,
                        int admit_min_count, int admit_log2, bool lead_handoff,
-                       bool scratch_carry, bool red_rank, bool delta_track, int delta_log2) {
+                       bool scratch_carry, bool red_rank, bool delta_track, int delta_log2,
+                       bool red_local) {
              EngineConfig c;
+             c.red_local = red_local;
              c.delta_track = delta_track;
              c.delta_log2 = delta_log2;
              c.red_rank = red_rank;
@@ -444,7 +447,7 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
            py::arg("lead_handoff") = true, py::arg("scratch_carry") = true,
            py::arg("red_rank") = true, py::arg("delta_track") = false,
-           py::arg("delta_log2") = 0)
+           py::arg("delta_log2") = 0, py::arg("red_local") = true)
       // delta checkpoints (EngineConfig::delta_track)
       .def("delta_count", &Engine::delta_count, py::call_guard<py::gil_scoped_release>())
       .def("delta_export",
@@ -504,9 +507,14 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def_property_readonly("table_growths", &Engine::table_growths)
       .def_property_readonly("csr_steps", &Engine::csr_steps)
       // (rows, fields, field_major: the batch's shape, which the leader handoff depends on)
+      // red_local follows lead, so it is reported here, for a batch, and not
+      // by the bare plan_step, whose callers compare plans with "lead" left out
       .def("step_plan",
            [](const Engine& e, int S, int64_t rows, int64_t fields, bool field_major) {
-             return plan_dict(e.plan(S, rows, fields, field_major));
+             const StepPlan p = e.plan(S, rows, fields, field_major);
+             py::dict d = plan_dict(p);
+             d["red_local"] = p.red_local;
+             return d;
            },
            py::arg("S"), py::arg("rows") = 0, py::arg("fields") = 0, py::arg("field_major") = false)
       .def_property_readonly("table_splits", &Engine::table_splits)

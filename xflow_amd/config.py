@@ -165,6 +165,11 @@ class EngineConfig:
     # the compaction writes no slot -> unique map; False keeps the map
     # (bit-equal results, the A/B switch)
     red_rank: bool = True
+    # leader-handoff steps (docs/DESIGN.md §3): the forward/backward kernel
+    # writes its gradient records sorted by reduction bucket and the sums read
+    # them in place, without the reduction's scan and scatter passes; False
+    # keeps the passes (bit-equal results, the A/B switch)
+    red_local: bool = True
     # delta checkpoints (docs/DESIGN.md §2): mark every key whose state may
     # have changed in a filter of 2^delta_log2 bits indexed by key hash, so
     # that Engine.save_delta writes only those keys.  delta_log2: 10..34,
