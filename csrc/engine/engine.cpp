@@ -167,7 +167,17 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
     // sums a wide bucket with red_nsub workgroups -- only when the adaptive
     // scratch has grown that far (bench shape: S = 8 at 2^23 active slots
     // stays at 4096 buckets of 2^14).
-    const uint64_t dests = scratch_.cap * (uint64_t)slice_cap_;
+    uint64_t dests = scratch_.cap * (uint64_t)slice_cap_;
+    // A CSR step reduces every slice at once, not one slice group: its dests
+    // are unique << slog2, up to max_nnz << slog2(max_slices).  Wherever
+    // plan_step takes the CSR path the buckets cover that too (a dest past
+    // the allocated buckets has no cursor in k_red_scatter).
+    {
+      int sl = 0;
+      while ((1 << sl) < cfg_.max_slices) ++sl;
+      const uint64_t csr_dests = (uint64_t)cfg_.max_nnz << sl;
+      if (cfg_.csr && sl <= shift && csr_dests < 4294967295ull && csr_dests > dests) dests = csr_dests;
+    }
     // vector records: the producer's larger bucket cap where its LDS allows
     // (vec_red_max_buckets) and the batch fits the scatter-free form
     const int vd = nv - 1;  // k_fm_std_red<vd>: NV = 1 + vd
@@ -851,11 +861,45 @@ void Engine::csr_debug(std::vector<u32>& off, std::vector<u32>& cnt, std::vector
   be_->copy_d2h(cnt.data(), csr_cnt_, sizeof(u32) * (size_t)n);
   u64 end = 0;
   for (int64_t i = 0; i < n; ++i) end = std::max<u64>(end, (u64)off[i] + cnt[i]);
-  const bool rows = csr_vent_ && cfg_.model.kind == kFM && cfg_.model.fm_math == kFmStandard;
+  // (full-row entries, MVM's too, are in csr_vent_: csr_forward_backward)
+  const bool rows = csr_vent_ && csr_full_rows();
   const int w = rows ? csr_row_words(table_.L.P) : csr_entry_bytes() / 4;
   words.resize((size_t)end * w);
   if (end) be_->copy_d2h(words.data(), rows ? static_cast<const void*>(csr_vent_.get()) : red_pairs_.get(),
                          sizeof(u32) * (size_t)end * w);
+}
+
+std::vector<u64> Engine::unique_keys() {
+  std::vector<u64> k((size_t)n_unique());
+  if (!k.empty()) be_->copy_d2h(k.data(), uniq_keys_, sizeof(u64) * k.size());
+  return k;
+}
+
+Engine::RedGeometry Engine::red_geometry(int S, int64_t nuq) {
+  RedGeometry g;
+  const bool fm_std = cfg_.model.kind == kFM && cfg_.model.fm_math == kFmStandard;
+  const bool mvm = cfg_.model.kind == kMVM && cfg_.model.kernel_dim() >= 2;
+  const int kd = cfg_.model.kernel_dim();
+  const int nv = fm_vals_ ? 2 : (fm_std ? 1 + kd : (mvm ? kd : 1));
+  int sl = 0;
+  while ((1 << sl) < S) ++sl;
+  g.base = red_shift(nv);
+  g.maxb = red_maxb_ > 0 ? red_maxb_ : kRedMaxBuckets;
+  g.nsub = red_nsub_;
+  g.nb = red_nb_;
+  g.nuq = nuq >= 0 ? nuq : n_unique();
+  // RedGeom::shift and RedGeom::active (csrc/hip/model_common.h), dests = unique << sl
+  const u64 dests = (u64)g.nuq << sl;
+  int sh = g.base;
+  while (((dests + (1ull << sh) - 1) >> sh) > (u64)kRedMaxBuckets) ++sh;
+  if (g.maxb > kRedMaxBuckets && sh - g.base >= 2)
+    while (sh > g.base && ((dests + (1ull << (sh - 1)) - 1) >> (sh - 1)) <= (u64)g.maxb) --sh;
+  const int min_shift = csr_full_rows() ? kCsrVecMinShift : 0;
+  g.shift = sh < min_shift ? min_shift : sh;
+  const u64 n = (dests + (1ull << g.shift) - 1) >> g.shift;
+  g.needed = (int64_t)n;  // (beyond nb: the step's dests do not fit the allocated buckets)
+  g.buckets = n < (u64)g.nb ? (int)n : g.nb;
+  return g;
 }
 
 void Engine::train_step(const BatchView& b) {

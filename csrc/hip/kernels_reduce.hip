@@ -652,18 +652,12 @@ __global__ void __launch_bounds__(kCsrBlock) k_red_csr(const void* __restrict__ 
       for (u32 sub = 0; sub < wn; sub += kCsrHash) {
         for (u32 i = (u32)tid; i < (u32)(kCsrHash * NV); i += kCsrBlock) acc[i] = 0ll;
         lds_barrier();
-        if (reg) {
-#pragma unroll
-          for (int q = 0; q < kCsrReg; ++q) {
-            const u32 d = pd[q] - woff - sub;
-            if (pd[q] != ~0u && d < (u32)kCsrHash && pd[q] - woff < wn) add(d, pr[q]);
-          }
-        } else {
-          for (u32 i = beg + (u32)tid; i < end; i += kCsrBlock) {
-            const T r = src[i];
-            const u64 d = (u64)RedRec<NV>::dest(r) - wlo - sub;
-            if (d < (u64)kCsrHash) add((u32)d, r);
-          }
+        // (never the register form: it holds at most kCsrReg * kCsrBlock =
+        // kCsrHash / 2 records, and this branch has more in one window)
+        for (u32 i = beg + (u32)tid; i < end; i += kCsrBlock) {
+          const T r = src[i];
+          const u64 d = (u64)RedRec<NV>::dest(r) - wlo - sub;
+          if (d < (u64)kCsrHash) add((u32)d, r);
         }
         lds_barrier();
         for (u32 l = (u32)tid; l < (u32)kCsrHash; l += kCsrBlock) {

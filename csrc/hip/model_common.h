@@ -66,7 +66,7 @@ __device__ __forceinline__ int slice_of(const BatchView& b, int64_t r, int S) {
 // Bucket geometry of this step's gradient reduction (FwdArgs::red_bcap):
 // the smallest shift >= base that keeps ceil(dests / 2^shift) within
 // kRedMaxBuckets, dests = (batch scratch capacity) * S.
-constexpr int kCsrVecMinShift = 14;
+// (kCsrVecMinShift: backend.h, next to Engine::red_geometry's host copy of shift())
 struct RedGeom {
   const unsigned long long* bcap;
   u64 cap;

@@ -324,6 +324,7 @@ struct FwdArgs {
 };
 constexpr int kRedShift = 14;      // 16384 gradient destinations per bucket (64 KB of LDS)
 constexpr int kRedMaxBuckets = 4096;
+constexpr int kCsrVecMinShift = 14;  // smallest bucket shift of the CSR vector reduction (RedGeom)
 // destinations per bucket for NV aggregated values per key (NV x 2^shift x 4 B <= 64 KB)
 // (nv >= 3: standard-FM vector records, 1 + D values: 2^shift x nv int64 in
 // at most ~114 KB of LDS)

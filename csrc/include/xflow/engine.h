@@ -364,6 +364,18 @@ class Engine {
   // host copies of the last CSR step's per-key (off, cnt) and its entry words
   // (tests / debugging; syncs)
   void csr_debug(std::vector<u32>& off, std::vector<u32>& cnt, std::vector<u32>& words);
+  // the unique keys of the last fused step, in unique order (which slot a key
+  // gets is a CAS race, so the order is the step's own; tests; syncs)
+  std::vector<u64> unique_keys();
+  // the bucket geometry a CSR step of S slices has at the last batch's unique
+  // count: RedGeom::shift / active on the host (tests assert the branch of
+  // k_red_csr / k_red_csr_vec a case reaches; syncs)
+  struct RedGeometry {
+    int base = 0, shift = 0, buckets = 0, maxb = 0, nsub = 1, nb = 0;
+    int64_t nuq = 0, needed = 0;
+  };
+  // (nuq < 0: the last batch's unique count)
+  RedGeometry red_geometry(int S, int64_t nuq = -1);
   int64_t table_splits() const { return splits_; }
   // feature admission: the filter's bytes (0: off) and log2 of them, the
   // estimates min(c0, c1) of keys' sightings, the whole filter to / from

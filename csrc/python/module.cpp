@@ -784,6 +784,22 @@ PYBIND11_MODULE(_xflow_native, m) {
              e.csr_debug(o, c, w);
              return py::make_tuple(to_np(o), to_np(c), to_np(w));
            })
+      .def("unique_keys", [](Engine& e) { return to_np(e.unique_keys()); })
+      .def("red_geometry",
+           [](Engine& e, int S, int64_t nuq) {
+             const Engine::RedGeometry g = e.red_geometry(S, nuq);
+             py::dict d;
+             d["base"] = g.base;
+             d["shift"] = g.shift;
+             d["buckets"] = g.buckets;
+             d["maxb"] = g.maxb;
+             d["nsub"] = g.nsub;
+             d["nb"] = g.nb;
+             d["nuq"] = g.nuq;
+             d["needed"] = g.needed;
+             return d;
+           },
+           py::arg("S"), py::arg("nuq") = -1)
       .def("n_unique", &Engine::n_unique)
       .def("table_size", &Engine::table_size)
       .def("scratch_capacity", &Engine::scratch_capacity)
