@@ -11,6 +11,7 @@
 #include <thread>
 #include <fstream>
 #include <stdexcept>
+#include <string>
 
 namespace xflow {
 
@@ -219,7 +220,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   wpull_.alloc(be, rows1 * vstride_);
   be.memset(wpull_ + scratch_.cap * vstride_, 0, sizeof(float) * vstride_);
   stats_.alloc_zero(be, 2);
-  bucket_ws_.alloc(be, 512);
+  if (!be.partitioned_dedup()) bucket_ws_.alloc(be, 512);  // (Backend::bucket's cursors)
   slice_rows_.alloc(be, kSliceGroup);
 
   st_keys_.alloc(be, nnz);
@@ -240,7 +241,7 @@ void Engine::use_worker_set(int wb) {
   Backend& be = *be_;
   const int64_t nnz = cfg_.max_nnz;
   ws_->uniq_pos.alloc(be, nnz);
-  ws_->send_pos.alloc(be, nnz);
+  if (!be.partitioned_dedup()) ws_->send_pos.alloc(be, nnz);  // (Backend::bucket's output)
   ws_->n_uniq.alloc_zero(be, 1);
   ws_->bcap.alloc_zero(be, 1);
   ws_->pos.alloc(be, nnz);
@@ -581,8 +582,7 @@ StepPlan plan_step(const StepInputs& in, int S) {
   StepPlan p;
   p.S = S;
   const TableLayout& L = in.L;
-  const bool lr16_slot = in.kind == kLR && L.stride == 4 && L.P == 1 && L.opt == kFTRL &&
-                         !L.has_flag;
+  const bool lr16_slot = in.kind == kLR && L.lr16();
   // CSR: several ordered slices of LR-FTRL 16-byte slots or reference FM, on
   // unique-index positions; dests = unique * 2^sl + slice inside one bucket
   // and in 32 bits
@@ -1124,6 +1124,10 @@ std::vector<float> Engine::pull_host(const std::vector<u64>& keys) {
 // ---------------------------------------------------------------------------
 void Engine::w_prepare(const BatchView& b, int world, int64_t* counts_out, u64* send_keys_out,
                        int wb, int64_t seq) {
+  // (the partitioned dedup is the backend's only way to group keys by owner)
+  if (be_->partitioned_dedup() && (world < 1 || world > kMaxParts))
+    throw std::runtime_error("w_prepare: world size " + std::to_string(world) + " outside [1, " +
+                             std::to_string(kMaxParts) + "]");
   if (world <= 1) seq = -1;  // (no exchange to check)
   use_worker_set(wb);
   if (slices_of(b) > cfg_.max_slices)
@@ -1140,7 +1144,7 @@ void Engine::w_prepare(const BatchView& b, int world, int64_t* counts_out, u64* 
     ws_->send_map = ws_->uniq_pos;
     return;
   }
-  if (world >= 1 && world <= kMaxParts && be_->partitioned_dedup()) {
+  if (be_->partitioned_dedup()) {
     // owner-partitioned scratch: the slot-ordered unique list is the send
     // order already; counts are range counts (one range at world 1).  ws_->inv
     // (slot -> send index) lets the LR backward write the send buffer directly.
@@ -1179,7 +1183,7 @@ void Engine::ensure_server_capacity(int64_t n, int buf) {
 
 bool Engine::lr16_layout() const {
   const TableLayout& L = table_.L;
-  return be_->is_gpu() && L.stride == 4 && L.P == 1 && L.opt == kFTRL && !L.has_flag;
+  return be_->is_gpu() && L.lr16();
 }
 
 void Engine::w_forward(const BatchView& b, const float* pulled, int64_t n_send, float* pctr,

@@ -204,7 +204,10 @@ class HipBackend final : public Backend {
   void remap_pos(u32* pos, int64_t nnz, const u32* inv, u32 none) override {
     hip::launch_remap_pos(pos, nnz, inv, none, stream_);
   }
-  void bucket(const BucketArgs& a) override { hip::launch_bucket(a, stream_); }
+  // (never called: Engine::w_prepare takes the partitioned dedup on this backend)
+  void bucket(const BucketArgs&) override {
+    throw std::logic_error("bucket: not on the HIP backend");
+  }
   bool partitioned_dedup() const override { return true; }
   void partition_counts(const ScratchView& s, const u32* chunk_offsets, const int64_t* n_uniq,
                         int64_t* counts, int64_t seq) override {

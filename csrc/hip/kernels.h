@@ -8,20 +8,24 @@
 namespace xflow {
 namespace hip {
 
-// kernels_table.hip
+// kernels_dedup.hip
 void launch_dedup(const u64* keys, int64_t nnz, ScratchView s, DedupOut o, hipStream_t st);
-void launch_table_pull(const PullArgs& a, hipStream_t st);
-void launch_table_apply(const ApplyArgs& a, hipStream_t st);
-void launch_gather_grads(const GatherGradArgs& a, hipStream_t st);
-void launch_owner_group(const OwnerGroupArgs& a, hipStream_t st);
-void launch_bucket(const BucketArgs& a, hipStream_t st);
 void launch_remap_pos(u32* pos, int64_t nnz, const u32* inv, u32 none, hipStream_t st);
 void launch_partition_counts(const ScratchView& s, const u32* chunk_offsets,
                              const int64_t* n_uniq, int64_t* counts, int64_t seq, hipStream_t st);
+
+// kernels_pull.hip
+void launch_table_pull(const PullArgs& a, hipStream_t st);
+
+// kernels_apply.hip
+void launch_table_apply(const ApplyArgs& a, hipStream_t st);
+void launch_owner_group(const OwnerGroupArgs& a, hipStream_t st);
+
+// kernels_exchange.hip
+void launch_gather_grads(const GatherGradArgs& a, hipStream_t st);
 void launch_scatter_rows(const float* src, float* dst, const u32* map, const int64_t* n_dev,
                          int64_t n_max, int width, float* zero_out, int zero_width,
                          hipStream_t st);
-void launch_fill_u64(u64* p, u64 v, size_t n, hipStream_t st);
 // CSR exchange: exclusive scan (out[n] = total; tiles: n_max / 4096 + 2 words)
 void launch_scan_u32(const u32* in, u32* out, const int64_t* n_dev, int64_t n_max, u32* tiles,
                      hipStream_t st);
@@ -30,6 +34,9 @@ void launch_csr_pack(const u32* off, const u32* cnt, const void* src, const u32*
                      hipStream_t st);
 void launch_csr_totals(const int64_t* counts, int world, bool encoded, const u32* doff,
                        int64_t* totals, hipStream_t st);
+
+// kernels_table.hip
+void launch_fill_u64(u64* p, u64 v, size_t n, hipStream_t st);
 void launch_upload_small(void* dst, const void* src, size_t bytes, hipStream_t st);
 void launch_download_small(void* host_dst, const void* src, size_t bytes, hipStream_t st);
 void launch_snapshot(HostSnap* dst, const u32* mon, unsigned long long seq, hipStream_t st);

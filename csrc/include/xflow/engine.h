@@ -552,7 +552,7 @@ class Engine {
     DeviceBuffer<u32> uniq_pos;   // [max_nnz]
     DeviceBuffer<u32> inv;        // [scratch cap] slot -> send index (partitioned dedup, LR)
     DeviceBuffer<int64_t> n_uniq;  // [1]
-    DeviceBuffer<u32> send_pos;   // [max_nnz]
+    DeviceBuffer<u32> send_pos;   // [max_nnz] (only without the partitioned dedup)
     const u32* send_map = nullptr;  // send order -> scratch slot (send_pos or uniq_pos)
     bool inv_valid = false;       // inv describes the batch of the last w_prepare
     DeviceBuffer<unsigned long long> bcap;  // scratch capacity of the set's batch (device)
@@ -661,7 +661,7 @@ class Engine {
   bool reduction_masks(bool unique_positions) const;
   void ensure_inv();
   DeviceBuffer<LossStats> stats_;  // [1]
-  DeviceBuffer<int64_t> bucket_ws_;  // [2*256]
+  DeviceBuffer<int64_t> bucket_ws_;  // [2*256] (only without the partitioned dedup)
   DeviceBuffer<int32_t> slice_rows_;  // [kSliceGroup per slice group]
   int64_t cached_rows_ = -1, cached_slice_rows_ = -1;
   int cached_S_ = -1;

@@ -80,6 +80,9 @@ struct TableLayout {
   int flag_word = 0;
   int stride = 4;      // words per slot
 
+  // LR-FTRL on 16-byte slots {key, n, z}: the layout of the lr16 kernels
+  XF_HD bool lr16() const { return stride == 4 && P == 1 && opt == kFTRL && !has_flag; }
+
   static TableLayout make(const ModelSpec& m, const OptSpec& o) {
     TableLayout t;
     t.P = m.P();

@@ -9,7 +9,6 @@
 #   bash scripts/gpu.sh pmc "ARGS" "KREGEX"       three PMC passes over the kernels matching KREGEX
 #   bash scripts/gpu.sh ab "V1 V2" "ARGS"         ABAB of variants/<V>/ snapshots (make_variant.sh)
 #   bash scripts/gpu.sh shared "N..." "ARGS|..."  multi-process RCCL rehearsal, N ranks sharing GPU 0
-#   bash scripts/gpu.sh kbench "ARGS"             tools/kbench.hip kernel experiments
 #
 # Outputs go to gpurun_out/$TAG/ (TAG defaults to the subcommand).  Every GPU
 # step runs under its own time limit and the script stops at the first
@@ -152,18 +151,6 @@ run_shared() {  # "N..." "ARGS|ARGS|..."
   done
 }
 
-run_kbench() {
-  if [ ! -x build/kbench ] || [ -n "$REBUILD" ]; then
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off \
-      -Icsrc/include -Icsrc/hip tools/kbench.hip csrc/hip/kernels_table.hip \
-      csrc/hip/kernels_model.hip csrc/hip/kernels_lr.hip csrc/hip/kernels_fm.hip \
-      csrc/hip/kernels_mvm.hip csrc/hip/kernels_reduce.hip csrc/hip/kernels_reduce_vec.hip \
-      csrc/hip/kernels_synth.hip -o build/kbench || exit 1
-  fi
-  timeout -k 10 300 build/kbench ${1:-} > "$O/kbench.log" 2>&1 || { echo "kbench failed"; tail -20 "$O/kbench.log"; exit 1; }
-  cat "$O/kbench.log"
-}
-
 case $cmd in
   head) run_tests && run_smoke && run_bench "" && run_bench "" && run_prof "" ;;
   tests) run_tests "$@" ;;
@@ -174,6 +161,5 @@ case $cmd in
   pmcx) run_pmcx "${1:-}" "${2:-.}" "${3:?counters}" ;;
   ab) run_ab "${1:?variants}" "${2:-}" ;;
   shared) run_shared "${1:-2}" "${2:-}" ;;
-  kbench) run_kbench "${1:-}" ;;
   *) echo "unknown subcommand $cmd"; exit 2 ;;
 esac

@@ -1,4 +1,4 @@
-"""The optimiser apply (csrc/hip/kernels_table.hip, the CPU backend's
+"""The optimiser apply (csrc/hip/kernels_apply.hip, the CPU backend's
 table_apply) against a float32 model of the recurrence, bit for bit.
 
 With the gradients given, an apply is a sequential float32 recurrence per (key,

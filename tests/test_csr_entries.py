@@ -4,7 +4,7 @@
 s_apply_csr, against xflow_amd/testing/csr_ref.py.
 
 Structure and LR values are exact.  Which slot -- and so which unique index --
-a key gets is a CAS race of the dedup (csrc/hip/kernels_table.hip), so device
+a key gets is a CAS race of the dedup (csrc/hip/kernels_dedup.hip), so device
 outputs are always compared per key, through the step's own unique list
 (Engine::unique_keys, the send keys of w_prepare), never index by index
 between two engines.
@@ -520,10 +520,10 @@ _WIRE_FUSED = {}
 @pytest.mark.parametrize("world", [1, 2, 3, 8, 256])
 @pytest.mark.parametrize("name", list(WIRE_SPECS))
 def test_wire_form(gpu_device, name, world, seq):
-    """Every world here takes the owner-partitioned dedup (partition_counts):
-    on the GPU w_prepare uses it up to kMaxParts = 1024 owners and refuses more
-    than that ("bucket: world size > 256 unsupported"), so k_bucket_count,
-    k_bucket_scatter and k_encode_counts cannot be reached from it."""
+    """Every world here takes the owner-partitioned dedup (partition_counts),
+    the GPU's only way to group keys by owner: w_prepare uses it for 1 to
+    kMaxParts = 1024 owners and refuses any other world before it launches
+    anything (test_w_prepare_refuses_world_outside_parts)."""
     plant = name.startswith("fm")
     if name not in _WIRE_FUSED:
         spec = WIRE_SPECS[name]()
@@ -533,6 +533,29 @@ def test_wire_form(gpu_device, name, world, seq):
     if world >= 8:
         assert world < 256 or (w["c"] == 0).any(), "an owner without keys"
     _check_wire(spec, name, world, w, fused)
+
+
+@pytest.mark.gpu
+def test_w_prepare_refuses_world_outside_parts(gpu_device):
+    """world = 1025 (> kMaxParts) and world = 0 are host-side argument errors,
+    raised before any launch: the same engine then prepares the batch for 256
+    owners.  (max_nnz is the wire cases': every owner needs slots of its own in
+    the dedup scratch, which is sized by max_nnz.)"""
+    keys = _vocab(16, 40)[np.array([[0, 1], [2, 3], [4, 5], [6, 7], [0, 2], [1, 3], [8, 9], [8, 8]])]
+    spec = Spec(keys, 1, 8, 41)
+    eng = _engine(gpu_device, "lr", spec, max_nnz=8 * 64 * 6)
+    b = spec.batch(gpu_device)
+    counts = torch.zeros(1025, dtype=torch.int64, device=gpu_device)
+    send = torch.zeros(len(spec.keys), dtype=torch.int64, device=gpu_device)
+    with pytest.raises(RuntimeError, match="1024"):
+        eng.w_prepare(b, 1025, counts, send)
+    with pytest.raises(RuntimeError):
+        eng.w_prepare(b, 0, counts, send)
+    eng.w_prepare(b, 256, counts, send)
+    c = counts.cpu().numpy()[:256]
+    assert int(c.sum()) == eng.n_unique() == len(spec.ukeys)
+    skeys = send.cpu().numpy().view(np.uint64)[:int(c.sum())]
+    assert set(skeys.tolist()) == set(spec.ukeys.tolist())
 
 
 @pytest.mark.gpu

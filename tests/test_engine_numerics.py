@@ -141,7 +141,7 @@ def test_gpu_matches_cpu_backend_eval(gpu_device):
 
 def test_slice_normalisation_f32_division_equals_reference_double():
     """The apply kernels normalise a float gradient sum by the slice's row count
-    with an f32 division (kernels_table.hip norm_grad); the reference divides
+    with an f32 division (table_common.h norm_grad); the reference divides
     in double and rounds to float (lr_worker.cc:116-118).  Double rounding is
     innocuous for division when the wide format has >= 2p+2 bits, so both give
     the same float for rows < 2^24 -- checked here on random and edge values."""

@@ -25,7 +25,8 @@ def test_device_assert_build_compiles(tmp_path):
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    for src in ("kernels_table.hip", "kernels_model.hip", "kernels_lr.hip", "kernels_fm.hip",
+    for src in ("kernels_table.hip", "kernels_dedup.hip", "kernels_pull.hip", "kernels_apply.hip",
+                "kernels_exchange.hip", "kernels_model.hip", "kernels_lr.hip", "kernels_fm.hip",
                 "kernels_mvm.hip", "kernels_reduce.hip", "kernels_reduce_vec.hip"):
         r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17",
                             "-DXFLOW_DEVICE_ASSERT=1", "-I" + os.path.join(ROOT, "csrc", "include"),

@@ -1,4 +1,4 @@
-"""A float32 model of the owner apply (csrc/hip/kernels_table.hip, the CPU
+"""A float32 model of the owner apply (csrc/hip/kernels_apply.hip, the CPU
 backend's table_apply), for tests that compare table contents bit for bit.
 
 With the gradients given, the apply is a sequential float32 recurrence per
@@ -43,7 +43,7 @@ from xflow_amd.config import OptimConfig
 
 F32 = np.float32
 NO_SLOT = 0xFFFFFFFF
-CSR_SHORT_CHAIN = 16   # kCsrShortChain, csrc/hip/kernels_table.hip
+CSR_SHORT_CHAIN = 16   # kCsrShortChain, csrc/hip/kernels_apply.hip
 
 ALL_KERNELS = frozenset({
     "k_apply_lr16<false>", "k_apply_lr16<true>", "k_apply_lr16_multi",
@@ -84,7 +84,7 @@ def apply_kernels(L: Layout, *, gpu: bool, S: int, masks: bool, csr: bool = Fals
                   grouped: bool = False, stash: bool = False, sum_slices: bool = False,
                   pstride: int | None = None) -> frozenset:
     """The kernels one owner apply launches: launch_table_apply's dispatch
-    (csrc/hip/kernels_table.hip, from ``const bool lr16_slot`` to the final
+    (csrc/hip/kernels_apply.hip, from ``const bool lr16_slot`` to the final
     ``k_apply_generic`` branch) as a function of what the callers set.
     grouped: ApplyArgs::grp (s_pull grouped >= 2 active sources and s_apply got
     the same offsets); stash: ApplyArgs::nz_stash (only the LR-FTRL 16-byte
