@@ -574,6 +574,7 @@ StepInputs Engine::step_inputs() const {
   in.lead_handoff = cfg_.lead_handoff;
   in.red_rank = cfg_.red_rank;
   in.red_local = cfg_.red_local;
+  in.red_apply = cfg_.red_apply;
   return in;
 }
 
@@ -683,6 +684,10 @@ StepPlan plan_step(const StepInputs& in, int S) {
   // the one producer that holds every record's bucket before its backward).
   // Does not change the gradient layout.
   p.red_local = in.red_local && p.lead;
+  // FTRL inside the reduction: the bucket-sorted handoff steps whose sums are
+  // ranked -- one slice, one group, 16-byte FTRL slots.  Does not change the
+  // gradient layout (the unique-order array is just never materialised).
+  p.red_apply = in.red_apply && p.red_local && p.red_rank && p.lr16;
   return p;
 }
 
@@ -933,7 +938,10 @@ void Engine::train_step(const BatchView& b) {
     bool pull_zeroes = true;  // (the slice bits instead when several slices run: uq)
   } uo;
   const size_t un = (size_t)cfg_.max_nnz;
-  if (P.lr16) {
+  if (P.red_apply) {
+    // (never materialised: the reduction pushes each sum where it would store it)
+    uo = {nullptr, 1, true, false};
+  } else if (P.lr16) {
     uo = {lr_grad_.ensure(*be_, un * slice_cap_), 1, true, true};
   } else if (P.fmu) {  // (B, C) normalised before the expansion: 2 divisions a key, not P
     uo = {fm_grad_.ensure(*be_, 2 * un * slice_cap_), 2, true, true};
@@ -989,7 +997,7 @@ void Engine::train_step(const BatchView& b) {
     fa.fm_compact = fa.red_pairs && fa.agg_ok && cfg_.model.kind == kFM &&
                     cfg_.model.fm_math == kFmReference;
     if (fm_vals_ && !fa.fm_compact) throw std::logic_error("train_step: compact FM rows need the reduction");
-    if (uo.buf) {
+    if (uo.buf || P.red_apply) {
       fa.red_out = uo.buf;
       // (unique-index positions: the outputs' rows are the dests' own)
       fa.red_inv = upos || P.red_rank ? nullptr : ws_->inv.get();
@@ -1000,7 +1008,17 @@ void Engine::train_step(const BatchView& b) {
       }
       if (uo.normalised) fa.red_rows = srk;
     }
+    if (P.red_apply) {
+      // the apply's inputs: the reduction's launch is the step's last (one
+      // group), and carries the snapshot the apply's would
+      fa.red_apply_words = table_.words;
+      fa.red_apply_slots = uniq_slot_;
+      fa.red_apply_nz = nz;
+      fa.red_apply_ftrl = cfg_.opt.ftrl;
+      attach_snapshot(fa, b.nnz);
+    }
     be_->forward_backward(fa);
+    if (P.red_apply) continue;
 
     ApplyArgs aa = apply_args(uniq_keys_, uniq_slot_, ws_->n_uniq, b.nnz, Sg);
     aa.sum_slices = cfg_.sum_slices;
@@ -1438,15 +1456,19 @@ bool Engine::snap_ready(int64_t seq) const {
 
 // The next snapshot rides on this apply launch (its first wave stores it):
 // valid as long as no insert is queued between it and end_step.
-void Engine::attach_snapshot(ApplyArgs& aa) {
-  if (!be_->is_gpu() || monitor_disabled() || aa.n_max <= 0) return;
+template <typename Args>
+void Engine::attach_snapshot_to(Args& a, int64_t n_max) {
+  if (!be_->is_gpu() || monitor_disabled() || n_max <= 0) return;
   const int64_t seq = snap_seq_ + 1;
   if (seq - 1 - snap_seen_ >= kSnaps) poll_snapshots(seq - kSnaps);  // (ring slot reuse)
-  aa.snap = &snaps_[seq % kSnaps];
-  aa.snap_mon = mon_;
-  aa.snap_seq = (unsigned long long)seq;
+  a.snap = &snaps_[seq % kSnaps];
+  a.snap_mon = mon_;
+  a.snap_seq = (unsigned long long)seq;
   snap_carried_ = true;
 }
+void Engine::attach_snapshot(ApplyArgs& aa) { attach_snapshot_to(aa, aa.n_max); }
+// (a reduction that applies, FwdArgs::red_apply_*: n_max = the batch's occurrences)
+void Engine::attach_snapshot(FwdArgs& fa, int64_t n_max) { attach_snapshot_to(fa, n_max); }
 
 void Engine::poll_snapshots(int64_t wait_upto) {
   while (snap_seen_ < snap_seq_) {

@@ -46,6 +46,8 @@ constexpr int kWave = 64;        // CDNA wavefront width
 constexpr int kBlock = 256;      // 4 waves per workgroup
 // Memory-bound grid cap: 256 CUs x 8 resident 256-thread blocks.
 constexpr int kMaxGrid = 2048;
+// a key without a table slot (not admitted, or no room within the probe bound)
+constexpr u32 kNoSlot = 0xFFFFFFFFu;
 
 inline int grid_for(int64_t n, int block = kBlock, int cap = kMaxGrid) {
   if (n <= 0) return 1;

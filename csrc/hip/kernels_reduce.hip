@@ -76,7 +76,9 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
   constexpr u32 kChunkW = (1u << kCompactChunkLog2) / 32;
   static_assert(kRw <= (u32)kRedBlock && kChunkW == 2 * kWave && kRw % kChunkW == 0,
                 "a unit is whole chunks, a chunk two waves of bitmap words");
-  const bool rank = f.out && f.rk_offs;  // (block-uniform)
+  // FTRL in place of the unique-order store (RedFinal::ap_*, below)
+  const bool apply = kSeg && f.ap_slots;                // (block-uniform)
+  const bool rank = (f.out || apply) && f.rk_offs;      // (block-uniform)
   u32 rk_pre = 0;
   if (rank && threadIdx.x < kRw) {
     const u32 w = threadIdx.x;
@@ -330,6 +332,90 @@ __device__ __forceinline__ void red_sum_unit(u64 lo, u32 beg, u32 end,
       }
     }
   };
+  if constexpr (kSeg) {
+    if (apply) {
+      // The unit's stamped slots are the keys [r0, r0 + cnt) of the unique
+      // list, in slot order (rank_of), and thread t applies the keys r0 + t,
+      // + kRedBlock, ...: the slot and (n, z) reads are dense and the lanes of
+      // the FTRL arithmetic all live, where one lane per slot of the
+      // 4x-headroom scratch would leave four of five idle.  The way from a key
+      // back to its sum goes through the accumulators' own words: dest l's
+      // normalised sum -- a zero sum too: k_apply_lr16 pushes g = 0 -- replaces
+      // the low word of acc[l], written by the thread that read it; after a
+      // barrier (every sum has been read) l goes to the high word of
+      // acc[rank - r0].  Every stamped slot below the capacity leads a tile of
+      // k_lr_lead, so it has a record in this unit and is handled exactly
+      // once -- in the sparse form by the record that claims its bit, as
+      // emit's.
+      constexpr u32 kNone = 0xFFFFFFFFu;
+      const u32 r0 = rpre[0];  // (lo below the capacity, else cnt == 0)
+      u32 cnt = 0;
+#pragma unroll
+      for (u32 i = 0; i < kRw / kWave; ++i) cnt += rwt[i];
+      u32* aw = reinterpret_cast<u32*>(acc);
+      // as emit: normalised like the gather would (lr_worker.cc:116-118, in double)
+      auto put_sum = [&](u32 l) {
+        aw[2 * l] = __float_as_uint((float)(fx_to_double<kFx>(acc[l]) / (double)f.rows[0]));
+      };
+      u32 mine = 0;  // (sparse) the records that claimed their dest
+      if (dense) {
+        for (u32 l = threadIdx.x; l < kR; l += kRedBlock)
+          if (rank_of(l) != kNone) put_sum(l);
+      } else {
+#pragma unroll
+        for (int q = 0; q < kSp; ++q) {
+          const u32 l = lr[q];
+          if (l >= kR) continue;
+          const u32 bit = 1u << (l & 31);
+          if (atomicOr(&cbits[l >> 5], bit) & bit) continue;
+          if (rank_of(l) == kNone) continue;
+          mine |= 1u << q;
+          put_sum(l);
+        }
+      }
+      lds_barrier();
+      if (dense) {
+        for (u32 l = threadIdx.x; l < kR; l += kRedBlock) {
+          const u32 o = rank_of(l);
+          if (o != kNone) aw[2 * (o - r0) + 1] = l;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < kSp; ++q)
+          if (mine & (1u << q)) aw[2 * (rank_of(lr[q]) - r0) + 1] = lr[q];
+      }
+      lds_barrier();
+      // kAp keys' inputs in flight together (indices past the unit's keys are
+      // clamped, not predicated: no branch around a load), then their pushes
+      // and stores.  A unit of more than kAp kRedBlock keys -- a scratch more
+      // than a quarter full -- takes another round, whose loads queue behind
+      // the first round's stores (vmcnt counts both).
+      constexpr int kAp = 4;
+      const FtrlParams fp = f.ap_fp;
+      for (u32 j0 = threadIdx.x; j0 < cnt; j0 += kAp * kRedBlock) {
+        u32 slot[kAp];
+        float2 nz[kAp];
+        float g[kAp];
+#pragma unroll
+        for (int q = 0; q < kAp; ++q) {
+          const u32 j = j0 + (u32)q * kRedBlock;
+          const u32 jc = j < cnt ? j : cnt - 1u;
+          slot[q] = f.ap_slots[r0 + jc];
+          nz[q] = f.ap_nz[r0 + jc];
+          g[q] = __uint_as_float(aw[2 * (aw[2 * jc + 1] & (kR - 1u))]);  // (masked: an index inside the unit, whatever the word)
+        }
+#pragma unroll
+        for (int q = 0; q < kAp; ++q) {
+          // (kNoSlot: not admitted, or the table had no room)
+          if (j0 + (u32)q * kRedBlock >= cnt || slot[q] == kNoSlot) continue;
+          const float w = ftrl_weight(nz[q].y, nz[q].x, fp);
+          ftrl_push(nz[q].x, nz[q].y, w, g[q], fp);
+          *reinterpret_cast<float2*>(f.ap_words + (u64)slot[q] * 4 + 2) = nz[q];
+        }
+      }
+      return;
+    }
+  }
   if (dense) {
     for (u32 l = threadIdx.x; l < kR; l += kRedBlock)
       emit(l, f.masks && ((pbits[l >> 5] >> (l & 31)) & 1u));
@@ -404,8 +490,16 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum(const void* __restrict__ 
 // wave has more than the 2 kRedUnroll rows its lanes have record slots for
 // (and at most kWave segments), else dense.  Nothing here depends on another
 // workgroup of this launch.
+// snap: the step's capacity snapshot, when this launch stands in for the
+// apply's (RedFinal::ap_*): the pulls and the forward have completed.
+struct RedSnap {
+  HostSnap* dst = nullptr;
+  const u32* mon = nullptr;
+  unsigned long long seq = 0;
+};
 __global__ void __launch_bounds__(kRedBlock) k_red_sum_local(LeadSegs sg, RedFinal f, RedGeom geom,
-                                                             int nb) {
+                                                             int nb, RedSnap snap) {
+  if (snap.dst) store_snapshot(snap.dst, snap.mon, snap.seq);
   constexpr int kShift = red_shift(1);
   constexpr u32 kR = 1u << kShift;
   constexpr u32 kWaves = kRedBlock / kWave;
@@ -681,7 +775,17 @@ static RedFinal red_final(const FwdArgs& a) {
   RedFinal f{a.grad, a.wpull, a.S, a.model.pstride(), a.model.v_dim,
              a.red_out, a.red_inv, a.red_rows, NV == 2 && a.fm_compact,
              a.S > 1 ? a.red_masks : nullptr};
-  if (a.red_rank_offs && a.red_out) {
+  if (a.red_apply_slots) {
+    // (the sums are pushed where they would be stored: k_red_sum_local's ranks)
+    if (NV != 1 || !a.red_local || a.red_out || !a.red_rank_offs || !a.red_rows ||
+        !a.red_apply_words || !a.red_apply_nz)
+      throw std::runtime_error("red_apply: the ranked bucket-sorted LR step only (plan_step)");
+    f.ap_words = a.red_apply_words;
+    f.ap_slots = a.red_apply_slots;
+    f.ap_nz = reinterpret_cast<const float2*>(a.red_apply_nz);
+    f.ap_fp = a.red_apply_ftrl;
+  }
+  if (a.red_rank_offs && (a.red_out || a.red_apply_slots)) {
     // (dests are slots, the slice bits' bitmap is free for the stamps)
     if (a.S != 1 || a.red_nuq || !a.red_rank_stamps || !a.red_bcap)
       throw std::runtime_error("red_rank: one slice, slot positions, the batch's stamps and capacity");
@@ -710,8 +814,10 @@ void launch_reduction(const FwdArgs& a, int groups, int rows_per_group, hipStrea
     sg.groups = (u32)groups;
     sg.gcap = (u32)(kLeadTile * b.nnz_per_row);
     const u32 grid = std::min<u32>((u32)(a.red_nb * a.red_nsub), (u32)device_cus());
+    RedSnap snap;
+    if (a.red_apply_slots) snap = {a.snap, a.snap_mon, a.snap_seq};
     hipLaunchKernelGGL(k_red_sum_local, dim3(grid), dim3(kRedBlock), 0, st, sg, red_final<1>(a),
-                       red_geom(a), a.red_nb);
+                       red_geom(a), a.red_nb, snap);
     return;
   }
   u32* start = a.red_tot + a.red_nb + 1;

@@ -540,6 +540,13 @@ struct RedFinal {
   const unsigned char* rk_stamps = nullptr;
   const unsigned long long* rk_cap = nullptr;  // slots the compaction covered (FwdArgs::red_bcap)
   u32 rk_epoch = 0;
+  // (k_red_sum_local, rk_offs, no out) FTRL in place of the store
+  // (FwdArgs::red_apply_*): the table's words, and in unique order the keys'
+  // table slots and pulled (n, z); ap_slots null: off
+  u32* ap_words = nullptr;
+  const u32* ap_slots = nullptr;
+  const float2* ap_nz = nullptr;
+  FtrlParams ap_fp;
 };
 
 // Slice bits of one slot from the presence bitmap: its dests slot*S + s that

@@ -14,7 +14,6 @@
 namespace xflow {
 namespace hip {
 
-constexpr u32 kNoSlot = 0xFFFFFFFFu;
 // grid cap of the lane-group pull/apply kernels (8 K workgroups of 256: four
 // resident rounds; their grid-stride loops pipeline the random row accesses,
 // see RowPipe -- 16 K measured 2 % slower on FM-8, 64 K 6 %)

@@ -305,6 +305,20 @@ struct FwdArgs {
   const u32* red_rank_offs = nullptr;
   const unsigned char* red_rank_stamps = nullptr;
   u32 red_rank_epoch = 0;
+  // FTRL inside the reduction (StepPlan::red_apply; HIP, with red_local and
+  // red_rank_*, LR-FTRL on 16-byte slots): k_red_sum_local stores no red_out
+  // (null here).  It pushes the normalised sum of every stamped slot onto the
+  // (n, z) the pull stashed at the slot's unique index and stores the state
+  // to the key's table slot -- k_apply_lr16's arithmetic on k_apply_lr16's
+  // inputs, every key once, keys without a table slot (kNoSlot) skipped.
+  // snap: the step's capacity snapshot rides on that launch (ApplyArgs::snap).
+  u32* red_apply_words = nullptr;        // TableView::words
+  const u32* red_apply_slots = nullptr;  // [unique] table slots
+  const float* red_apply_nz = nullptr;   // [unique][2] PullArgs::out_nz
+  FtrlParams red_apply_ftrl;
+  struct HostSnap* snap = nullptr;
+  const u32* snap_mon = nullptr;
+  unsigned long long snap_seq = 0;
   // Reference-math FM on the reduction path: keep only (B, C) = (Σ loss,
   // Σ loss*vsum) in the first two floats of each gradient row; the apply
   // expands them with the key's pre-step weights (ApplyArgs::fm_compact).

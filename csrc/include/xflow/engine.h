@@ -98,6 +98,12 @@ struct EngineConfig {
   // passes.  false keeps them everywhere (the A/B switch -- the results are
   // bit-equal either way).
   bool red_local = true;
+  // FTRL applied inside the bucket reduction (StepPlan::red_apply)
+  // on the bucket-sorted handoff steps with ranked outputs: the thread that
+  // would store a key's normalised sum pushes it instead, so the step has no
+  // unique-order gradient array and no apply launch.  false keeps both (the
+  // A/B switch -- the results are bit-equal either way).
+  bool red_apply = true;
   // Delta checkpoints (docs/DESIGN.md §2): a filter of 2^delta_log2 bits in
   // device memory, indexed by key hash (delta_bit, common.h), in which every
   // key whose state may have changed is marked -- by a launch of its own
@@ -152,6 +158,7 @@ struct StepInputs {
   double rows = 0.0, fields = 0.0;
   bool red_rank = true;  // EngineConfig::red_rank
   bool red_local = true;  // EngineConfig::red_local
+  bool red_apply = true;  // EngineConfig::red_apply
 };
 
 // Where a step's gradients land, one per step:
@@ -194,6 +201,10 @@ struct StepPlan {
   // with lead: k_lr_lead writes its records sorted by bucket and the sums read
   // them in place (FwdArgs::red_local): no k_red_scan, no k_red_scatter
   bool red_local = false;
+  // with red_local, red_rank and lr16 (one slice, one group, FTRL on 16-byte
+  // slots, slot positions, ranked outputs): k_red_sum_local pushes each key's
+  // sum itself (FwdArgs::red_apply_*): no lr_grad_, no table_apply
+  bool red_apply = false;
 };
 
 StepPlan plan_step(const StepInputs& in, int S);
@@ -732,6 +743,9 @@ class Engine {
   bool snap_ready(int64_t seq) const;
   void close_snapshot();
   void attach_snapshot(ApplyArgs& aa);
+  void attach_snapshot(FwdArgs& fa, int64_t n_max);
+  template <typename Args>
+  void attach_snapshot_to(Args& a, int64_t n_max);
   int64_t snap_seq_ = 0;            // snapshots recorded
   int64_t snap_seen_ = 0;           // snapshots consumed (all older ones complete)
   int64_t known_size_ = 0;          // table size at the last consumed snapshot (or sync)

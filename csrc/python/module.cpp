@@ -137,6 +137,7 @@ StepInputs inputs_from(py::dict d) {
   in.lead_handoff = flag("lead_handoff", true);
   in.red_rank = flag("red_rank", true);
   in.red_local = flag("red_local", true);
+  in.red_apply = flag("red_apply", true);
   in.field_major = flag("field_major", false);
   in.rows = d.contains("rows") ? d["rows"].cast<double>() : 0.0;
   in.fields = d.contains("fields") ? d["fields"].cast<double>() : 0.0;
@@ -150,7 +151,21 @@ PYBIND11_MODULE(_xflow_native, m) {
 
   m.def("hip_available", &hip_backend_available);
   // the single-rank step's layout decisions for hypothetical inputs (tests)
-  m.def("plan_step", [](py::dict inputs, int S) { return plan_dict(plan_step(inputs_from(inputs), S)); });
+  // (batch: with the entries that follow lead -- red_local, red_apply -- as
+  // Engine.step_plan reports them; callers that compare plans with "lead"
+  // left out leave it off)
+  m.def(
+      "plan_step",
+      [](py::dict inputs, int S, bool batch) {
+        const StepPlan p = plan_step(inputs_from(inputs), S);
+        py::dict d = plan_dict(p);
+        if (batch) {
+          d["red_local"] = p.red_local;
+          d["red_apply"] = p.red_apply;
+        }
+        return d;
+      },
+      py::arg("inputs"), py::arg("S"), py::arg("batch") = false);
   // The reference's pred_<rank>_<block>.txt (lr_worker.cc:65-68: `pctr \t
   // 1-label \t label`, ostream default float format = %g): formatted into one
   // buffer and written with a single fwrite, without the GIL.
@@ -410,9 +425,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int monitor_lag, int owner_group, double grow_start, bool csr,
                        int admit_min_count, int admit_log2, bool lead_handoff,
                        bool scratch_carry, bool red_rank, bool delta_track, int delta_log2,
-                       bool red_local) {
+                       bool red_local, bool red_apply) {
              EngineConfig c;
              c.red_local = red_local;
+             c.red_apply = red_apply;
              c.delta_track = delta_track;
              c.delta_log2 = delta_log2;
              c.red_rank = red_rank;
@@ -447,7 +463,8 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("csr") = true, py::arg("admit_min_count") = 1, py::arg("admit_log2") = 0,
            py::arg("lead_handoff") = true, py::arg("scratch_carry") = true,
            py::arg("red_rank") = true, py::arg("delta_track") = false,
-           py::arg("delta_log2") = 0, py::arg("red_local") = true)
+           py::arg("delta_log2") = 0, py::arg("red_local") = true,
+           py::arg("red_apply") = true)
       // delta checkpoints (EngineConfig::delta_track)
       .def("delta_count", &Engine::delta_count, py::call_guard<py::gil_scoped_release>())
       .def("delta_export",
@@ -514,6 +531,7 @@ PYBIND11_MODULE(_xflow_native, m) {
              const StepPlan p = e.plan(S, rows, fields, field_major);
              py::dict d = plan_dict(p);
              d["red_local"] = p.red_local;
+             d["red_apply"] = p.red_apply;
              return d;
            },
            py::arg("S"), py::arg("rows") = 0, py::arg("fields") = 0, py::arg("field_major") = false)

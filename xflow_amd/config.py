@@ -170,6 +170,11 @@ class EngineConfig:
     # them in place, without the reduction's scan and scatter passes; False
     # keeps the passes (bit-equal results, the A/B switch)
     red_local: bool = True
+    # bucket-sorted handoff steps with ranked outputs (docs/DESIGN.md §3): the
+    # reduction pushes each key's FTRL update itself, so the step has no
+    # unique-order gradient array and no apply launch; False keeps both
+    # (bit-equal results, the A/B switch)
+    red_apply: bool = True
     # delta checkpoints (docs/DESIGN.md §2): mark every key whose state may
     # have changed in a filter of 2^delta_log2 bits indexed by key hash, so
     # that Engine.save_delta writes only those keys.  delta_log2: 10..34,

@@ -207,6 +207,7 @@ class Engine:
                            scratch_carry=self.cfg.scratch_carry,
                            red_rank=self.cfg.red_rank,
                            red_local=self.cfg.red_local,
+                           red_apply=self.cfg.red_apply,
                            delta_track=self.cfg.delta_track,
                            delta_log2=self.cfg.delta_log2)
         if self.is_gpu != (self.device.type == "cuda"):
