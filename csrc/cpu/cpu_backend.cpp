@@ -548,6 +548,22 @@ class CpuBackend final : public Backend {
     }
     return n;
   }
+  int64_t table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
+                               float* weights_out, int64_t max_rows) override {
+    const TableLayout& L = t.L;
+    int64_t n = 0;
+    for (u64 s = 0; s < t.cap; ++s) {
+      const u32* sp = t.words + s * (u64)L.stride;
+      const u64 key = *reinterpret_cast<const u64*>(sp);
+      if (key == kEmptyKey || !slot_exported(sp, key, L, o)) continue;
+      if (n < max_rows) {
+        keys_out[n] = key;
+        for (int p = 0; p < L.P; ++p) weights_out[n * L.P + p] = slot_weight(sp, key, p, L, o);
+      }
+      ++n;
+    }
+    return n;
+  }
   int64_t delta_popcount(const u32* bits, int L) override {
     int64_t n = 0;
     for (u64 i = 0; i < (1ull << (L - 5)); ++i) n += __builtin_popcount(bits[i]);

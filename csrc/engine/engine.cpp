@@ -24,6 +24,7 @@ uint64_t next_pow2(uint64_t v) {
 }
 
 constexpr char kMagic[8] = {'X', 'F', 'L', 'O', 'W', 'T', 'B', '1'};
+constexpr char kServingMagic[8] = {'X', 'F', 'L', 'O', 'W', 'S', 'W', '1'};
 
 // XFLOW_NO_MONITOR=1: no per-step capacity snapshot (A/B of the monitor's
 // cost only; growth then relies on exact-size reads, overflow on the
@@ -54,7 +55,27 @@ const EngineConfig& Engine::validated(const EngineConfig& cfg) {
     throw std::invalid_argument("delta_log2 must be 0 (automatic) or in [10, 34]");
   if (next_pow2((uint64_t)((double)cfg.max_nnz * cfg.scratch_factor) + 1) > (1ull << 31))
     throw std::invalid_argument("max_nnz too large");
+  if (cfg.opt.kind != kFTRL && cfg.opt.kind != kSGD && cfg.opt.kind != kFrozen)
+    throw std::invalid_argument("optimizer kind must be 0 (FTRL), 1 (SGD) or 2 (frozen)");
+  if (cfg.opt.kind == kFrozen) {
+    if (cfg.opt.frozen_from != kFTRL && cfg.opt.frozen_from != kSGD)
+      throw std::invalid_argument("frozen_from must be 0 (FTRL) or 1 (SGD)");
+    // (read-only: nothing is admitted and nothing is tracked)
+    if (cfg.admit_min_count > 1)
+      throw std::runtime_error("admit_min_count > 1: this engine holds a serving snapshot "
+                               "(frozen, read-only): it admits no keys");
+    if (cfg.delta_track)
+      throw std::runtime_error("delta_track: this engine holds a serving snapshot (frozen, "
+                               "read-only): it has no deltas to save");
+  }
   return cfg;
+}
+
+void Engine::refuse_frozen(const char* what) const {
+  if (frozen())
+    throw std::runtime_error(std::string(what) + ": this engine holds a serving snapshot "
+                             "(frozen, read-only weights): it cannot be trained, pruned or "
+                             "saved as a training checkpoint");
 }
 
 Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
@@ -217,6 +238,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   // reference-math FM with the GPU reduction: compact (w, Σv, Σv^2, 0) value rows
   fm_vals_ = red_pairs_ && fm_ref;
   vstride_ = fm_vals_ ? 4 : ps;
+  serve_lr_ = frozen() && cfg_.serve_fused && cfg_.model.kind == kLR && be.serves_lr();
   wpull_.alloc(be, rows1 * vstride_);
   be.memset(wpull_ + scratch_.cap * vstride_, 0, sizeof(float) * vstride_);
   stats_.alloc_zero(be, 2);
@@ -821,6 +843,7 @@ void Engine::apply_by_source(const ApplyArgs& base, const std::vector<int64_t>& 
 
 void Engine::s_apply_csr(const u64* recv_keys, const u32* recv_cnt, const void* recv_ent,
                          const std::vector<int64_t>& src_offsets, int S, int buf) {
+  refuse_frozen("s_apply_csr");
   if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
   SrvBuf& sb = srv_[buf];
   sb.keys = nullptr;  // applied: no slot remap needed after a growth
@@ -908,6 +931,7 @@ Engine::RedGeometry Engine::red_geometry(int S, int64_t nuq) {
 }
 
 void Engine::train_step(const BatchView& b) {
+  refuse_frozen("train_step");
   stale_stashes();  // the table changes: server stashes are stale
   use_worker_set(0);
   const int S = slices_of(b);
@@ -1068,6 +1092,17 @@ PullArgs Engine::begin_fused_step(const BatchView& b, bool want_inv, bool upos, 
 }
 
 void Engine::eval_step(const BatchView& b, float* pctr) {
+  // (a frozen LR table: lookup and score in one launch, but for the batch
+  // sizes at which the three launches measured faster)
+  if (serve_lr_ && !(b.rows >= cfg_.serve_unfused_lo && b.rows < cfg_.serve_unfused_hi)) {
+    ServeLrArgs sa;
+    sa.table = table_;
+    sa.batch = b;
+    sa.pctr = pctr;
+    sa.stats = stats_ + 1;
+    be_->serve_lr(sa);
+    return;
+  }
   use_worker_set(0);
   dedup_(b);
   PullArgs pa = pull_args(uniq_keys_, ws_->n_uniq, b.nnz, false, uniq_slot_);
@@ -1087,6 +1122,7 @@ void Engine::ensure_host_staging(int64_t n) {
 }
 
 void Engine::push_host(const std::vector<u64>& keys, const std::vector<float>& grads) {
+  refuse_frozen("push");
   stale_stashes();  // the table changes: server stashes are stale
   const int64_t n = (int64_t)keys.size();
   const int P = cfg_.model.P();
@@ -1213,6 +1249,7 @@ void Engine::w_forward(const BatchView& b, const float* pulled, int64_t n_send, 
 
 void Engine::s_pull(const u64* recv_keys, int64_t n, float* out_vals, bool insert, int buf,
                     const std::vector<int64_t>& src_offsets, bool keep_weights) {
+  if (insert) refuse_frozen("s_pull(insert=True)");
   ensure_server_capacity(n, buf);
   SrvBuf& sb = srv_[buf];
   sb.n = n;
@@ -1382,6 +1419,7 @@ void Engine::w_forward_backward(const BatchView& b, const float* pulled, int64_t
 
 void Engine::s_apply(const u64* recv_keys, const float* recv_grads, const u32* recv_masks,
                      const std::vector<int64_t>& src_offsets, int S, int buf) {
+  refuse_frozen("s_apply");
   if (buf < 0 || buf >= kSrvBufs) throw std::invalid_argument("server buffer must be in [0, kSrvBufs)");
   SrvBuf& sb = srv_[buf];
   sb.keys = nullptr;  // applied: no slot remap needed after a growth
@@ -1693,6 +1731,7 @@ int64_t Engine::table_size() {
 // touched.  Capacity is not given back: the point is a lower load, shorter
 // chains and later growth.
 int64_t Engine::prune(float max_n) {
+  refuse_frozen("prune");
   if (std::isnan(max_n)) throw std::invalid_argument("prune: max_n must not be NaN");
   if (snap_carried_) close_snapshot();  // (as guard_inserts: it predates the prune)
   poll_snapshots(snap_seq_);
@@ -1983,6 +2022,7 @@ void Engine::import_table(const std::vector<u64>& keys, const std::vector<u32>& 
 // Shard file: the device export streams chunk by chunk from the staging
 // buffers to the file (no whole-table host copy).
 void Engine::save(const std::string& path) {
+  refuse_frozen("save");
   const int W = state_words();
   const int64_t n = table_size();
   std::FILE* f = std::fopen(path.c_str(), "wb");
@@ -2048,6 +2088,7 @@ void Engine::delta_export(std::vector<u64>& keys, std::vector<u32>& words) {
 
 // Engine::save's format with hdr[7] = 1; the device buffers hold the delta only.
 void Engine::save_delta(const std::string& path) {
+  refuse_frozen("save_delta");
   if (!delta_bits_) throw std::runtime_error("save_delta: delta tracking is off");
   const int W = state_words();
   DeviceBuffer<u64> dk;
@@ -2070,6 +2111,80 @@ void Engine::save_delta(const std::string& path) {
   }
   ok = (std::fclose(f) == 0) && ok;
   if (!ok) throw std::runtime_error("write failed: " + path);
+}
+
+// ---------------------------------------------------------------------------
+// serving snapshots
+// ---------------------------------------------------------------------------
+int64_t Engine::export_weights_count() {
+  return be_->table_export_weights(table_, cfg_.opt, nullptr, nullptr, 0);
+}
+
+int64_t Engine::weights_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<float>& dw) {
+  const int64_t n = export_weights_count();
+  if (n == 0) return 0;
+  dk.alloc(*be_, (size_t)n);
+  dw.alloc(*be_, (size_t)n * table_.L.P);
+  if (be_->table_export_weights(table_, cfg_.opt, dk, dw, n) != n)
+    throw std::runtime_error("export_weights: key count changed between the passes");
+  return n;
+}
+
+void Engine::export_weights(std::vector<u64>& keys, std::vector<float>& weights) {
+  const int P = table_.L.P;
+  DeviceBuffer<u64> dk;
+  DeviceBuffer<float> dw;
+  const int64_t n = weights_to_device(dk, dw);
+  keys.resize((size_t)n);
+  weights.resize((size_t)n * P);
+  if (n == 0) return;
+  d2h_stream(dk, sizeof(u64) * n, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)keys.data() + o, c, b);
+  });
+  d2h_stream(dw, sizeof(float) * n * P, [&](const void* c, size_t o, size_t b) {
+    par_copy((char*)weights.data() + o, c, b);
+  });
+}
+
+int64_t Engine::save_serving(const std::string& path) {
+  const int P = table_.L.P;
+  DeviceBuffer<u64> dk;
+  DeviceBuffer<float> dw;
+  const uint64_t total = (uint64_t)table_size();
+  const int64_t n = weights_to_device(dk, dw);
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot open " + path);
+  const int32_t hdr[6] = {cfg_.model.kind, cfg_.model.v_dim, cfg_.model.fm_math,
+                          cfg_.model.mvm_math, P,
+                          frozen() ? cfg_.opt.frozen_from : cfg_.opt.kind};
+  const uint64_t un = (uint64_t)n;
+  bool ok = std::fwrite(kServingMagic, 1, 8, f) == 8;
+  ok = ok && std::fwrite(hdr, sizeof(hdr), 1, f) == 1;
+  ok = ok && std::fwrite(&total, sizeof(total), 1, f) == 1;
+  ok = ok && std::fwrite(&un, sizeof(un), 1, f) == 1;
+  if (n > 0 && ok) {
+    auto put = [&](const void* c, size_t, size_t b) {
+      ok = ok && std::fwrite(c, 1, b, f) == b;
+    };
+    d2h_stream(dk, sizeof(u64) * n, put);
+    d2h_stream(dw, sizeof(float) * n * P, put);
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  if (!ok) throw std::runtime_error("write failed: " + path);
+  return n;
+}
+
+void Engine::import_weights(const u64* keys, const float* weights, int64_t n) {
+  if (!frozen())
+    throw std::runtime_error("import_weights: only a frozen engine (a serving snapshot) "
+                             "stores resolved weights");
+  if (n <= 0) return;
+  // (a frozen slot's state words: the P weights' bits, then the 16-byte padding)
+  const int W = state_words(), P = table_.L.P;
+  std::vector<u32> words((size_t)n * W, 0u);
+  for (int64_t i = 0; i < n; ++i)
+    std::memcpy(words.data() + (size_t)i * W, weights + (size_t)i * P, sizeof(float) * P);
+  import_from(keys, words.data(), n);
 }
 
 void Engine::delta_clear() {

@@ -436,6 +436,15 @@ class HipBackend final : public Backend {
     copy_d2h(&n, counter_, sizeof(n));
     return (int64_t)n;
   }
+  int64_t table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
+                               float* weights_out, int64_t max_rows) override {
+    hip::launch_table_export_weights(t, o, keys_out, weights_out, max_rows, counter_, stream_);
+    unsigned long long n = 0;
+    copy_d2h(&n, counter_, sizeof(n));
+    return (int64_t)n;
+  }
+  bool serves_lr() const override { return true; }
+  void serve_lr(const ServeLrArgs& a) override { hip::launch_serve_lr(a, stream_); }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

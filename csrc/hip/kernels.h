@@ -64,6 +64,13 @@ void launch_table_export_marked(const TableView& t, const u32* bits, int L, u64*
                                 u32* words_out, int64_t max_rows, unsigned long long* counter,
                                 hipStream_t st);
 void launch_delta_popcount(const u32* bits, int L, unsigned long long* counter, hipStream_t st);
+// serving snapshots: the slot_exported keys and their P resolved weights
+void launch_table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
+                                 float* weights_out, int64_t max_rows,
+                                 unsigned long long* counter, hipStream_t st);
+
+// kernels_serve.hip
+void launch_serve_lr(const ServeLrArgs& a, hipStream_t st);
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

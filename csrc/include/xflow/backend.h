@@ -666,6 +666,18 @@ inline void check_shuffle_args(const ShuffleArgs& a) {
     throw std::invalid_argument("shuffle_rows: null array");
 }
 
+// One-launch LR scoring from a frozen table (Backend::serve_lr, HIP:
+// kernels_serve.hip): every occurrence of the batch probes the table itself
+// and a row's weights are summed in occurrence order -- no dedup scratch, no
+// pulled-weights buffer.  An absent key adds 0.0f.  pctr[r] =
+// sigmoid_ref(sum); stats (optional) accumulate like the forward's.
+struct ServeLrArgs {
+  TableView table;                 // LR, kFrozen: 16-byte slots {key, w, pad}
+  BatchView batch;                 // any of the three layouts
+  float* pctr = nullptr;           // [rows] optional
+  LossStats* stats = nullptr;      // optional
+};
+
 struct SynthArgs {                 // synthetic Criteo-shaped batch generator
   u64* keys = nullptr;
   float* labels = nullptr;
@@ -1037,6 +1049,18 @@ class Backend {
   virtual int64_t table_export_marked(const TableView& t, const u32* bits, int L, u64* keys_out,
                                       u32* words_out, int64_t max_rows) = 0;
   virtual int64_t delta_popcount(const u32* bits, int L) = 0;
+  // Serving snapshots: table_export restricted to the keys that meet
+  // slot_exported (types.h), written as P resolved weights per key instead of
+  // state words (max_rows = 0 only counts).  Returns the number of such keys.
+  virtual int64_t table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
+                                       float* weights_out, int64_t max_rows) = 0;
+  // One-launch lookup-and-score of an LR batch from a frozen table
+  // (ServeLrArgs; HIP only -- the CPU backend has no launches to save)
+  virtual bool serves_lr() const { return false; }
+  virtual void serve_lr(const ServeLrArgs& a) {
+    (void)a;
+    throw std::runtime_error("serve_lr is not supported by this backend");
+  }
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

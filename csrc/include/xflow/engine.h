@@ -115,6 +115,22 @@ struct EngineConfig {
   // never grows.  false: no filter exists and no launch is added.
   bool delta_track = false;
   int delta_log2 = 0;
+  // A frozen engine (OptSpec::kind == kFrozen: a serving snapshot)
+  // scores LR batches with the one-launch lookup-and-score kernel
+  // (Backend::serve_lr) where the backend has one; false -- or FM / MVM --
+  // runs eval_step's dedup -> pull -> forward as on a training engine (the A/B
+  // switch).  Ignored by engines that are not frozen.
+  bool serve_fused = true;
+  // ... except for batches of serve_unfused_lo <= rows < serve_unfused_hi,
+  // which take the three-launch path (tests/test_serving_snapshot.py holds
+  // the two paths to the same bits).  profiles/serve.txt (tools/serve_bench.py,
+  // rows x 39 fields): the one-launch kernel is ahead at 1, 8, 16 and 32 rows
+  // and from 256 rows up, and 6 % behind at 64 and 128 rows (0.0400 against
+  // 0.0378 ms, 0.0418 against 0.0395) -- one or two waves walk their rows'
+  // dependent probe rounds alone.  The window is [first size measured behind,
+  // first size measured ahead again).  lo >= hi: always one launch.
+  int64_t serve_unfused_lo = 64;
+  int64_t serve_unfused_hi = 256;
 };
 
 // Engine::delta_stats
@@ -470,6 +486,25 @@ class Engine {
   // Binary shard file: header + keys + state words.
   void save(const std::string& path);
   void load(const std::string& path);
+  // ---- serving snapshots (docs/DESIGN.md §2) -----------------------------
+  // The keys whose weights differ from what an absent key reads
+  // (slot_exported, types.h) and their P resolved fp32 weights each: a count
+  // pass, device buffers of exactly that size, then the export -- the peak
+  // extra device memory is the snapshot, not the table.  Syncs.
+  int64_t export_weights_count();
+  void export_weights(std::vector<u64>& keys, std::vector<float>& weights);
+  // The same as a file: magic "XFLOWSW1", int32 {model kind, v_dim, fm_math,
+  // mvm_math, P, source optimiser kind}, u64 keys of this table, u64 n, keys
+  // u64[n], weights f32[n][P].  Returns n.
+  int64_t save_serving(const std::string& path);
+  // Insert n (key, P weights) pairs into this frozen engine's table (the
+  // import path with words = weight bits); throws on any other engine.
+  void import_weights(const u64* keys, const float* weights, int64_t n);
+  // this engine holds a serving snapshot: read-only, every training entry
+  // point, prune and the training checkpoints throw
+  bool frozen() const { return cfg_.opt.kind == kFrozen; }
+  // eval_step runs the one-launch LR kernel (EngineConfig::serve_fused)
+  bool serve_fused() const { return serve_lr_; }
   // ---- delta checkpoints (EngineConfig::delta_track) ----------------------
   // The table's keys whose filter bit is set: their number (a count pass;
   // syncs), host copies of them and their state words (count pass, device
@@ -595,6 +630,10 @@ class Engine {
   }
   bool fm_vals_ = false;
   int vstride_ = 1;
+  bool serve_lr_ = false;  // frozen LR on a backend with serve_lr, serve_fused on
+  // throws "<what>: this engine holds a serving snapshot ..." when frozen
+  void refuse_frozen(const char* what) const;
+  int64_t weights_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<float>& dw);
   const float* pulled_weights(int buf, int64_t off) const;
 
   // worker buffers (backend memory)

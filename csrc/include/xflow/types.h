@@ -10,7 +10,9 @@ namespace xflow {
 
 // Model families of the reference (src/model/{lr,fm,mvm}).
 enum ModelKind : int { kLR = 0, kFM = 1, kMVM = 2 };
-enum OptKind : int { kFTRL = 0, kSGD = 1 };
+// kFrozen: a read-only table of resolved fp32 weights (a serving snapshot,
+// docs/DESIGN.md §2): one word per param, the weight itself, no pushed flag.
+enum OptKind : int { kFTRL = 0, kSGD = 1, kFrozen = 2 };
 
 // FM interaction math.  kFmReference reproduces fm_worker.cc:159-202 /
 // :126-157 (y = wx + (Σ_k Σ_f v)^2 - Σ_k Σ_f v^2, w-grad accumulated D times);
@@ -64,12 +66,16 @@ struct OptSpec {
   SgdParams sgd;
   float v_init_scale = 1e-2f;  // ftrl.h:117
   uint64_t seed = 0x5eed;
+  // kFrozen: the optimiser the snapshot was exported from (kFTRL or kSGD).
+  // It decides what a key that is not in the table reads (absent_weight)
+  int frozen_from = kFTRL;
 };
 
 // Slot layout of the HBM-resident open-addressing table, in 32-bit words:
 //   [0,1]  u64 key (kEmptyKey when free)
-//   [2, 2+sp*P)  optimizer state: FTRL (n,z) pairs, SGD w
-//   [2+sp*P]     pushed flag (only when the model has latent params)
+//   [2, 2+sp*P)  optimizer state: FTRL (n,z) pairs, SGD w, frozen w
+//   [2+sp*P]     pushed flag (only when the model has latent params; never
+//                in a frozen table: every stored weight is resolved)
 // padded to a multiple of 4 words (16 B).  LR-FTRL is exactly 16 B/slot.
 struct TableLayout {
   int P = 1;
@@ -89,7 +95,7 @@ struct TableLayout {
     t.p_w = m.p_w();
     t.opt = o.kind;
     t.sp = (o.kind == kFTRL) ? 2 : 1;
-    t.has_flag = (t.P > t.p_w) ? 1 : 0;
+    t.has_flag = (t.P > t.p_w && o.kind != kFrozen) ? 1 : 0;
     t.flag_word = 2 + t.sp * t.P;
     int words = 2 + t.sp * t.P + t.has_flag;
     t.stride = (words + 3) & ~3;
@@ -141,12 +147,34 @@ XF_HD bool slot_prunable(const u32* slot, u64 key, const TableLayout& L, const O
 }
 
 // Weight of a key that is not in the table (lookup-only pulls at eval time).
+// A frozen table answers with its source optimiser's init (OptSpec::frozen_from).
 XF_HD float absent_weight(u64 key, int p, const TableLayout& L, const OptSpec& o) {
   if (p >= L.p_w) {
-    return L.opt == kFTRL ? normal_init(key, (u32)(p - L.p_w), o.seed) * o.v_init_scale
-                          : o.sgd.v_init;
+    const int from = L.opt == kFrozen ? o.frozen_from : L.opt;
+    return from == kFTRL ? normal_init(key, (u32)(p - L.p_w), o.seed) * o.v_init_scale
+                         : o.sgd.v_init;
   }
   return 0.0f;
+}
+
+// Export rule of a serving snapshot (Backend::table_export_weights): the key
+// in `slot` is written, with its P resolved weights, unless every one of them
+// has the bit pattern an absent key reads -- compared as u32, so -0.0, +0.0
+// and NaN need no argument.  What follows from it: LR drops every key of
+// weight +0.0; a latent-param key whose pushed flag is unset reads its lazy
+// init and is dropped; a pushed one is kept even when L1 zeroed its latents,
+// since an absent key would read the non-zero init.  By construction a pull
+// of any key returns the same bits from the snapshot as from this table.
+XF_HD u32 weight_bits(float w) {
+  u32 b;
+  __builtin_memcpy(&b, &w, sizeof(b));
+  return b;
+}
+XF_HD bool slot_exported(const u32* slot, u64 key, const TableLayout& L, const OptSpec& o) {
+  for (int p = 0; p < L.P; ++p)
+    if (weight_bits(slot_weight(slot, key, p, L, o)) != weight_bits(absent_weight(key, p, L, o)))
+      return true;
+  return false;
 }
 
 // Apply one push of gradient g to param p of `slot` (slot lock-free: callers

@@ -81,6 +81,7 @@ OptSpec opt_from(py::dict d) {
   if (d.contains("sgd_v_init")) o.sgd.v_init = d["sgd_v_init"].cast<float>();
   if (d.contains("v_init_scale")) o.v_init_scale = d["v_init_scale"].cast<float>();
   if (d.contains("seed")) o.seed = d["seed"].cast<uint64_t>();
+  if (d.contains("frozen_from")) o.frozen_from = d["frozen_from"].cast<int>();
   return o;
 }
 
@@ -425,8 +426,12 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int monitor_lag, int owner_group, double grow_start, bool csr,
                        int admit_min_count, int admit_log2, bool lead_handoff,
                        bool scratch_carry, bool red_rank, bool delta_track, int delta_log2,
-                       bool red_local, bool red_apply) {
+                       bool red_local, bool red_apply, bool serve_fused,
+                       int64_t serve_unfused_lo, int64_t serve_unfused_hi) {
              EngineConfig c;
+             c.serve_fused = serve_fused;
+             c.serve_unfused_lo = serve_unfused_lo;
+             c.serve_unfused_hi = serve_unfused_hi;
              c.red_local = red_local;
              c.red_apply = red_apply;
              c.delta_track = delta_track;
@@ -464,7 +469,35 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("lead_handoff") = true, py::arg("scratch_carry") = true,
            py::arg("red_rank") = true, py::arg("delta_track") = false,
            py::arg("delta_log2") = 0, py::arg("red_local") = true,
-           py::arg("red_apply") = true)
+           py::arg("red_apply") = true, py::arg("serve_fused") = true,
+           py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256)
+      // serving snapshots (docs/DESIGN.md §2)
+      .def_property_readonly("frozen", &Engine::frozen)
+      .def_property_readonly("serve_fused", &Engine::serve_fused)
+      .def("export_weights_count", &Engine::export_weights_count,
+           py::call_guard<py::gil_scoped_release>())
+      .def("export_weights",
+           [](Engine& e) {
+             std::vector<u64> k;
+             std::vector<float> w;
+             {
+               py::gil_scoped_release nogil;
+               e.export_weights(k, w);
+             }
+             return py::make_tuple(to_np(k), to_np(w));
+           })
+      .def("save_serving", &Engine::save_serving, py::call_guard<py::gil_scoped_release>())
+      .def("import_weights",
+           [](Engine& e, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> keys,
+              py::array_t<float, py::array::c_style | py::array::forcecast> weights) {
+             const int64_t n = (int64_t)keys.size();
+             if ((int64_t)weights.size() != n * e.layout().P)
+               throw std::invalid_argument("import_weights: weights must hold P floats per key");
+             const u64* kp = reinterpret_cast<const u64*>(keys.data());
+             const float* wp = weights.data();
+             py::gil_scoped_release nogil;
+             e.import_weights(kp, wp, n);
+           })
       // delta checkpoints (EngineConfig::delta_track)
       .def("delta_count", &Engine::delta_count, py::call_guard<py::gil_scoped_release>())
       .def("delta_export",

@@ -9,7 +9,9 @@
 // Optional flags after the positional args: --threads N --device D
 // --serial-slices --keep-remainder --sgd --fm-standard --mvm-fixed
 // --mvm-predict-compat --v-dim D --log2-cap N --admit-min-count N
-// --admit-log2 N --prune-every N --prune-max-n X --save PATH --load PATH.
+// --admit-log2 N --prune-every N --prune-max-n X --save PATH --load PATH
+// --save-serving PATH (a serving snapshot file: resolved weights of the keys
+// that differ from an absent key, Engine::save_serving).
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -37,7 +39,7 @@ int main(int argc, char* argv[]) {
   cfg.train_prefix = argv[1];
   cfg.test_prefix = argv[2];
   cfg.epochs = std::atoi(argv[4]);
-  std::string save, load;
+  std::string save, load, save_serving;
   const char* dev = std::getenv("XFLOW_DEVICE");
   const bool gpu = xflow::hip_backend_available();
   cfg.device = gpu ? (dev ? std::atoi(dev) : 0) : -1;
@@ -66,6 +68,7 @@ int main(int argc, char* argv[]) {
     else if (a == "--prune-max-n") cfg.prune_max_n = (float)std::atof(next());
     else if (a == "--train-block-bytes") cfg.train_block_bytes = std::atoll(next());
     else if (a == "--save") save = next();
+    else if (a == "--save-serving") save_serving = next();
     else if (a == "--load") load = next();
     else {
       std::cerr << "unknown flag " << a << std::endl;
@@ -93,6 +96,7 @@ int main(int argc, char* argv[]) {
     if (!load.empty()) t.engine().load(load);
     t.train();
     if (!save.empty()) t.engine().save(save);
+    if (!save_serving.empty()) t.engine().save_serving(save_serving);
   } catch (const std::exception& e) {
     std::cerr << "xflow_lr: " << e.what() << std::endl;
     return 1;

@@ -26,6 +26,19 @@ one and importing each delta on top, oldest first -- an import overwrites the
 state of a key that is present.  ``publish`` never deletes a version that a
 kept version's chain needs.
 
+A serving snapshot (``save_serving``; meta.json "kind": "serving") is not a
+checkpoint to resume from: it holds only the keys whose weights differ from
+what an absent key reads, as resolved fp32 weights without optimiser state,
+  serving-<rank>-of-<world>.xfw  magic "XFLOWSW1", int32 {model kind, v_dim,
+                                 fm_math, mvm_math, P, source optimiser kind},
+                                 u64 keys of the source table, u64 n,
+                                 keys u64[n], weights f32[n, P]
+  meta.json                      "kind": "serving", model, optim (the source's),
+                                 the crosses record, keys_total, keys_kept
+``load_serving`` imports every rank's file into one frozen engine
+(OptimConfig.kind "frozen"); ``load`` / ``check_compatible`` refuse it, and
+``publish`` neither counts nor deletes such a directory.
+
 Resume is world-size agnostic: with the same world size each rank loads its
 own shard; otherwise every rank scans all shards and imports exactly the keys
 it owns under the new hash sharding (owner = fmix64(key) >> 32 mod world).
@@ -67,6 +80,24 @@ def admit_name(rank: int, world: int) -> str:
 
 def delta_name(rank: int, world: int) -> str:
     return f"delta-{rank:05d}-of-{world:05d}.xftb"
+
+
+SERVING_MAGIC = b"XFLOWSW1"
+
+
+def serving_name(rank: int, world: int) -> str:
+    return f"serving-{rank:05d}-of-{world:05d}.xfw"
+
+
+def is_serving(meta: dict) -> bool:
+    return meta.get("kind") == "serving"
+
+
+def _refuse_serving(meta: dict, where: str) -> None:
+    if is_serving(meta):
+        raise ValueError(f"{where}: a serving snapshot (resolved weights only, no optimiser "
+                         f"state): it cannot be resumed from; load it with "
+                         f"xflow_amd.serve.Predictor or checkpoint.load_serving")
 
 
 def shard_keys(path: str) -> int:
@@ -212,6 +243,7 @@ def check_compatible(engine, meta: dict) -> None:
     """The checkpoint's layout-defining model/optimizer fields must equal the
     running ones; other differences (hyperparameters, kernel choices) are
     reported as warnings."""
+    _refuse_serving(meta, "checkpoint")
     want = {"model": dataclasses.asdict(engine.model), "optim": dataclasses.asdict(engine.optim)}
     for k, cur in want.items():
         saved = meta.get(k)
@@ -355,6 +387,7 @@ def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
     """Load the version (resolving a delta's chain, see ``chain``) and leave
     the engine's touched-key filter clean: its state equals the chain's tip,
     so the next save may be a delta on ``ckpt_dir``."""
+    _refuse_serving(load_meta(ckpt_dir), ckpt_dir)
     links = chain(ckpt_dir)
     meta = load_meta(ckpt_dir)
     check_compatible(engine, meta)
@@ -363,6 +396,117 @@ def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
         _load_version(engine, d, rank, world, delta=i > 0)
     engine.delta_clear()
     engine._delta_tip = _tip(ckpt_dir)
+    return meta
+
+
+# ---------------------------------------------------------------- serving
+def read_serving(path: str):
+    """(header ints, keys u64 [n], weights f32 [n, P]) of a serving file."""
+    with open(path, "rb") as f:
+        if f.read(8) != SERVING_MAGIC:
+            raise ValueError(f"{path}: not an xflow serving snapshot")
+        hdr = struct.unpack("<6i", f.read(24))
+        _total, n = struct.unpack("<QQ", f.read(16))
+        keys = np.frombuffer(f.read(8 * n), dtype=np.uint64)
+        P = hdr[4]
+        weights = np.frombuffer(f.read(4 * n * P), dtype=np.float32).reshape(n, P)
+    if len(keys) != n or weights.shape[0] != n:
+        raise ValueError(f"{path}: truncated serving snapshot")
+    return hdr, keys, weights
+
+
+def serving_counts(path: str):
+    """(keys of the source table, keys kept) of a serving file, from its
+    header only."""
+    with open(path, "rb") as f:
+        if f.read(8) != SERVING_MAGIC:
+            raise ValueError(f"{path}: not an xflow serving snapshot")
+        f.seek(24, os.SEEK_CUR)
+        total, n = struct.unpack("<QQ", f.read(16))
+    return int(total), int(n)
+
+
+def serving_files(ckpt_dir: str) -> list:
+    """Every rank's file of a serving directory, by rank."""
+    w = int(load_meta(ckpt_dir)["world"])
+    got = sorted(glob.glob(os.path.join(ckpt_dir, "serving-*-of-%05d.xfw" % w)))
+    if len(got) != w:
+        raise FileNotFoundError(f"{ckpt_dir}: expected {w} serving files, found {len(got)}")
+    return got
+
+
+def _serving_dir(d: str) -> bool:
+    try:
+        return is_serving(load_meta(d))
+    except (OSError, ValueError):
+        return False
+
+
+def save_serving(engine, out_dir: str, rank: int, world: int, meta: Optional[dict] = None,
+                 barrier: Optional[Callable[[], None]] = None) -> str:
+    """Write this rank's serving file (Engine.save_serving: the keys that
+    differ from an absent key, as resolved weights; fsync'd), wait for every
+    rank, then rank 0 writes meta.json -- ``save``'s protocol.  keys_total /
+    keys_kept are summed from the files' headers, which carry both counts."""
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, serving_name(rank, world))
+    engine.save_serving(path + ".tmp")
+    _fsync_file(path + ".tmp")
+    os.replace(path + ".tmp", path)
+    (barrier or _default_barrier)()
+    if rank == 0:
+        counts = [serving_counts(os.path.join(out_dir, serving_name(r, world)))
+                  for r in range(world)]
+        optim = dataclasses.asdict(engine.optim)
+        if optim.get("kind") == "frozen":  # (a snapshot of a snapshot: the source's source)
+            optim["kind"] = optim["frozen_from"]
+        m = dict(meta or {})
+        m.pop("delta_base", None)
+        m.update(kind="serving", world=world, model=dataclasses.asdict(engine.model),
+                 optim=optim, keys_total=sum(c[0] for c in counts),
+                 keys_kept=sum(c[1] for c in counts))
+        mtmp = os.path.join(out_dir, "meta.json.tmp")
+        with open(mtmp, "w") as f:
+            json.dump(m, f, indent=1)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(mtmp, os.path.join(out_dir, "meta.json"))
+        _fsync_dir(out_dir)
+    return path
+
+
+def frozen_optim(meta: dict) -> dict:
+    """The OptimConfig fields of the frozen engine that serves ``meta``'s
+    snapshot: the source optimiser's, with kind "frozen"."""
+    o = dict(meta["optim"])
+    o["frozen_from"] = o.get("kind", "ftrl")
+    o["kind"] = "frozen"
+    return o
+
+
+def load_serving(engine, ckpt_dir: str) -> dict:
+    """Import every rank's serving file into one frozen engine."""
+    meta = load_meta(ckpt_dir)
+    if not is_serving(meta):
+        raise ValueError(f"{ckpt_dir}: not a serving snapshot (use checkpoint.load)")
+    if not engine.frozen:
+        raise ValueError("load_serving: the engine must be frozen (OptimConfig.kind 'frozen')")
+    lay = engine.layout
+    from xflow_amd.config import FM_MATH, MVM_MATH, OPT_KINDS
+
+    exp = (lay["kind"], int(engine.model.v_dim), FM_MATH[engine.model.fm_math],
+           MVM_MATH[engine.model.mvm_math], lay["P"], OPT_KINDS[engine.optim.frozen_from])
+    for p in serving_files(ckpt_dir):
+        hdr, keys, weights = read_serving(p)
+        got = tuple(hdr[:6])
+        # (v_dim, fm_math and mvm_math only mean something to their own model)
+        same = got[0] == exp[0] and got[4] == exp[4] and got[5] == exp[5] and \
+            (exp[0] == 0 or got[1] == exp[1]) and (exp[0] != 1 or got[2] == exp[2]) and \
+            (exp[0] != 2 or got[3] == exp[3])
+        if not same:
+            raise ValueError(f"{p}: snapshot header {got} does not match this engine {exp}")
+        if len(keys):
+            engine.import_weights(keys, weights)
     return meta
 
 
@@ -384,7 +528,7 @@ def publish(root: str, epoch: int, keep: int = 2) -> None:
         os.fsync(f.fileno())
     os.replace(tmp, os.path.join(root, LATEST))
     _fsync_dir(root)
-    vers = sorted(glob.glob(os.path.join(root, "epoch-*")))
+    vers = [d for d in sorted(glob.glob(os.path.join(root, "epoch-*"))) if not _serving_dir(d)]
     needed = set()
     for d in vers[-keep:]:  # the kept versions and every link of their chains
         try:

@@ -124,6 +124,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--delta-log2", type=int, default=0,
                     help="--save-delta: bits of the touched-key filter per rank = 2^N (10..34; 0: "
                          "min(34, the table's largest log2 capacity + 2))")
+    ap.add_argument("--save-serving", default="",
+                    help="after the last epoch every rank writes its shard's serving snapshot "
+                         "here: only the keys that differ from an absent key, as resolved fp32 "
+                         "weights (xflow_amd.serve loads it; it cannot be resumed from)")
     ap.add_argument("--metrics", default="", help="JSON-lines metrics file (rank 0)")
     ap.add_argument("--trace-dir", default="", help="torch.profiler chrome trace directory")
     return ap
@@ -143,6 +147,7 @@ def config_from_args(a) -> TrainConfig:
         checkpoint_dir=a.save,
         save_every=a.save_every, resume_dir=a.resume,
         save_delta=a.save_delta, delta_full_every=a.delta_full_every,
+        save_serving=a.save_serving,
         prune_every=a.prune_every, prune_max_n=a.prune_max_n, gauc_field=a.gauc_field,
         metrics_file=a.metrics, async_p2p=a.async_p2p, async_ps=a.async_ps,
         staleness=a.staleness,

@@ -23,7 +23,9 @@ from dataclasses import dataclass, field
 
 MODEL_KINDS = {"lr": 0, "fm": 1, "mvm": 2}
 MODEL_NAMES = {v: k for k, v in MODEL_KINDS.items()}
-OPT_KINDS = {"ftrl": 0, "sgd": 1}
+# "frozen": a read-only table of resolved fp32 weights (a serving snapshot,
+# docs/DESIGN.md §2), never an optimiser to train with
+OPT_KINDS = {"ftrl": 0, "sgd": 1, "frozen": 2}
 FM_MATH = {"reference": 0, "standard": 1}
 MVM_MATH = {"compat": 0, "fixed": 1}
 
@@ -105,7 +107,7 @@ class ModelConfig:
 
 @dataclass
 class OptimConfig:
-    kind: str = "ftrl"           # ftrl | sgd
+    kind: str = "ftrl"           # ftrl | sgd | frozen (a serving snapshot: read-only)
     alpha: float = 5e-2
     beta: float = 1.0
     lambda1: float = 5e-5
@@ -114,10 +116,17 @@ class OptimConfig:
     sgd_v_init: float = 1e-3
     v_init_scale: float = 1e-2
     seed: int = 0x5EED
+    # kind "frozen": the optimiser the snapshot was exported from (ftrl | sgd).
+    # It decides what a key that is not in the snapshot reads: latents take
+    # that optimiser's init (N(0,1) * v_init_scale under seed, or sgd_v_init)
+    frozen_from: str = "ftrl"
 
     def native(self) -> dict:
         d = dataclasses.asdict(self)
         d["kind"] = OPT_KINDS[self.kind]
+        if self.frozen_from not in ("ftrl", "sgd"):
+            raise ValueError(f"frozen_from must be ftrl or sgd, got {self.frozen_from!r}")
+        d["frozen_from"] = OPT_KINDS[self.frozen_from]
         return d
 
 
@@ -182,6 +191,16 @@ class EngineConfig:
     # no extra launch.  csrc/include/xflow/engine.h
     delta_track: bool = False
     delta_log2: int = 0
+    # a frozen engine (OptimConfig.kind "frozen") scores LR batches on the GPU
+    # with one lookup-and-score launch; False -- or FM / MVM -- runs dedup,
+    # pull and forward as on a training engine (the A/B switch)
+    serve_fused: bool = True
+    # ... except for batches of serve_unfused_rows[0] <= rows <
+    # serve_unfused_rows[1], which take the three launches (the same bits,
+    # tests/test_serving_snapshot.py): profiles/serve.txt has the one-launch
+    # kernel ahead up to 32 rows and from 256 rows, 6 % behind at 64 and 128;
+    # (0, 0): always one launch
+    serve_unfused_rows: tuple = (64, 256)
 
 
 @dataclass
@@ -218,6 +237,10 @@ class TrainConfig:
     # chain's length and the restart time
     save_delta: bool = False
     delta_full_every: int = 8
+    # after the last epoch every rank writes its shard's serving snapshot
+    # (checkpoint.save_serving: only the keys that differ from an absent key,
+    # as resolved fp32 weights) into this directory; "": off
+    save_serving: str = ""
     # prune the table (Engine.prune: drop keys whose weights are all exactly
     # zero) at the end of every N-th epoch, 0: never; prune_max_n: with FTRL
     # only keys with every n <= it (negative: no bound)

@@ -209,7 +209,10 @@ class Engine:
                            red_local=self.cfg.red_local,
                            red_apply=self.cfg.red_apply,
                            delta_track=self.cfg.delta_track,
-                           delta_log2=self.cfg.delta_log2)
+                           delta_log2=self.cfg.delta_log2,
+                           serve_fused=self.cfg.serve_fused,
+                           serve_unfused_lo=int(self.cfg.serve_unfused_rows[0]),
+                           serve_unfused_hi=int(self.cfg.serve_unfused_rows[1]))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -815,6 +818,47 @@ class Engine:
     @property
     def state_words(self) -> int:
         return int(self._e.state_words)
+
+    # ---- serving snapshots (docs/DESIGN.md §2) --------------------------------
+    @property
+    def frozen(self) -> bool:
+        """This engine holds a serving snapshot (OptimConfig.kind "frozen"):
+        read-only; training, prune and the training checkpoints raise."""
+        return bool(self._e.frozen)
+
+    @property
+    def serve_fused(self) -> bool:
+        """eval_step runs the one-launch LR kernel (EngineConfig.serve_fused on
+        a frozen LR engine on the GPU)."""
+        return bool(self._e.serve_fused)
+
+    def export_weights_count(self) -> int:
+        """Keys export_weights() would write (a count pass; syncs)."""
+        self._sync_stream()
+        return int(self._e.export_weights_count())
+
+    def export_weights(self):
+        """(keys u64 [n], weights f32 [n, P]) of the keys whose weights differ
+        -- as bit patterns -- from what an absent key reads (slot_exported,
+        csrc/include/xflow/types.h), each with its P resolved weights.  LR
+        drops every zero-weight key; FM / MVM drop the keys never pushed and
+        keep a pushed key even when L1 zeroed its latents.  A pull of any key
+        returns the same bits from ``import_weights`` of this as from here."""
+        self._sync_stream()
+        k, w = self._e.export_weights()
+        return k, w.reshape(len(k), self.params_per_key)
+
+    def save_serving(self, path: str) -> int:
+        """export_weights() as one ``.xfw`` file (checkpoint.save_serving's
+        per-rank file); returns the keys written."""
+        self._sync_stream()
+        return int(self._e.save_serving(path))
+
+    def import_weights(self, keys, weights) -> None:
+        """Insert (key, P weights) pairs into this frozen engine."""
+        self._sync_stream()
+        self._e.import_weights(np.ascontiguousarray(keys, dtype=np.uint64),
+                               np.ascontiguousarray(weights, dtype=np.float32).reshape(-1))
 
     def save(self, path: str) -> None:
         self._sync_stream()

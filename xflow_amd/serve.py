@@ -19,6 +19,18 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
                    or {"keys": [[k, ...], ...]}  -> {"pctr": [...]}
         GET  /health
 
+A serving snapshot (checkpoint.save_serving, ``--save-serving``, or the offline
+conversion below) is loaded the same way: ``Predictor(dir)`` sees "kind":
+"serving" in its meta.json and builds a frozen engine that holds only the keys
+whose weights differ from an absent key's, as resolved fp32 weights -- the
+same predictions, bit for bit, from a fraction of the memory.
+
+    python -m xflow_amd.serve export --checkpoint ckpt/ --out snap/ [--parts N]
+
+converts any checkpoint (a delta tip included) part by part: part r of N loads
+only the keys it owns (checkpoint.load's resharding) into a table sized for
+them and writes serving-r-of-N.xfw, so the peak memory is 1/N of the model.
+
 Rows are scored in batches of ``max_rows``; one engine serves requests one
 at a time (a lock around the device work).
 """
@@ -58,11 +70,14 @@ class Predictor:
     """Scores rows with a model loaded from a checkpoint (see module doc)."""
 
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
-                 max_nnz_per_row: int = 64):
+                 max_nnz_per_row: int = 64, serve_fused: bool = True,
+                 serve_unfused_rows=None):
         self.ckpt = _resolve(ckpt)
         meta = checkpoint.load_meta(self.ckpt)
+        self.snapshot = checkpoint.is_serving(meta)
         self.model = _fields(ModelConfig, meta["model"])
-        self.optim = _fields(OptimConfig, meta["optim"])
+        self.optim = _fields(OptimConfig, checkpoint.frozen_optim(meta) if self.snapshot
+                             else meta["optim"])
         self.meta = meta
         # the feature crosses the model was trained with (absent: none): every
         # request is crossed the same way before it is scored
@@ -70,7 +85,11 @@ class Predictor:
         # (key counts from the shard headers: nothing else is read twice; a
         # delta version: its full base's shards plus every delta's of its
         # chain, an upper bound -- a delta repeats keys its bases hold)
-        n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(self.ckpt))
+        if self.snapshot:
+            n_keys = sum(checkpoint.serving_counts(p)[1]
+                         for p in checkpoint.serving_files(self.ckpt))
+        else:
+            n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(self.ckpt))
         # every shard's keys in one table at load <= 0.5 (no growth while serving)
         lg = max(16, int(math.ceil(math.log2(max(2 * n_keys, 1)))))
         if device is None:
@@ -81,10 +100,15 @@ class Predictor:
                              EngineConfig(table_log2_cap=lg, max_rows=self.max_rows,
                                           max_nnz=self.max_rows * (int(max_nnz_per_row)
                                                                    + len(self.crosses)),
-                                          table_grow=False),
+                                          table_grow=False, serve_fused=serve_fused,
+                                          **({} if serve_unfused_rows is None else
+                                             {"serve_unfused_rows": tuple(serve_unfused_rows)})),
                              device=device)
-        checkpoint.load(self.engine, self.ckpt, 0, 1)
-        self.keys = self.engine.table_size()
+        if self.snapshot:
+            checkpoint.load_serving(self.engine, self.ckpt)
+        else:
+            checkpoint.load(self.engine, self.ckpt, 0, 1)
+        self.keys = self.engine.table_size()  # (a snapshot: the keys it kept)
         self._lock = threading.Lock()
 
     # ---------------------------------------------------------------- scoring
@@ -178,7 +202,8 @@ def make_app(pred: Predictor):
     @app.get("/health")
     def health():
         return {"status": "ok", "model": pred.model.kind, "keys": int(pred.keys),
-                "device": str(pred.device), "checkpoint": pred.ckpt}
+                "device": str(pred.device), "checkpoint": pred.ckpt,
+                "snapshot": bool(pred.snapshot)}
 
     def predict(req):
         if (req.libffm is None) == (req.keys is None):
@@ -195,7 +220,56 @@ def make_app(pred: Predictor):
     return app
 
 
+def export_snapshot(ckpt: str, out: str, parts: int = 1,
+                    device: Optional[torch.device] = None) -> dict:
+    """Offline conversion of a checkpoint (a delta tip included) into a
+    serving snapshot of ``parts`` files.  Part r loads the keys it owns under
+    a ``parts``-way sharding into a table sized for them, exports, and frees
+    the engine before the next part.  Returns the snapshot's meta."""
+    src = _resolve(ckpt)
+    meta = checkpoint.load_meta(src)
+    if checkpoint.is_serving(meta):
+        raise ValueError(f"{src}: already a serving snapshot")
+    if parts < 1:
+        raise ValueError("--parts must be >= 1")
+    model = _fields(ModelConfig, meta["model"])
+    optim = _fields(OptimConfig, meta["optim"])
+    n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(src))
+    # (hash sharding is even: a part holds about 1/parts of the keys; the table
+    # still grows if a part turns out fuller)
+    lg = max(16, int(math.ceil(math.log2(max(2 * n_keys / parts, 1)))))
+    if device is None:
+        device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
+    keep = {k: meta[k] for k in ("epoch", "steps", "crosses", "cross_field_base") if k in meta}
+    for r in reversed(range(parts)):
+        eng = Engine(model, optim, EngineConfig(table_log2_cap=min(lg, 31), max_rows=1024,
+                                                max_nnz=1 << 16), device=device)
+        checkpoint.load(eng, src, r, parts)
+        # (one process writes every part in turn, part 0 last: its meta.json
+        # is written once every file exists)
+        checkpoint.save_serving(eng, out, r, parts, meta=keep, barrier=lambda: None)
+        del eng
+    return checkpoint.load_meta(out)
+
+
 def main(argv=None) -> int:
+    import sys
+
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and argv[0] == "export":
+        ap = argparse.ArgumentParser(prog="python -m xflow_amd.serve export",
+                                     description="convert a checkpoint into a serving snapshot")
+        ap.add_argument("--checkpoint", required=True, help="checkpoint directory or versioned root")
+        ap.add_argument("--out", required=True, help="directory of the snapshot")
+        ap.add_argument("--parts", type=int, default=1,
+                        help="files to write; each part loads 1/N of the model at a time")
+        ap.add_argument("--cpu", action="store_true")
+        a = ap.parse_args(argv[1:])
+        m = export_snapshot(a.checkpoint, a.out, a.parts,
+                            device=torch.device("cpu") if a.cpu else None)
+        print(f"serving snapshot {a.out}: kept {m['keys_kept']} of {m['keys_total']} keys "
+              f"in {a.parts} part(s)", flush=True)
+        return 0
     ap = argparse.ArgumentParser(prog="python -m xflow_amd.serve", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", required=True)

@@ -649,6 +649,8 @@ class Trainer:
             self.init_push()
         # cfg.epochs counts the whole run: a resumed job trains the rest
         self.train_epochs(max(0, self.cfg.epochs - self.epoch) if self.resumed else self.cfg.epochs)
+        if self.cfg.save_serving:
+            self.save_serving(self.cfg.save_serving)
         res = None
         if self.rank == 0:
             _say("LR AUC: " if model_kind(self.cfg.model.kind) == 0 else "FM AUC: ")
@@ -666,6 +668,19 @@ class Trainer:
                                meta=dict({"epoch": self.epoch, "steps": self.steps},
                                          **checkpoint.cross_meta(self.crosses, self._cross_base)),
                                barrier=xdist.barrier, delta_base=delta_base)
+        xdist.barrier()
+        return path
+
+    def save_serving(self, out_dir: str) -> str:
+        """Every rank writes its own shard's serving snapshot (no gather);
+        returns this rank's file (checkpoint.save_serving)."""
+        if hasattr(self.sharded, "flush"):
+            self.sharded.flush()
+        path = checkpoint.save_serving(
+            self.table, out_dir, self.rank, self.world,
+            meta=dict({"epoch": self.epoch, "steps": self.steps},
+                      **checkpoint.cross_meta(self.crosses, self._cross_base)),
+            barrier=xdist.barrier)
         xdist.barrier()
         return path
 
