@@ -68,6 +68,11 @@ const EngineConfig& Engine::validated(const EngineConfig& cfg) {
       throw std::runtime_error("delta_track: this engine holds a serving snapshot (frozen, "
                                "read-only): it has no deltas to save");
   }
+  // (the FM / MVM window: both bounds negative -- the model's measured default
+  // -- or both given)
+  if ((cfg.serve_unfused_latent_lo < 0) != (cfg.serve_unfused_latent_hi < 0))
+    throw std::invalid_argument("serve_unfused_latent: give both bounds, or both negative "
+                                "for the model's default");
   return cfg;
 }
 
@@ -239,6 +244,19 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(validated(cfg)) {
   fm_vals_ = red_pairs_ && fm_ref;
   vstride_ = fm_vals_ ? 4 : ps;
   serve_lr_ = frozen() && cfg_.serve_fused && cfg_.model.kind == kLR && be.serves_lr();
+  serve_model_ = frozen() && cfg_.serve_fused && be.serves_models() &&
+                 (cfg_.model.kind == kMVM ||
+                  (cfg_.model.kind == kFM &&
+                   !(cfg_.model.fm_math == kFmStandard && cfg_.model.fm_mfma)));
+  if (cfg_.serve_unfused_latent_lo < 0) {  // (validated: then both are)
+    // the model's measured window (EngineConfig::serve_unfused_latent_lo).
+    // cfg_ holds the window in force from here on, not the caller's (-1, -1):
+    // serve_unfused_latent() and eval_step read it
+    cfg_.serve_unfused_latent_lo = 0;
+    cfg_.serve_unfused_latent_hi =
+        cfg_.model.kind == kMVM ? INT64_MAX
+                                : (cfg_.model.fm_math == kFmReference ? 512 : 0);
+  }
   wpull_.alloc(be, rows1 * vstride_);
   be.memset(wpull_ + scratch_.cap * vstride_, 0, sizeof(float) * vstride_);
   stats_.alloc_zero(be, 2);
@@ -1101,6 +1119,21 @@ void Engine::eval_step(const BatchView& b, float* pctr) {
     sa.pctr = pctr;
     sa.stats = stats_ + 1;
     be_->serve_lr(sa);
+    return;
+  }
+  // (frozen FM / MVM likewise, with a window of their own; fm_vals_: the
+  // forward below would sum compact value rows, so the kernel does)
+  if (serve_model_ &&
+      !(b.rows >= cfg_.serve_unfused_latent_lo && b.rows < cfg_.serve_unfused_latent_hi)) {
+    ServeArgs sa;
+    sa.table = table_;
+    sa.batch = b;
+    sa.pctr = pctr;
+    sa.stats = stats_ + 1;
+    sa.model = cfg_.model;
+    sa.opt = cfg_.opt;
+    sa.fm_vals = fm_vals_;
+    be_->serve_model(sa);
     return;
   }
   use_worker_set(0);

@@ -445,6 +445,8 @@ class HipBackend final : public Backend {
   }
   bool serves_lr() const override { return true; }
   void serve_lr(const ServeLrArgs& a) override { hip::launch_serve_lr(a, stream_); }
+  bool serves_models() const override { return true; }
+  void serve_model(const ServeArgs& a) override { hip::launch_serve_model(a, stream_); }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

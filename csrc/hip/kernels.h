@@ -71,6 +71,7 @@ void launch_table_export_weights(const TableView& t, const OptSpec& o, u64* keys
 
 // kernels_serve.hip
 void launch_serve_lr(const ServeLrArgs& a, hipStream_t st);
+void launch_serve_model(const ServeArgs& a, hipStream_t st);  // FM, MVM
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

@@ -678,6 +678,26 @@ struct ServeLrArgs {
   LossStats* stats = nullptr;      // optional
 };
 
+// The same for FM and MVM (Backend::serve_model, HIP: k_serve_fm /
+// k_serve_mvm): slots of 2 + P words {key, w_0 .. w_{P-1}, pad}; a key that
+// is not in the table reads absent_weight(key, p, table.L, opt) -- the source
+// optimiser's lazy init (OptSpec::frozen_from) -- and the kernel-width
+// padding reads 0.0f.  A row is summed as the forward the engine would run on
+// its pulled rows sums it, operation for operation (docs/DESIGN.md §2), so
+// pctr has the unfused path's bits.  Standard FM with ModelSpec::fm_mfma is
+// refused: the matrix-core forward sums a row in another association.
+struct ServeArgs {
+  TableView table;                 // kFrozen, TableLayout::make(model, opt)
+  BatchView batch;                 // any of the three layouts (MVM: with fgid)
+  float* pctr = nullptr;           // [rows] optional
+  LossStats* stats = nullptr;      // optional
+  ModelSpec model;                 // kFM or kMVM
+  OptSpec opt;
+  // reference-math FM: sum each key's (Σ_k v_k, Σ_k v_k^2) first, as the
+  // compact value rows do (FwdArgs::fm_vals); false: the full-row sums (k_fm)
+  bool fm_vals = false;
+};
+
 struct SynthArgs {                 // synthetic Criteo-shaped batch generator
   u64* keys = nullptr;
   float* labels = nullptr;
@@ -1060,6 +1080,12 @@ class Backend {
   virtual void serve_lr(const ServeLrArgs& a) {
     (void)a;
     throw std::runtime_error("serve_lr is not supported by this backend");
+  }
+  // ... and of an FM or MVM batch (ServeArgs; HIP only)
+  virtual bool serves_models() const { return false; }
+  virtual void serve_model(const ServeArgs& a) {
+    (void)a;
+    throw std::runtime_error("serve_model is not supported by this backend");
   }
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --

@@ -12,6 +12,7 @@
 #pragma once
 
 #include <memory>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -116,10 +117,11 @@ struct EngineConfig {
   bool delta_track = false;
   int delta_log2 = 0;
   // A frozen engine (OptSpec::kind == kFrozen: a serving snapshot)
-  // scores LR batches with the one-launch lookup-and-score kernel
-  // (Backend::serve_lr) where the backend has one; false -- or FM / MVM --
-  // runs eval_step's dedup -> pull -> forward as on a training engine (the A/B
-  // switch).  Ignored by engines that are not frozen.
+  // scores batches with the model's one-launch lookup-and-score kernel
+  // (Backend::serve_lr, Backend::serve_model) where the backend has one; false
+  // -- or standard FM with fm_mfma -- runs eval_step's dedup -> pull -> forward
+  // as on a training engine (the A/B switch).  Ignored by engines that are
+  // not frozen.
   bool serve_fused = true;
   // ... except for batches of serve_unfused_lo <= rows < serve_unfused_hi,
   // which take the three-launch path (tests/test_serving_snapshot.py holds
@@ -131,6 +133,23 @@ struct EngineConfig {
   // first size measured ahead again).  lo >= hi: always one launch.
   int64_t serve_unfused_lo = 64;
   int64_t serve_unfused_hi = 256;
+  // The same window for FM and MVM (the LR window above was measured for LR
+  // and holds for LR only); (0, 0): always one launch.  Negative (the
+  // default): the model's own measured window -- the families differ badly
+  // (profiles/serve.txt, FM-8 and MVM-10, rows x 39 fields):
+  //   reference FM  [0, 512): its unfused path gathers compact 16-byte value
+  //                 rows and is 7 to 24 % ahead up to 256 rows (0.0338 against
+  //                 0.0363 ms at 1 row, 0.0441 against 0.0545 at 32), within
+  //                 2 % at 512; the kernel is 30 % ahead at 1024 and 4096
+  //                 rows and 16 % at 262144
+  //   standard FM   [0, 0): the kernel is level at 32 rows and 2 to 28 %
+  //                 ahead everywhere else
+  //   MVM           every size: the kernel never won (0.0696 against 0.0458
+  //                 ms at 1 row, 0.4531 against 0.3306 at 262144); it ships
+  //                 for serve_unfused_rows_latent=(0, 0) and is off by default
+  // Engine::serve_unfused_latent() reports the window in force.
+  int64_t serve_unfused_latent_lo = -1;
+  int64_t serve_unfused_latent_hi = -1;
 };
 
 // Engine::delta_stats
@@ -503,8 +522,18 @@ class Engine {
   // this engine holds a serving snapshot: read-only, every training entry
   // point, prune and the training checkpoints throw
   bool frozen() const { return cfg_.opt.kind == kFrozen; }
-  // eval_step runs the one-launch LR kernel (EngineConfig::serve_fused)
-  bool serve_fused() const { return serve_lr_; }
+  // The model's one-launch kernel is available and switched on
+  // (EngineConfig::serve_fused; frozen, a backend that has it, not standard FM
+  // with fm_mfma).  Which batch sizes eval_step gives it is the window's
+  // business: serve_unfused_lo/hi for LR, serve_unfused_latent() for FM and
+  // MVM.  With the default window a frozen MVM engine reports true here and
+  // never launches k_serve_mvm, and reference FM launches k_serve_fm only
+  // from 512 rows.
+  bool serve_fused() const { return serve_lr_ || serve_model_; }
+  // FM / MVM: batches of first <= rows < second take the unfused path
+  std::pair<int64_t, int64_t> serve_unfused_latent() const {
+    return {cfg_.serve_unfused_latent_lo, cfg_.serve_unfused_latent_hi};
+  }
   // ---- delta checkpoints (EngineConfig::delta_track) ----------------------
   // The table's keys whose filter bit is set: their number (a count pass;
   // syncs), host copies of them and their state words (count pass, device
@@ -631,6 +660,9 @@ class Engine {
   bool fm_vals_ = false;
   int vstride_ = 1;
   bool serve_lr_ = false;  // frozen LR on a backend with serve_lr, serve_fused on
+  // frozen FM / MVM on a backend with serve_model, serve_fused on (not
+  // standard FM with fm_mfma: that forward sums a row in another association)
+  bool serve_model_ = false;
   // throws "<what>: this engine holds a serving snapshot ..." when frozen
   void refuse_frozen(const char* what) const;
   int64_t weights_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<float>& dw);

@@ -427,8 +427,11 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int admit_min_count, int admit_log2, bool lead_handoff,
                        bool scratch_carry, bool red_rank, bool delta_track, int delta_log2,
                        bool red_local, bool red_apply, bool serve_fused,
-                       int64_t serve_unfused_lo, int64_t serve_unfused_hi) {
+                       int64_t serve_unfused_lo, int64_t serve_unfused_hi,
+                       int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi) {
              EngineConfig c;
+             c.serve_unfused_latent_lo = serve_unfused_latent_lo;
+             c.serve_unfused_latent_hi = serve_unfused_latent_hi;
              c.serve_fused = serve_fused;
              c.serve_unfused_lo = serve_unfused_lo;
              c.serve_unfused_hi = serve_unfused_hi;
@@ -470,10 +473,12 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("red_rank") = true, py::arg("delta_track") = false,
            py::arg("delta_log2") = 0, py::arg("red_local") = true,
            py::arg("red_apply") = true, py::arg("serve_fused") = true,
-           py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256)
+           py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256,
+           py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1)
       // serving snapshots (docs/DESIGN.md §2)
       .def_property_readonly("frozen", &Engine::frozen)
       .def_property_readonly("serve_fused", &Engine::serve_fused)
+      .def_property_readonly("serve_unfused_latent", &Engine::serve_unfused_latent)
       .def("export_weights_count", &Engine::export_weights_count,
            py::call_guard<py::gil_scoped_release>())
       .def("export_weights",

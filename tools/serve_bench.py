@@ -14,7 +14,13 @@ saved as a full checkpoint and as a snapshot.  Then, in one process:
     alternating blocks;
   * FM-8: snapshot bytes and keys kept only.
 
-    python tools/serve_bench.py [--out profiles/serve.txt]
+--model fm|mvm [--v-dim D --fm-math M --opt ftrl|sgd --sgd-v-init X] measures
+the same three columns for an FM or MVM table instead (2^--fm-log2-cap slots
+prefilled to --fm-table-load); the frozen_fused column is then k_serve_fm /
+k_serve_mvm.  MVM wants --opt sgd --sgd-v-init 0.9: with the default init of
+1e-3 every field product underflows and the table never changes.
+
+    python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
 """
 from __future__ import annotations
 
@@ -40,8 +46,8 @@ def dir_bytes(d):
     return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
 
 
-def trained(a, dev, model, log2_cap, load=None):
-    eng = Engine(model, OptimConfig(),
+def trained(a, dev, model, log2_cap, load=None, optim=None):
+    eng = Engine(model, optim or OptimConfig(),
                  EngineConfig(table_log2_cap=log2_cap, max_rows=a.batch, max_nnz=a.batch * a.fields,
                               table_grow=False), device=dev)
     synth = SynthConfig(total_features=a.features, hash_space=a.features, seed=a.seed,
@@ -81,6 +87,11 @@ def main() -> int:
     ap.add_argument("--fm-log2-cap", type=int, default=25)
     ap.add_argument("--fm-table-load", type=float, default=0.2,
                     help="FM-8 prefill load (the steps' own keys come on top)")
+    ap.add_argument("--model", choices=("lr", "fm", "mvm"), default="lr")
+    ap.add_argument("--v-dim", type=int, default=8)
+    ap.add_argument("--fm-math", choices=("reference", "standard"), default="reference")
+    ap.add_argument("--opt", choices=("ftrl", "sgd"), default="ftrl")
+    ap.add_argument("--sgd-v-init", type=float, default=1e-3)
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -91,13 +102,18 @@ def main() -> int:
         print(s, flush=True)
         lines.append(s)
 
-    say("# tools/serve_bench.py: LR-FTRL, %d fields, %d features, a table of 2^%d slots prefilled "
+    lr = a.model == "lr"
+    model = ModelConfig(kind=a.model, v_dim=a.v_dim, fm_math=a.fm_math)
+    optim = OptimConfig(kind=a.opt, sgd_v_init=a.sgd_v_init)
+    log2_cap, load = (a.log2_cap, a.table_load) if lr else (a.fm_log2_cap, a.fm_table_load)
+    what = "LR" if lr else ("FM-%d %s" % (a.v_dim, a.fm_math) if a.model == "fm" else "MVM-%d" % a.v_dim)
+    say("# tools/serve_bench.py: %s-%s, %d fields, %d features, a table of 2^%d slots prefilled "
         "to load %.2f and trained %d steps of %d rows, %s"
-        % (a.fields, a.features, a.log2_cap, a.table_load, a.steps, a.batch,
+        % (what, a.opt.upper(), a.fields, a.features, log2_cap, load, a.steps, a.batch,
            torch.cuda.get_device_name(dev)))
     tmp = tempfile.mkdtemp(prefix="serve_bench_", dir=a.tmp or None)
     try:
-        eng, synth = trained(a, dev, ModelConfig(kind="lr"), a.log2_cap)
+        eng, synth = trained(a, dev, model, log2_cap, load, optim)
         full_dir, snap_dir = os.path.join(tmp, "full"), os.path.join(tmp, "snap")
         checkpoint.save(eng, full_dir, 0, 1, barrier=lambda: None)
         checkpoint.save_serving(eng, snap_dir, 0, 1, barrier=lambda: None)
@@ -109,7 +125,8 @@ def main() -> int:
         for name, path, kw in (("full", full_dir, {}),
                                ("frozen_unfused", snap_dir, {"serve_fused": False}),
                                # ((0, 0): the kernel at every size, not the engine's pick)
-                               ("frozen_fused", snap_dir, {"serve_unfused_rows": (0, 0)})):
+                               ("frozen_fused", snap_dir, {"serve_unfused_rows": (0, 0),
+                                                           "serve_unfused_rows_latent": (0, 0)})):
             p, s, db = loaded(path, dev, a, **kw)
             arms.append((name, p))
             say("%s %d %d %.3f %d" % (name, p.keys, dir_bytes(path), s, db))
@@ -141,18 +158,19 @@ def main() -> int:
                                 " ; ".join(" ".join("%.4f" % x for x in t) for t in times)))
         del arms, gens, bats, p
         torch.cuda.empty_cache()
-        # FM-8: sizes only
-        eng, _ = trained(a, dev, ModelConfig(kind="fm", v_dim=8), a.fm_log2_cap,
-                         a.fm_table_load)
-        ffull, fsnap = os.path.join(tmp, "fm_full"), os.path.join(tmp, "fm_snap")
-        checkpoint.save(eng, ffull, 0, 1, barrier=lambda: None)
-        checkpoint.save_serving(eng, fsnap, 0, 1, barrier=lambda: None)
-        m = checkpoint.load_meta(fsnap)
-        say("# FM-8, 2^%d slots prefilled to load %.2f: checkpoint %d bytes, snapshot %d bytes, kept %d of %d keys"
-            % (a.fm_log2_cap, a.fm_table_load, dir_bytes(ffull), dir_bytes(fsnap), m["keys_kept"], m["keys_total"]))
+        if lr:  # FM-8: sizes only
+            eng, _ = trained(a, dev, ModelConfig(kind="fm", v_dim=8), a.fm_log2_cap,
+                             a.fm_table_load)
+            ffull, fsnap = os.path.join(tmp, "fm_full"), os.path.join(tmp, "fm_snap")
+            checkpoint.save(eng, ffull, 0, 1, barrier=lambda: None)
+            checkpoint.save_serving(eng, fsnap, 0, 1, barrier=lambda: None)
+            m = checkpoint.load_meta(fsnap)
+            say("# FM-8, 2^%d slots prefilled to load %.2f: checkpoint %d bytes, snapshot %d bytes, "
+                "kept %d of %d keys" % (a.fm_log2_cap, a.fm_table_load, dir_bytes(ffull),
+                                        dir_bytes(fsnap), m["keys_kept"], m["keys_total"]))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    if a.out:
+    if a.out:  # (only a run that finished writes its table)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")

@@ -191,9 +191,10 @@ class EngineConfig:
     # no extra launch.  csrc/include/xflow/engine.h
     delta_track: bool = False
     delta_log2: int = 0
-    # a frozen engine (OptimConfig.kind "frozen") scores LR batches on the GPU
-    # with one lookup-and-score launch; False -- or FM / MVM -- runs dedup,
-    # pull and forward as on a training engine (the A/B switch)
+    # a frozen engine (OptimConfig.kind "frozen") scores batches on the GPU
+    # with the model's one lookup-and-score launch; False -- or standard FM
+    # with fm_mfma -- runs dedup, pull and forward as on a training engine
+    # (the A/B switch)
     serve_fused: bool = True
     # ... except for batches of serve_unfused_rows[0] <= rows <
     # serve_unfused_rows[1], which take the three launches (the same bits,
@@ -201,6 +202,13 @@ class EngineConfig:
     # kernel ahead up to 32 rows and from 256 rows, 6 % behind at 64 and 128;
     # (0, 0): always one launch
     serve_unfused_rows: tuple = (64, 256)
+    # the same window for FM and MVM (serve_unfused_rows is LR's, measured for
+    # LR); (0, 0): always one launch.  (-1, -1): the model's own measured
+    # window (profiles/serve.txt; csrc/include/xflow/engine.h): reference FM
+    # (0, 512), standard FM (0, 0), MVM every size -- its kernel never won
+    # and runs only when asked for.  Engine.serve_unfused_rows_latent reports
+    # the window in force
+    serve_unfused_rows_latent: tuple = (-1, -1)
 
 
 @dataclass

@@ -212,7 +212,9 @@ class Engine:
                            delta_log2=self.cfg.delta_log2,
                            serve_fused=self.cfg.serve_fused,
                            serve_unfused_lo=int(self.cfg.serve_unfused_rows[0]),
-                           serve_unfused_hi=int(self.cfg.serve_unfused_rows[1]))
+                           serve_unfused_hi=int(self.cfg.serve_unfused_rows[1]),
+                           serve_unfused_latent_lo=int(self.cfg.serve_unfused_rows_latent[0]),
+                           serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
 
@@ -828,9 +830,20 @@ class Engine:
 
     @property
     def serve_fused(self) -> bool:
-        """eval_step runs the one-launch LR kernel (EngineConfig.serve_fused on
-        a frozen LR engine on the GPU)."""
+        """The model's one-launch kernel is available and switched on
+        (EngineConfig.serve_fused on a frozen engine on the GPU; not standard
+        FM with fm_mfma).  Which batch sizes eval_step gives it is the
+        window's business: serve_unfused_rows for LR, serve_unfused_rows_latent
+        (this engine's property: the window in force) for FM and MVM -- by
+        default MVM never takes the kernel and reference FM from 512 rows."""
         return bool(self._e.serve_fused)
+
+    @property
+    def serve_unfused_rows_latent(self) -> tuple:
+        """The FM / MVM batch sizes [lo, hi) that take the unfused path on this
+        engine (EngineConfig.serve_unfused_rows_latent, resolved per model)."""
+        lo, hi = self._e.serve_unfused_latent
+        return int(lo), int(hi)
 
     def export_weights_count(self) -> int:
         """Keys export_weights() would write (a count pass; syncs)."""

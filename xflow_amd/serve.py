@@ -71,7 +71,7 @@ class Predictor:
 
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
                  max_nnz_per_row: int = 64, serve_fused: bool = True,
-                 serve_unfused_rows=None):
+                 serve_unfused_rows=None, serve_unfused_rows_latent=None):
         self.ckpt = _resolve(ckpt)
         meta = checkpoint.load_meta(self.ckpt)
         self.snapshot = checkpoint.is_serving(meta)
@@ -102,7 +102,10 @@ class Predictor:
                                                                    + len(self.crosses)),
                                           table_grow=False, serve_fused=serve_fused,
                                           **({} if serve_unfused_rows is None else
-                                             {"serve_unfused_rows": tuple(serve_unfused_rows)})),
+                                             {"serve_unfused_rows": tuple(serve_unfused_rows)}),
+                                          **({} if serve_unfused_rows_latent is None else
+                                             {"serve_unfused_rows_latent":
+                                              tuple(serve_unfused_rows_latent)})),
                              device=device)
         if self.snapshot:
             checkpoint.load_serving(self.engine, self.ckpt)
