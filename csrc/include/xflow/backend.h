@@ -1,6 +1,6 @@
 // xflow-amd: device backend interface.
 //
-// The engine (engine.cpp) is written once against this interface.  Two
+// The engine (csrc/engine/) is written once against this interface.  Two
 // implementations exist: HipBackend (gfx950 kernels, csrc/hip/*.hip) and
 // CpuBackend (csrc/cpu/cpu_backend.cpp) which runs the identical per-element
 // recipes from common.h/types.h on the host, single threaded and

@@ -603,8 +603,6 @@ class Engine {
   void delta_mark(const u64* keys, const int64_t* n_dev, int64_t n) {
     if (delta_bits_) be_->delta_mark(delta_bits_, delta_log2_, keys, n_dev, n, n);
   }
-  // count pass, then the marked keys into device buffers of exactly that size
-  int64_t delta_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<u32>& dw);
   DeviceBuffer<u64> scratch_keys_;
   DeviceBuffer<unsigned char> scratch_stamps_;
   DeviceBuffer<unsigned long long> scratch_claims_, scratch_ctl_;
@@ -617,7 +615,20 @@ class Engine {
   void d2h_stream(const void* src, size_t bytes, Sink sink);
   template <typename Fill>
   void h2d_stream(void* dst, size_t bytes, Fill fill);
-  void table_from_device(const u64* dk, const u32* dw, int64_t n);
+  // engine_io.cpp: an export's (keys, values) on the device -- every live
+  // slot, the delta's, the serving weights' (count pass, then buffers of
+  // exactly that size) -- and its way to host memory or into a file behind a
+  // header; import_from's and load's upload of n pairs, which differ in the fill
+  struct Pairs;
+  template <typename Pass>
+  Pairs export_pairs(int64_t n, int width, const char* changed, Pass pass);
+  Pairs full_to_device();
+  Pairs delta_to_device();
+  Pairs weights_to_device();
+  void pairs_to_host(const Pairs& p, void* keys, void* vals);
+  void pairs_to_file(const Pairs& p, const std::string& path, const void* hdr, size_t hbytes);
+  template <typename Fill>
+  bool import_pairs(int64_t n, Fill fill);
   DeviceBuffer<char, Mem::kStaging> stage_io_[2];
   void ensure_host_staging(int64_t n);  // push_host / pull_host device arrays of n keys
   void ensure_server_capacity(int64_t n, int buf = 0);
@@ -665,7 +676,6 @@ class Engine {
   bool serve_model_ = false;
   // throws "<what>: this engine holds a serving snapshot ..." when frozen
   void refuse_frozen(const char* what) const;
-  int64_t weights_to_device(DeviceBuffer<u64>& dk, DeviceBuffer<float>& dw);
   const float* pulled_weights(int buf, int64_t off) const;
 
   // worker buffers (backend memory)

@@ -2,8 +2,16 @@
 // on the CPU backend, for the host sanitizers (scripts/sanitize_host.sh:
 // AddressSanitizer + UBSan with leak detection).  It walks the paths that
 // allocate, grow or free engine memory and destroys the engine after each
-// group, so a buffer nobody owns shows up as a leak.  No data files.
+// group, so a buffer nobody owns shows up as a leak.  The checkpoint files go
+// through a temporary directory of its own (files()); an open stream stays
+// reachable from the C library, so that group counts the process's open
+// descriptors around every save and load instead, the failing ones included.
+#include <stdlib.h>
+
 #include <cstdio>
+#include <cstring>
+#include <filesystem>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -153,6 +161,129 @@ void prune_round(EngineConfig c) {
   check(e.table_size() > 0 && !e.overflowed(), "training after a prune");
 }
 
+// ---- checkpoint files --------------------------------------------------------
+struct TempDir {
+  std::string path = (std::filesystem::temp_directory_path() / "xflow_lifecycle_XXXXXX").string();
+  TempDir() { check(mkdtemp(path.data()) != nullptr, "mkdtemp"); }
+  ~TempDir() {
+    std::error_code ec;
+    std::filesystem::remove_all(path, ec);
+  }
+  std::string operator/(const char* name) const { return path + "/" + name; }
+};
+
+std::string slurp(const std::string& path) {
+  std::FILE* f = std::fopen(path.c_str(), "rb");
+  std::string s;
+  char buf[1 << 16];
+  for (size_t n; f && (n = std::fread(buf, 1, sizeof(buf), f)) > 0;) s.append(buf, n);
+  if (f) std::fclose(f);
+  check(f != nullptr, "a file that was written cannot be read");
+  return s;
+}
+
+void spit(const std::string& path, const std::string& s) {
+  std::FILE* f = std::fopen(path.c_str(), "wb");
+  const bool ok = f && std::fwrite(s.data(), 1, s.size(), f) == s.size();
+  if (f) std::fclose(f);
+  check(ok, "cannot write a test file");
+}
+
+// the export by key (slot order is the table's business)
+std::map<u64, std::vector<u32>> table_of(Engine& e) {
+  std::vector<u64> keys;
+  std::vector<u32> words;
+  e.export_table(keys, words);
+  const size_t W = (size_t)e.state_words();
+  std::map<u64, std::vector<u32>> m;
+  for (size_t i = 0; i < keys.size(); ++i)
+    m[keys[i]].assign(words.begin() + i * W, words.begin() + (i + 1) * W);
+  return m;
+}
+
+size_t open_fds() {
+  size_t n = 0;
+  for (const auto& e : std::filesystem::directory_iterator("/proc/self/fd")) n += !e.path().empty();
+  return n;
+}
+
+template <typename F>
+void must_throw(F f, const char* text, const char* what) {
+  try {
+    f();
+  } catch (const std::runtime_error& ex) {
+    check(std::strstr(ex.what(), text) != nullptr, what);
+    return;
+  }
+  check(false, what);
+}
+
+// save / load, a delta on top of its base, a serving snapshot into a frozen
+// engine; then the failures, each of which must close its file and leave the
+// engine able to train
+void files() {
+  const TempDir dir;
+  const std::string base = dir / "base", delta = dir / "delta", serving = dir / "serving";
+  EngineConfig c = config(kLR);
+  c.delta_track = true;
+  Engine a(c);
+  for (uint64_t step = 0; step < 3; ++step) a.train_step(batch(a, 1, step));
+  const size_t fds = open_fds();
+  a.save(base);
+  a.delta_clear();
+  {
+    Engine b(config(kLR));
+    b.load(base);
+    check(a.table_size() > 0 && table_of(b) == table_of(a), "save / load round trip");
+  }
+  a.train_step(batch(a, 1, 3));
+  a.save_delta(delta);
+  {
+    Engine b(config(kLR));
+    b.load(base);
+    b.load(delta);
+    check(a.delta_count() < a.table_size() && table_of(b) == table_of(a), "base + delta");
+  }
+  {
+    const size_t n = (size_t)a.save_serving(serving), P = (size_t)a.config().model.P();
+    const std::string raw = slurp(serving);
+    check(n > 0 && raw.size() == 48 + n * (8 + 4 * P) && raw.compare(0, 8, "XFLOWSW1") == 0,
+          "serving file");
+    std::vector<u64> keys(n);
+    std::vector<float> weights(n * P);
+    std::memcpy(keys.data(), raw.data() + 48, 8 * n);
+    std::memcpy(weights.data(), raw.data() + 48 + 8 * n, 4 * n * P);
+    EngineConfig fc = config(kLR);
+    fc.opt.kind = kFrozen;
+    fc.opt.frozen_from = kFTRL;
+    Engine f(fc);
+    f.import_weights(keys.data(), weights.data(), (int64_t)n);
+    check(f.pull_host(keys) == a.pull_host(keys), "serving weights");
+  }
+  check(open_fds() == fds, "a save or a load left its file open");
+  must_throw([&] { a.save(dir / "no_such_dir/shard"); }, "cannot open", "save into a missing directory");
+  check(open_fds() == fds, "a failed save left a file open");
+  const std::string good = slurp(base);
+  std::string cut = good.substr(0, 48 + 8 * (((good.size() - 48) / 16) / 2) + 3);  // (inside the keys)
+  std::string magic = good, layout = good;
+  magic[7] = '2';
+  layout[8 + 4 * 6] ^= 0x10;  // (hdr[6]: the slot stride)
+  const struct {
+    const std::string& bytes;
+    const char* text;
+  } bad[] = {{cut, "truncated checkpoint"}, {magic, "bad checkpoint"}, {layout, "checkpoint layout"}};
+  uint64_t step = 4;
+  for (const auto& b : bad) {
+    spit(dir / "bad", b.bytes);
+    const auto before = table_of(a);
+    must_throw([&] { a.load(dir / "bad"); }, b.text, b.text);
+    check(open_fds() == fds, "a failed load left its file open");
+    check(table_of(a) == before, "a failed load changed the table");
+    a.train_step(batch(a, 1, step++));
+    check(!a.overflowed(), "training after a failed load");
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -172,6 +303,7 @@ int main() {
     prune_round(config(kLR));
     prune_round(config(kFM));
     prune_round(config(kMVM));
+    files();
   } catch (const std::exception& ex) {
     std::fprintf(stderr, "%s\n", ex.what());
     return 1;

@@ -1,4 +1,4 @@
-"""Every gradient layout the step planner (plan_step, csrc/engine/engine.cpp)
+"""Every gradient layout the step planner (plan_step, csrc/engine/engine_step.cpp)
 can pick, exercised end to end against the plain PyTorch fp32 reference
 (xflow_amd/testing/torch_ref.py): each case first asserts which layout the
 engine plans for it -- so a routing change shows up here, not as a silent

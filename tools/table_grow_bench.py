@@ -6,7 +6,7 @@
 The table starts at 2^--log2-cap slots and is filled with synthetic keys
 (Engine.prefill, k_table_prefill) in chunks of --chunk keys; every chunk's
 insert guard grows the table by segment splits (linear hashing,
-csrc/engine/engine.cpp Engine::segments_for / split_to) once the fullest
+csrc/engine/engine_table.cpp Engine::segments_for / split_to) once the fullest
 segments pass grow_start.  Each split adds ONE segment of device memory,
 mapped at the end of the table's reserved address range
 (HipBackend::table_commit), and rewrites one segment -- so the table can grow

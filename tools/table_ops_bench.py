@@ -6,7 +6,7 @@ store's maintenance takes at the bench's occupancy.
 
 * prefill   --keys synthetic keys into 2^log2_cap slots (k_table_prefill)
 * export    every (key, state) pair to host arrays (Engine.export_table: the
-            checkpoint writer's source, csrc/engine/engine.cpp)
+            checkpoint writer's source, csrc/engine/engine_io.cpp)
 * save      the native shard file of a checkpoint (--save-dir; skipped when
             empty: a 1e9-key LR shard is 16 GB)
 * grow      every segment of a table prefilled to --grow-load split once

@@ -46,7 +46,9 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-ffp-contract=off", "-mcode-object-versi
             (["-DXFLOW_DEVICE_ASSERT=1"] if DEVICE_ASSERT else []) + \
             (["-DXFLOW_KTIMING=1"] if KTIMING else [])
 
-HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/trainer.cpp"]
+HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/engine_step.cpp",
+                "engine/engine_sharded.cpp", "engine/engine_table.cpp", "engine/engine_input.cpp",
+                "engine/engine_io.cpp", "engine/trainer.cpp"]
 
 
 def native_module_path() -> str:

@@ -7,7 +7,7 @@ Layout of ``<dir>/``:
                                  "crosses" / "cross_field_base" when the table
                                  was trained with feature crosses (cross_meta;
                                  absent: none)
-  shard-<rank>-of-<world>.xftb   native binary shard (csrc/engine/engine.cpp
+  shard-<rank>-of-<world>.xftb   native binary shard (csrc/engine/engine_io.cpp
                                  Engine::save): header + keys + state words
   admit-<rank>-of-<world>.xfad   only with feature admission on
                                  (EngineConfig.admit_min_count > 1): the rank's
@@ -258,7 +258,7 @@ def check_compatible(engine, meta: dict) -> None:
 
 
 def _check_header(engine, path: str, hdr) -> None:
-    """Shard header (csrc/engine/engine.cpp Engine::save: version, kind, v_dim,
+    """Shard header (csrc/engine/engine_io.cpp Engine::save: version, kind, v_dim,
     P, p_w, opt, stride) against the engine's table layout."""
     if hdr[0] != 1:
         raise ValueError(f"{path}: unsupported shard version {hdr[0]}")

@@ -1,6 +1,6 @@
 """Python face of the native Engine: torch-tensor batches, streams, checks.
 
-The native engine (csrc/engine/engine.cpp) owns the HBM hash table and all
+The native engine (csrc/engine/) owns the HBM hash table and all
 per-step buffers; this wrapper only validates tensors and hands device
 addresses over.  On a GPU it always runs the gfx950 HIP backend on torch's
 current stream (so engine kernels, torch ops and RCCL collectives are ordered
