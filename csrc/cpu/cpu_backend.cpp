@@ -564,6 +564,99 @@ class CpuBackend final : public Backend {
     }
     return n;
   }
+  int64_t table_export_weights_marked(const TableView& t, const OptSpec& o, const u32* bits,
+                                      int Lb, u64* keys_out, float* weights_out,
+                                      int64_t max_rows) override {
+    const TableLayout& L = t.L;
+    int64_t n = 0;
+    for (u64 s = 0; s < t.cap; ++s) {
+      const u32* sp = t.words + s * (u64)L.stride;
+      const u64 key = *reinterpret_cast<const u64*>(sp);
+      if (key == kEmptyKey) continue;
+      const u64 b = delta_bit(key, Lb);
+      if (!((bits[b >> 5] >> (u32)(b & 31u)) & 1u)) continue;
+      if (n < max_rows) {
+        keys_out[n] = key;
+        for (int p = 0; p < L.P; ++p) weights_out[n * L.P + p] = slot_weight(sp, key, p, L, o);
+      }
+      ++n;
+    }
+    return n;
+  }
+  // The HIP refresh kernels' two steps (kernels_refresh.hip) as plain loops.
+  void frozen_upsert(const TableView& t, const OptSpec& o, const u64* keys, const float* weights,
+                     int64_t n, u32* dirty) override {
+    const TableLayout& L = t.L;
+    if (L.opt != kFrozen) throw std::runtime_error("frozen_upsert: needs a frozen table");
+#if defined(XFLOW_DEVICE_ASSERT) && XFLOW_DEVICE_ASSERT
+    {  // the debug build's check of the contract: unique keys within a call
+      std::vector<u64> s(keys, keys + n);
+      for (u64& k : s) k = sanitize_key(k);
+      std::sort(s.begin(), s.end());
+      if (std::adjacent_find(s.begin(), s.end()) != s.end())
+        throw std::logic_error("frozen_upsert: a key occurs twice in one call");
+    }
+#endif
+    const u32* wbits = reinterpret_cast<const u32*>(weights);
+    for (int64_t i = 0; i < n; ++i) {
+      const u64 key = sanitize_key(keys[i]);
+      bool claimed = false;
+      const u32 slot = probe(t, key, true, claimed);
+      if (claimed) ++*t.size;
+      if (slot == kNoSlot) continue;
+      u32* sp = t.words + (u64)slot * L.stride;
+      bool absent = true;
+      for (int p = 0; p < L.P; ++p) {
+        const u32 b = wbits[i * L.P + p];
+        sp[2 + p] = b;
+        absent = absent && b == weight_bits(absent_weight(key, p, L, o));
+      }
+      if (absent) dirty[slot >> t.seg_log2] = 1u;
+    }
+  }
+  void frozen_sweep(const TableView& t, const OptSpec& o, const u32* dirty,
+                    unsigned long long* stats) override {
+    if (t.L.opt != kFrozen) throw std::runtime_error("frozen_sweep: needs a frozen table");
+    const int W = t.L.stride;
+    const int g = t.seg_log2;
+    const u64 G = 1ull << g, m = G - 1;
+    auto key_at = [&](u64 s) { return *reinterpret_cast<const u64*>(t.words + s * (u64)W); };
+    auto free_slot = [&](u32* sp) {
+      sp[0] = sp[1] = 0xFFFFFFFFu;
+      for (int w = 2; w < W; ++w) sp[w] = 0u;
+    };
+    unsigned long long cnt = 0;
+    for (u64 seg = 0; seg < (t.cap >> g); ++seg) {
+      if (!dirty[seg]) continue;  // (an unflagged segment is not read)
+      ++stats[1];
+      const u64 base = seg << g;
+      std::vector<u64> starts;  // marked before any slot changes
+      for (u64 c = 0; c < G; ++c)
+        if (key_at(base + c) != kEmptyKey && key_at(base + ((c - 1) & m)) == kEmptyKey)
+          starts.push_back(c);
+      for (u64 c : starts) {
+        auto at = [&](u64 off) { return base + ((c + off) & m); };
+        for (u64 d = 0; d < G; ++d) {
+          u32* sp = t.words + at(d) * (u64)W;
+          const u64 key = *reinterpret_cast<const u64*>(sp);
+          if (key == kEmptyKey) break;
+          if (!slot_exported(sp, key, t.L, o)) {
+            free_slot(sp);
+            ++cnt;
+          } else {
+            u64 off = ((fmix64(key) & m) - c) & m;
+            while (off < d && key_at(at(off)) != kEmptyKey) ++off;
+            if (off != d) {
+              std::memcpy(t.words + at(off) * (u64)W, sp, sizeof(u32) * W);
+              free_slot(sp);
+            }
+          }
+        }
+      }
+    }
+    *t.size -= cnt;
+    stats[0] += cnt;
+  }
   int64_t delta_popcount(const u32* bits, int L) override {
     int64_t n = 0;
     for (u64 i = 0; i < (1ull << (L - 5)); ++i) n += __builtin_popcount(bits[i]);

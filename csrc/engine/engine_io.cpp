@@ -1,5 +1,6 @@
 // xflow-amd: checkpoints -- table export / import, the training shard file
 // and its delta, serving snapshots.
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <thread>
@@ -76,6 +77,7 @@ namespace {
 
 constexpr char kMagic[8] = {'X', 'F', 'L', 'O', 'W', 'T', 'B', '1'};
 constexpr char kServingMagic[8] = {'X', 'F', 'L', 'O', 'W', 'S', 'W', '1'};
+constexpr char kServingDeltaMagic[8] = {'X', 'F', 'L', 'O', 'W', 'S', 'D', '1'};
 
 // A training shard's first 48 bytes; u64 keys[n], u32 words[n][stride - 2] follow
 struct ShardHeader {
@@ -290,19 +292,128 @@ void Engine::export_weights(std::vector<u64>& keys, std::vector<float>& weights)
   pairs_to_host(p, keys.data(), weights.data());
 }
 
+namespace {
+
+// A serving file's first 48 bytes (a snapshot's or a delta's, by the magic);
+// u64 keys[n], f32 weights[n][P] follow
+struct ServingHeader {
+  char magic[8];
+  int32_t w[6];  // model kind, v_dim, fm_math, mvm_math, P, source optimiser
+  uint64_t total, n;  // keys of the source table, entries of this file
+};
+static_assert(sizeof(ServingHeader) == 48, "no padding");
+ServingHeader serving_header(const char* magic, const EngineConfig& c, int P, int64_t total,
+                             int64_t n) {
+  ServingHeader h = {{}, {c.model.kind, c.model.v_dim, c.model.fm_math, c.model.mvm_math, P,
+                          c.opt.kind == kFrozen ? c.opt.frozen_from : c.opt.kind},
+                     (uint64_t)total, (uint64_t)n};
+  std::memcpy(h.magic, magic, 8);
+  return h;
+}
+
+}  // namespace
+
 int64_t Engine::save_serving(const std::string& path) {
-  struct {
-    char magic[8];
-    int32_t w[6];
-    uint64_t total, n;
-  } h = {{}, {cfg_.model.kind, cfg_.model.v_dim, cfg_.model.fm_math, cfg_.model.mvm_math, table_.L.P,
-              frozen() ? cfg_.opt.frozen_from : cfg_.opt.kind}, (uint64_t)table_size(), 0};
-  static_assert(sizeof(h) == 48, "no padding");
-  std::memcpy(h.magic, kServingMagic, 8);
+  const int64_t total = table_size();
   const Pairs p = weights_to_device();
-  h.n = (uint64_t)p.n;
+  const ServingHeader h = serving_header(kServingMagic, cfg_, table_.L.P, total, p.n);
   pairs_to_file(p, path, &h, sizeof(h));
   return p.n;
+}
+
+int64_t Engine::serving_delta_count() {
+  refuse_frozen("serving_delta_count");
+  if (!delta_bits_) throw std::runtime_error("serving_delta_count: delta tracking is off");
+  return be_->table_export_weights_marked(table_, cfg_.opt, delta_bits_, delta_log2_, nullptr,
+                                          nullptr, 0);
+}
+
+Engine::Pairs Engine::weights_delta_to_device() {
+  const int64_t n = serving_delta_count();
+  return export_pairs(n, table_.L.P,
+                      "export_weights_delta: marked key count changed between the passes",
+                      [&](u64* k, u32* v) {
+                        return be_->table_export_weights_marked(table_, cfg_.opt, delta_bits_,
+                                                                delta_log2_, k, (float*)v, n);
+                      });
+}
+
+void Engine::export_weights_delta(std::vector<u64>& keys, std::vector<float>& weights) {
+  refuse_frozen("export_weights_delta");
+  if (!delta_bits_) throw std::runtime_error("export_weights_delta: delta tracking is off");
+  const Pairs p = weights_delta_to_device();
+  keys.resize((size_t)p.n);
+  weights.resize((size_t)p.n * table_.L.P);
+  pairs_to_host(p, keys.data(), weights.data());
+}
+
+int64_t Engine::save_serving_delta(const std::string& path) {
+  refuse_frozen("save_serving_delta");
+  if (!delta_bits_) throw std::runtime_error("save_serving_delta: delta tracking is off");
+  const int64_t total = table_size();
+  const Pairs p = weights_delta_to_device();
+  const ServingHeader h = serving_header(kServingDeltaMagic, cfg_, table_.L.P, total, p.n);
+  pairs_to_file(p, path, &h, sizeof(h));
+  return p.n;
+}
+
+Engine::DeltaApplied Engine::apply_weights_delta(const u64* keys, const float* weights,
+                                                 int64_t n) {
+  if (!frozen())
+    throw std::runtime_error("apply_weights_delta: only a frozen engine (a serving snapshot) "
+                             "takes serving deltas");
+  DeltaApplied r;
+  if (n <= 0) return r;
+  // capacity, before anything changes: every entry may be a new key
+  const int64_t size0 = table_size();
+  const double room = cfg_.grow_load * (double)(max_segs_ << table_.seg_log2);
+  if ((double)size0 + (double)n > room) {
+    char msg[320];
+    std::snprintf(msg, sizeof(msg),
+                  "apply_weights_delta: %lld keys + %lld entries would pass the load bound %.2f "
+                  "of %llu slots%s; the table is unchanged",
+                  (long long)size0, (long long)n, cfg_.grow_load,
+                  (unsigned long long)(max_segs_ << table_.seg_log2),
+                  cfg_.table_grow ? "" : " (growth disabled)");
+    throw std::runtime_error(msg);
+  }
+  const int P = table_.L.P;
+  DeviceBuffer<u64> dk(*be_, (size_t)n);
+  DeviceBuffer<float> dw(*be_, (size_t)n * P);
+  auto from = [](const void* s) {
+    return [s](void* c, size_t o, size_t b) { par_copy(c, (const char*)s + o, b); };
+  };
+  h2d_stream(dk, sizeof(u64) * n, from(keys));
+  h2d_stream(dw, sizeof(float) * n * P, from(weights));
+  guard_inserts(n);  // (may split segments first)
+  stale_stashes();   // the table changes: server stashes are stale
+  const u64 nseg = table_.cap >> table_.seg_log2;
+  DeviceBuffer<u32> dirty;
+  dirty.alloc_zero(*be_, (size_t)nseg);
+  DeviceBuffer<unsigned long long> stats;
+  stats.alloc_zero(*be_, 3);
+  using clock = std::chrono::steady_clock;
+  be_->synchronize();
+  const auto t0 = clock::now();
+  be_->frozen_upsert(table_, cfg_.opt, dk, dw, n, dirty);
+  be_->synchronize();
+  const auto t1 = clock::now();
+  be_->frozen_sweep(table_, cfg_.opt, dirty, stats);
+  unsigned long long st[3] = {};
+  be_->copy_d2h(st, stats, sizeof(st));  // (synchronising)
+  r.sweep_seconds = std::chrono::duration<double>(clock::now() - t1).count();
+  r.upsert_seconds = std::chrono::duration<double>(t1 - t0).count();
+  const int64_t size1 = table_size();  // (re-bases the capacity monitor)
+  // (slots of the staying keys changed; a frozen engine has no pulled-but-not-
+  // applied server buffer to look up again: s_pull(insert) refuses it)
+  r.dropped = (int64_t)st[0];
+  r.segments_swept = (int64_t)st[1];
+  r.inserted = size1 + r.dropped - size0;
+  r.overwritten = n - r.inserted;
+  if (overflowed())
+    throw std::runtime_error("apply_weights_delta: an entry found no slot within the probe "
+                             "bound -- the table dropped keys of this delta");
+  return r;
 }
 
 void Engine::import_weights(const u64* keys, const float* weights, int64_t n) {

@@ -443,6 +443,33 @@ class HipBackend final : public Backend {
     copy_d2h(&n, counter_, sizeof(n));
     return (int64_t)n;
   }
+  int64_t table_export_weights_marked(const TableView& t, const OptSpec& o, const u32* bits, int L,
+                                      u64* keys_out, float* weights_out,
+                                      int64_t max_rows) override {
+    hip::launch_table_export_weights_marked(t, o, bits, L, keys_out, weights_out, max_rows,
+                                            counter_, stream_);
+    unsigned long long n = 0;
+    copy_d2h(&n, counter_, sizeof(n));
+    return (int64_t)n;
+  }
+  void frozen_upsert(const TableView& t, const OptSpec& o, const u64* keys, const float* weights,
+                     int64_t n, u32* dirty) override {
+    hip::launch_frozen_upsert(t, o, keys, weights, n, dirty, stream_);
+  }
+  // (as table_prune: launches of at most 2^28 slots over the marks workspace)
+  void frozen_sweep(const TableView& t, const OptSpec& o, const u32* dirty,
+                    unsigned long long* stats) override {
+    const int g = t.seg_log2;
+    const u64 nseg = t.cap >> g;
+    const u64 per_launch = g >= 28 ? 1 : (1ull << (28 - g));
+    XF_HIP_CHECK(hipMemsetAsync(stats + 2, 0, sizeof(unsigned long long), stream_));
+    for (u64 s0 = 0; s0 < nseg; s0 += per_launch) {
+      const u64 k = nseg - s0 < per_launch ? nseg - s0 : per_launch;
+      ensure_marks(t, k);
+      hip::launch_frozen_sweep(t, o, s0, k, dirty, split_marks_, stats + 2, stats + 1, stream_);
+    }
+    hip::launch_table_prune_finish(t.size, stats, stats + 2, stream_);
+  }
   bool serves_lr() const override { return true; }
   void serve_lr(const ServeLrArgs& a) override { hip::launch_serve_lr(a, stream_); }
   bool serves_models() const override { return true; }

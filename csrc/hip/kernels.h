@@ -68,6 +68,22 @@ void launch_delta_popcount(const u32* bits, int L, unsigned long long* counter, 
 void launch_table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
                                  float* weights_out, int64_t max_rows,
                                  unsigned long long* counter, hipStream_t st);
+// serving deltas: the marked keys (the filter bit alone) and their P resolved weights
+void launch_table_export_weights_marked(const TableView& t, const OptSpec& o, const u32* bits,
+                                        int L, u64* keys_out, float* weights_out,
+                                        int64_t max_rows, unsigned long long* counter,
+                                        hipStream_t st);
+
+// kernels_refresh.hip: a serving delta into a frozen table.  Upsert n unique
+// (key, P weights) entries, flagging dirty[segment] = 1 where the weights
+// written read as an absent key's; then, over segments [s0, s0 + k), drop the
+// slots of flagged segments that read as absent (marks as for the split),
+// adding their number to *dropped and the flagged segments to *swept
+void launch_frozen_upsert(const TableView& t, const OptSpec& o, const u64* keys,
+                          const float* weights, int64_t n, u32* dirty, hipStream_t st);
+void launch_frozen_sweep(const TableView& t, const OptSpec& o, u64 s0, u64 k, const u32* dirty,
+                         u64* marks, unsigned long long* dropped, unsigned long long* swept,
+                         hipStream_t st);
 
 // kernels_serve.hip
 void launch_serve_lr(const ServeLrArgs& a, hipStream_t st);

@@ -518,6 +518,43 @@ void launch_table_export_weights(const TableView& t, const OptSpec& o, u64* keys
   XF_HIP_CHECK(hipGetLastError());
 }
 
+// Serving deltas (docs/DESIGN.md §2): k_table_export_marked's walk and
+// compaction, k_table_export_weights' output.  The predicate is the filter bit
+// alone, not slot_exported: a marked key whose weights read as an absent key's
+// is the delta's way to say "this key left".  max_rows = 0 only counts.
+__global__ void __launch_bounds__(kBlock) k_table_export_weights_marked(
+    TableView t, OptSpec o, const u32* __restrict__ bits, int Lb, u64* __restrict__ keys_out,
+    float* __restrict__ weights_out, int64_t max_rows, unsigned long long* counter) {
+  const TableLayout& L = t.L;
+  const u64 stride = (u64)gridDim.x * blockDim.x;
+  for (u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x; s < t.cap; s += stride) {
+    const u32* sp = t.words + s * (u64)L.stride;
+    const u64 key = *reinterpret_cast<const u64*>(sp);
+    bool live = key != kEmptyKey;
+    if (live) {
+      const u64 b = delta_bit(key, Lb);
+      live = (bits[b >> 5] >> (u32)(b & 31u)) & 1u;
+    }
+    const unsigned long long idx = wave_append(counter, live);
+    if (live && (int64_t)idx < max_rows) {
+      keys_out[idx] = key;
+      for (int p = 0; p < L.P; ++p) weights_out[idx * L.P + p] = slot_weight(sp, key, p, L, o);
+    }
+  }
+}
+
+void launch_table_export_weights_marked(const TableView& t, const OptSpec& o, const u32* bits,
+                                        int L, u64* keys_out, float* weights_out,
+                                        int64_t max_rows, unsigned long long* counter,
+                                        hipStream_t st) {
+  if (L < kDeltaMinLog2 || L > kDeltaMaxLog2)
+    throw std::runtime_error("table_export_weights_marked: log2");
+  XF_HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(unsigned long long), st));
+  hipLaunchKernelGGL(k_table_export_weights_marked, dim3(grid_for((int64_t)t.cap)), dim3(kBlock),
+                     0, st, t, o, bits, L, keys_out, weights_out, max_rows, counter);
+  XF_HIP_CHECK(hipGetLastError());
+}
+
 // set bits of the filter's 2^(L - 5) words, one atomic per workgroup
 __global__ void __launch_bounds__(kBlock) k_delta_popcount(const u32* __restrict__ bits,
                                                            u64 words,

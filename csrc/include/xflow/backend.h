@@ -1074,6 +1074,26 @@ class Backend {
   // state words (max_rows = 0 only counts).  Returns the number of such keys.
   virtual int64_t table_export_weights(const TableView& t, const OptSpec& o, u64* keys_out,
                                        float* weights_out, int64_t max_rows) = 0;
+  // Serving deltas (docs/DESIGN.md §2).  table_export_weights_marked is
+  // table_export_weights with the filter bit as its only predicate: a marked
+  // key is written even when its weights read as an absent key's -- that entry
+  // is a deletion (max_rows = 0 only counts).
+  virtual int64_t table_export_weights_marked(const TableView& t, const OptSpec& o,
+                                              const u32* bits, int L, u64* keys_out,
+                                              float* weights_out, int64_t max_rows) = 0;
+  // Applying one to a frozen table, stream-ordered, in two steps.  frozen_upsert
+  // inserts or overwrites n entries (key, P weights; keys unique within the
+  // call after sanitize_key), counts the inserts into *t.size and sets
+  // dirty[segment of the slot] = 1 (u32 per segment of t, zeroed by the caller)
+  // wherever the P words written equal absent_weight's bits.  frozen_sweep
+  // drops, from the flagged segments only, every slot that reads as absent
+  // (!slot_exported) and re-packs the keys that stay as table_prune does; it
+  // subtracts the dropped count from *t.size and adds {dropped, flagged
+  // segments} to stats[0..1] (backend memory; stats[2] is its scratch).
+  virtual void frozen_upsert(const TableView& t, const OptSpec& o, const u64* keys,
+                             const float* weights, int64_t n, u32* dirty) = 0;
+  virtual void frozen_sweep(const TableView& t, const OptSpec& o, const u32* dirty,
+                            unsigned long long* stats) = 0;
   // One-launch lookup-and-score of an LR batch from a frozen table
   // (ServeLrArgs; HIP only -- the CPU backend has no launches to save)
   virtual bool serves_lr() const { return false; }

@@ -534,6 +534,36 @@ class Engine {
   std::pair<int64_t, int64_t> serve_unfused_latent() const {
     return {cfg_.serve_unfused_latent_lo, cfg_.serve_unfused_latent_hi};
   }
+  // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
+  // Producer, on a training engine with delta_track: (key, P resolved weights)
+  // of every key of the table whose touched-key bit is set -- the keys that
+  // now read as an absent key included (those entries are the deletions; no
+  // flag marks them).  Count pass, device buffers of exactly that size, then
+  // the export, as export_weights.  All three throw with tracking off and on a
+  // frozen engine; none of them clears the filter.  Sync.
+  int64_t serving_delta_count();
+  void export_weights_delta(std::vector<u64>& keys, std::vector<float>& weights);
+  // The same as a file: magic "XFLOWSD1", then save_serving's header fields
+  // and arrays.  Returns n.
+  int64_t save_serving_delta(const std::string& path);
+  // Consumer, on a frozen engine only (throws elsewhere): upsert the n entries,
+  // then sweep out every slot that reads as absent (Backend::frozen_upsert /
+  // frozen_sweep).  Keys must be unique within one call after sanitize_key (a
+  // slot then has one writer; the CPU backend checks it in the debug build).
+  // Stream-ordered on the engine's stream: an eval_step queued before the call
+  // sees the old model whole, one queued after it the new model whole.
+  // Capacity first, before any launch: the table holds at most its size + n
+  // keys afterwards; when that passes grow_load of the slots the table may
+  // grow to (table_grow = false: of the slots it has) the call throws with the
+  // table untouched, else the table grows by splits as before any insert.
+  // Syncs (the counts come back).
+  struct DeltaApplied {
+    int64_t inserted = 0, overwritten = 0;  // entries whose key was new / present
+    int64_t dropped = 0;         // slots the sweep freed
+    int64_t segments_swept = 0;  // segments the sweep read
+    double upsert_seconds = 0.0, sweep_seconds = 0.0;  // the two steps, each waited for
+  };
+  DeltaApplied apply_weights_delta(const u64* keys, const float* weights, int64_t n);
   // ---- delta checkpoints (EngineConfig::delta_track) ----------------------
   // The table's keys whose filter bit is set: their number (a count pass;
   // syncs), host copies of them and their state words (count pass, device
@@ -625,6 +655,7 @@ class Engine {
   Pairs full_to_device();
   Pairs delta_to_device();
   Pairs weights_to_device();
+  Pairs weights_delta_to_device();
   void pairs_to_host(const Pairs& p, void* keys, void* vals);
   void pairs_to_file(const Pairs& p, const std::string& path, const void* hdr, size_t hbytes);
   template <typename Fill>

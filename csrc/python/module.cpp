@@ -503,6 +503,44 @@ PYBIND11_MODULE(_xflow_native, m) {
              py::gil_scoped_release nogil;
              e.import_weights(kp, wp, n);
            })
+      // serving deltas
+      .def("serving_delta_count", &Engine::serving_delta_count,
+           py::call_guard<py::gil_scoped_release>())
+      .def("export_weights_delta",
+           [](Engine& e) {
+             std::vector<u64> k;
+             std::vector<float> w;
+             {
+               py::gil_scoped_release nogil;
+               e.export_weights_delta(k, w);
+             }
+             return py::make_tuple(to_np(k), to_np(w));
+           })
+      .def("save_serving_delta", &Engine::save_serving_delta,
+           py::call_guard<py::gil_scoped_release>())
+      .def("apply_weights_delta",
+           [](Engine& e, py::array_t<uint64_t, py::array::c_style | py::array::forcecast> keys,
+              py::array_t<float, py::array::c_style | py::array::forcecast> weights) {
+             const int64_t n = (int64_t)keys.size();
+             if ((int64_t)weights.size() != n * e.layout().P)
+               throw std::invalid_argument(
+                   "apply_weights_delta: weights must hold P floats per key");
+             const u64* kp = reinterpret_cast<const u64*>(keys.data());
+             const float* wp = weights.data();
+             Engine::DeltaApplied r;
+             {
+               py::gil_scoped_release nogil;
+               r = e.apply_weights_delta(kp, wp, n);
+             }
+             py::dict d;
+             d["inserted"] = r.inserted;
+             d["overwritten"] = r.overwritten;
+             d["dropped"] = r.dropped;
+             d["segments_swept"] = r.segments_swept;
+             d["upsert_seconds"] = r.upsert_seconds;
+             d["sweep_seconds"] = r.sweep_seconds;
+             return d;
+           })
       // delta checkpoints (EngineConfig::delta_track)
       .def("delta_count", &Engine::delta_count, py::call_guard<py::gil_scoped_release>())
       .def("delta_export",

@@ -38,12 +38,12 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 CXX = os.environ.get("CXX", "g++")
 
 COMMON_FLAGS = ["-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-ffp-contract=off",
-                "-I" + os.path.join(CSRC, "include"), "-I" + os.path.join(CSRC, "capi")]
+                "-I" + os.path.join(CSRC, "include"), "-I" + os.path.join(CSRC, "capi")] + \
+               (["-DXFLOW_DEVICE_ASSERT=1"] if DEVICE_ASSERT else [])  # (host checks too)
 # -ffp-contract=off: keep the device FTRL / loss math bit-identical to the CPU
 # backend and the reference (no silent FMA contraction).
 HIP_FLAGS = ["--offload-arch=" + ARCH, "-ffp-contract=off", "-mcode-object-version=5",
              "-I" + os.path.join(CSRC, "hip"), "-Wno-unused-result"] + \
-            (["-DXFLOW_DEVICE_ASSERT=1"] if DEVICE_ASSERT else []) + \
             (["-DXFLOW_KTIMING=1"] if KTIMING else [])
 
 HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/engine_step.cpp",

@@ -39,6 +39,17 @@ what an absent key reads, as resolved fp32 weights without optimiser state,
 (OptimConfig.kind "frozen"); ``load`` / ``check_compatible`` refuse it, and
 ``publish`` neither counts nor deletes such a directory.
 
+A serving delta version (``save_serving(..., delta_base=...)``; meta.json still
+"kind": "serving", plus "delta_base") holds, instead of the .xfw files,
+  serving-delta-<rank>-of-<world>.xfwd   magic "XFLOWSD1", then the .xfw header
+                                 fields and arrays: (key, P resolved weights) of
+                                 every key touched since the base version --
+                                 a key that now reads as an absent key included,
+                                 which is how a deletion is written
+``serving_chain`` resolves it to its full base; ``load_serving`` loads the
+base and applies the deltas in order (Engine.apply_weights_delta);
+``publish_serving`` keeps every version a kept one needs.
+
 Resume is world-size agnostic: with the same world size each rank loads its
 own shard; otherwise every rank scans all shards and imports exactly the keys
 it owns under the new hash sharding (owner = fmix64(key) >> 32 mod world).
@@ -87,6 +98,13 @@ SERVING_MAGIC = b"XFLOWSW1"
 
 def serving_name(rank: int, world: int) -> str:
     return f"serving-{rank:05d}-of-{world:05d}.xfw"
+
+
+SERVING_DELTA_MAGIC = b"XFLOWSD1"
+
+
+def serving_delta_name(rank: int, world: int) -> str:
+    return f"serving-delta-{rank:05d}-of-{world:05d}.xfwd"
 
 
 def is_serving(meta: dict) -> bool:
@@ -400,39 +418,98 @@ def load(engine, ckpt_dir: str, rank: int, world: int) -> dict:
 
 
 # ---------------------------------------------------------------- serving
+def _read_serving_file(path: str, magic: bytes, what: str):
+    with open(path, "rb") as f:
+        if f.read(8) != magic:
+            raise ValueError(f"{path}: not an xflow {what}")
+        head = f.read(40)
+        if len(head) != 40:
+            raise ValueError(f"{path}: truncated {what}")
+        hdr = struct.unpack("<6i", head[:24])
+        _total, n = struct.unpack("<QQ", head[24:])
+        P = hdr[4]
+        if P < 1 or n > (1 << 40):
+            raise ValueError(f"{path}: bad {what} header")
+        kb, wb = f.read(8 * n), f.read(4 * n * P)
+    if len(kb) != 8 * n or len(wb) != 4 * n * P:
+        raise ValueError(f"{path}: truncated {what}")
+    return hdr, np.frombuffer(kb, dtype=np.uint64), \
+        np.frombuffer(wb, dtype=np.float32).reshape(n, P)
+
+
 def read_serving(path: str):
     """(header ints, keys u64 [n], weights f32 [n, P]) of a serving file."""
-    with open(path, "rb") as f:
-        if f.read(8) != SERVING_MAGIC:
-            raise ValueError(f"{path}: not an xflow serving snapshot")
-        hdr = struct.unpack("<6i", f.read(24))
-        _total, n = struct.unpack("<QQ", f.read(16))
-        keys = np.frombuffer(f.read(8 * n), dtype=np.uint64)
-        P = hdr[4]
-        weights = np.frombuffer(f.read(4 * n * P), dtype=np.float32).reshape(n, P)
-    if len(keys) != n or weights.shape[0] != n:
-        raise ValueError(f"{path}: truncated serving snapshot")
-    return hdr, keys, weights
+    return _read_serving_file(path, SERVING_MAGIC, "serving snapshot")
+
+
+def read_serving_delta(path: str):
+    """The same of a serving delta file (``.xfwd``)."""
+    return _read_serving_file(path, SERVING_DELTA_MAGIC, "serving delta")
 
 
 def serving_counts(path: str):
     """(keys of the source table, keys kept) of a serving file, from its
     header only."""
     with open(path, "rb") as f:
-        if f.read(8) != SERVING_MAGIC:
-            raise ValueError(f"{path}: not an xflow serving snapshot")
+        if f.read(8) not in (SERVING_MAGIC, SERVING_DELTA_MAGIC):
+            raise ValueError(f"{path}: not an xflow serving snapshot or delta")
         f.seek(24, os.SEEK_CUR)
         total, n = struct.unpack("<QQ", f.read(16))
     return int(total), int(n)
 
 
 def serving_files(ckpt_dir: str) -> list:
-    """Every rank's file of a serving directory, by rank."""
-    w = int(load_meta(ckpt_dir)["world"])
-    got = sorted(glob.glob(os.path.join(ckpt_dir, "serving-*-of-%05d.xfw" % w)))
+    """Every rank's file of a serving directory, by rank (the ``.xfwd`` files
+    of a delta version)."""
+    meta = load_meta(ckpt_dir)
+    w = int(meta["world"])
+    pat = ("serving-delta-*-of-%05d.xfwd" if meta.get("delta_base") else "serving-*-of-%05d.xfw") % w
+    got = sorted(glob.glob(os.path.join(ckpt_dir, pat)))
     if len(got) != w:
-        raise FileNotFoundError(f"{ckpt_dir}: expected {w} serving files, found {len(got)}")
+        raise FileNotFoundError(f"{ckpt_dir}: expected {w} files {pat}, found {len(got)}")
     return got
+
+
+def serving_chain(ckpt_dir: str) -> list:
+    """The serving versions ``ckpt_dir`` is made of, oldest first: the full
+    snapshot its ``delta_base`` links end at, then every delta up to
+    ``ckpt_dir`` itself.  A missing link raises FileNotFoundError naming it."""
+    links = chain(ckpt_dir)
+    for d in links:
+        if not is_serving(load_meta(d)):
+            raise ValueError(f"{_tip(ckpt_dir)}: its chain holds {d}, which is not a serving version")
+    return links
+
+
+def _serving_record(meta: dict):
+    """What two serving versions of one chain must share."""
+    return meta.get("model"), meta.get("optim"), crosses_of(meta)
+
+
+def _can_serving_delta(engine, out_dir: str, world: int, delta_base: Optional[str],
+                       record) -> bool:
+    """``_can_delta`` for a serving version: tracking on, nothing happened
+    that a delta cannot carry, the filter was last cleared when the base was
+    written, and the base is a complete serving version under the same root
+    with the same world size, model, source optimiser and crosses record."""
+    if not delta_base or engine.frozen or engine.delta_log2 == 0 or engine.delta_needs_full:
+        return False
+    base = os.path.join(os.path.dirname(_tip(out_dir)), delta_base)
+    if getattr(engine, "_serving_tip", None) != (_tip(base), engine.delta_clears):
+        return False
+    try:
+        bm = load_meta(base)
+        serving_files(base)
+    except (OSError, ValueError, KeyError):
+        return False
+    return is_serving(bm) and int(bm["world"]) == world and _serving_record(bm) == record
+
+
+def mark_serving_tip(engine, out_dir: str) -> None:
+    """The engine's touched-key filter was cleared with ``out_dir`` durable on
+    every rank: the next serving version may be a delta on it -- until the
+    filter is cleared again."""
+    engine._serving_tip = (_tip(out_dir), engine.delta_clears)
 
 
 def _serving_dir(d: str) -> bool:
@@ -443,28 +520,66 @@ def _serving_dir(d: str) -> bool:
 
 
 def save_serving(engine, out_dir: str, rank: int, world: int, meta: Optional[dict] = None,
-                 barrier: Optional[Callable[[], None]] = None) -> str:
+                 barrier: Optional[Callable[[], None]] = None, delta_base: Optional[str] = None,
+                 clear: bool = True) -> str:
     """Write this rank's serving file (Engine.save_serving: the keys that
     differ from an absent key, as resolved weights; fsync'd), wait for every
     rank, then rank 0 writes meta.json -- ``save``'s protocol.  keys_total /
-    keys_kept are summed from the files' headers, which carry both counts."""
+    keys_kept are summed from the files' headers, which carry both counts.
+
+    ``delta_base``: the name of the previous serving version's directory under
+    the same root.  The rank then writes a serving delta (``.xfwd``:
+    Engine.save_serving_delta) and meta.json names the base -- under
+    ``save``'s conditions for a checkpoint delta (``_can_serving_delta``);
+    otherwise the version is a full snapshot.  As there, the ranks of one job
+    must decide alike.
+
+    The touched-key filter has one clear per version point.  ``clear`` (the
+    default): once every rank's file is durable the rank clears its filter and
+    the next serving version may be a delta on this one; a checkpoint chain
+    loses its base by that (its next version is full).  ``clear=False``: the
+    filter stays as it is, and so does the base of the next serving delta (a
+    snapshot written aside); or a checkpoint version is written from the same
+    filter at this point -- the caller saves it next (its save clears) and
+    then calls ``mark_serving_tip``."""
     os.makedirs(out_dir, exist_ok=True)
-    path = os.path.join(out_dir, serving_name(rank, world))
-    engine.save_serving(path + ".tmp")
+    optim = dataclasses.asdict(engine.optim)
+    if optim.get("kind") == "frozen":  # (a snapshot of a snapshot: the source's source)
+        optim["kind"] = optim["frozen_from"]
+    m = dict(meta or {})
+    m.pop("delta_base", None)
+    m.update(kind="serving", world=world, model=dataclasses.asdict(engine.model), optim=optim)
+    m = json.loads(json.dumps(m))  # (as a reader sees it: tuples are lists)
+    delta = _can_serving_delta(engine, out_dir, world, delta_base, _serving_record(m))
+    name, other = serving_delta_name(rank, world), serving_name(rank, world)
+    if not delta:
+        name, other = other, name
+    path = os.path.join(out_dir, name)
+    (engine.save_serving_delta if delta else engine.save_serving)(path + ".tmp")
     _fsync_file(path + ".tmp")
     os.replace(path + ".tmp", path)
+    stale = os.path.join(out_dir, other)  # (an interrupted save of the other kind)
+    if os.path.exists(stale):
+        os.remove(stale)
     (barrier or _default_barrier)()
+    if clear and not engine.frozen and engine.delta_log2:
+        engine.delta_clear()
+        engine._delta_tip = None  # (a checkpoint delta would miss what was marked before)
+        mark_serving_tip(engine, out_dir)
     if rank == 0:
-        counts = [serving_counts(os.path.join(out_dir, serving_name(r, world)))
+        counts = [serving_counts(os.path.join(out_dir, (serving_delta_name if delta else
+                                                        serving_name)(r, world)))
                   for r in range(world)]
-        optim = dataclasses.asdict(engine.optim)
-        if optim.get("kind") == "frozen":  # (a snapshot of a snapshot: the source's source)
-            optim["kind"] = optim["frozen_from"]
-        m = dict(meta or {})
-        m.pop("delta_base", None)
-        m.update(kind="serving", world=world, model=dataclasses.asdict(engine.model),
-                 optim=optim, keys_total=sum(c[0] for c in counts),
-                 keys_kept=sum(c[1] for c in counts))
+        kinds = [len(glob.glob(os.path.join(out_dir, pat % world)))
+                 for pat in ("serving-delta-*-of-%05d.xfwd", "serving-*-of-%05d.xfw")]
+        if kinds[0] and kinds[1]:
+            raise RuntimeError(f"{out_dir}: the ranks did not agree on a full or a delta serving "
+                               f"version (delta, full files: {kinds}, world {world})")
+        if delta:
+            m.update(delta_base=delta_base, keys_total=sum(c[0] for c in counts),
+                     keys_delta=sum(c[1] for c in counts))
+        else:
+            m.update(keys_total=sum(c[0] for c in counts), keys_kept=sum(c[1] for c in counts))
         mtmp = os.path.join(out_dir, "meta.json.tmp")
         with open(mtmp, "w") as f:
             json.dump(m, f, indent=1)
@@ -484,30 +599,69 @@ def frozen_optim(meta: dict) -> dict:
     return o
 
 
-def load_serving(engine, ckpt_dir: str) -> dict:
-    """Import every rank's serving file into one frozen engine."""
-    meta = load_meta(ckpt_dir)
-    if not is_serving(meta):
-        raise ValueError(f"{ckpt_dir}: not a serving snapshot (use checkpoint.load)")
-    if not engine.frozen:
-        raise ValueError("load_serving: the engine must be frozen (OptimConfig.kind 'frozen')")
+def check_serving_header(engine, path: str, hdr) -> None:
+    """A serving file's header (a snapshot's or a delta's) against the frozen
+    engine that is to take it."""
     lay = engine.layout
     from xflow_amd.config import FM_MATH, MVM_MATH, OPT_KINDS
 
     exp = (lay["kind"], int(engine.model.v_dim), FM_MATH[engine.model.fm_math],
            MVM_MATH[engine.model.mvm_math], lay["P"], OPT_KINDS[engine.optim.frozen_from])
-    for p in serving_files(ckpt_dir):
+    got = tuple(hdr[:6])
+    # (v_dim, fm_math and mvm_math only mean something to their own model)
+    same = got[0] == exp[0] and got[4] == exp[4] and got[5] == exp[5] and \
+        (exp[0] == 0 or got[1] == exp[1]) and (exp[0] != 1 or got[2] == exp[2]) and \
+        (exp[0] != 2 or got[3] == exp[3])
+    if not same:
+        raise ValueError(f"{path}: snapshot header {got} does not match this engine {exp}")
+
+
+def read_serving_deltas(engine, version_dir_: str) -> list:
+    """[(keys, weights)] of one serving delta version, every rank's file read
+    into host memory and its header checked against ``engine``."""
+    out = []
+    for p in serving_files(version_dir_):
+        hdr, keys, weights = read_serving_delta(p)
+        check_serving_header(engine, p, hdr)
+        out.append((keys, weights))
+    return out
+
+
+def apply_serving_deltas(engine, deltas: list) -> dict:
+    """Apply what ``read_serving_deltas`` read; the counts of every file summed."""
+    tot = {"inserted": 0, "overwritten": 0, "dropped": 0, "segments_swept": 0}
+    for keys, weights in deltas:
+        if len(keys):
+            r = engine.apply_weights_delta(keys, weights)
+            for k in tot:
+                tot[k] += r[k]
+    return tot
+
+
+def load_serving(engine, ckpt_dir: str) -> dict:
+    """Import every rank's serving file into one frozen engine; a delta tip:
+    its chain's full snapshot first, then each delta version applied in order.
+    Any world size per version: every rank's file goes into the one engine."""
+    meta = load_meta(ckpt_dir)
+    if not is_serving(meta):
+        raise ValueError(f"{ckpt_dir}: not a serving snapshot (use checkpoint.load)")
+    if not engine.frozen:
+        raise ValueError("load_serving: the engine must be frozen (OptimConfig.kind 'frozen')")
+    links = serving_chain(ckpt_dir)
+    for p in serving_files(links[0]):
         hdr, keys, weights = read_serving(p)
-        got = tuple(hdr[:6])
-        # (v_dim, fm_math and mvm_math only mean something to their own model)
-        same = got[0] == exp[0] and got[4] == exp[4] and got[5] == exp[5] and \
-            (exp[0] == 0 or got[1] == exp[1]) and (exp[0] != 1 or got[2] == exp[2]) and \
-            (exp[0] != 2 or got[3] == exp[3])
-        if not same:
-            raise ValueError(f"{p}: snapshot header {got} does not match this engine {exp}")
+        check_serving_header(engine, p, hdr)
         if len(keys):
             engine.import_weights(keys, weights)
+    for d in links[1:]:
+        apply_serving_deltas(engine, read_serving_deltas(engine, d))
     return meta
+
+
+def serving_chain_keys(ckpt_dir: str) -> int:
+    """An upper bound of the keys a frozen engine holds after loading the
+    version: the full base's kept keys plus every delta's entries."""
+    return sum(serving_counts(p)[1] for d in serving_chain(ckpt_dir) for p in serving_files(d))
 
 
 LATEST = "LATEST"
@@ -533,6 +687,29 @@ def publish(root: str, epoch: int, keep: int = 2) -> None:
     for d in vers[-keep:]:  # the kept versions and every link of their chains
         try:
             needed.update(chain(d))
+        except (OSError, ValueError):
+            needed.add(_tip(d))
+    for d in vers[:-keep]:
+        if _tip(d) not in needed:
+            shutil.rmtree(d, ignore_errors=True)
+
+
+def publish_serving(root: str, epoch: int, keep: int = 2) -> None:
+    """``publish`` for a root of serving versions: point LATEST at the
+    version and drop all but the newest ``keep`` serving versions -- and the
+    versions those are deltas on (``serving_chain``)."""
+    tmp = os.path.join(root, LATEST + ".tmp")
+    with open(tmp, "w") as f:
+        f.write(os.path.basename(version_dir(root, epoch)) + "\n")
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, os.path.join(root, LATEST))
+    _fsync_dir(root)
+    vers = [d for d in sorted(glob.glob(os.path.join(root, "epoch-*"))) if _serving_dir(d)]
+    needed = set()
+    for d in vers[-keep:]:
+        try:
+            needed.update(serving_chain(d))
         except (OSError, ValueError):
             needed.add(_tip(d))
     for d in vers[:-keep]:

@@ -128,6 +128,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after the last epoch every rank writes its shard's serving snapshot "
                          "here: only the keys that differ from an absent key, as resolved fp32 "
                          "weights (xflow_amd.serve loads it; it cannot be resumed from)")
+    ap.add_argument("--serving-every", type=int, default=0,
+                    help="with --save-serving DIR: at the end of every N-th epoch write a serving "
+                         "version DIR/epoch-XXXXXX/ (a delta on the previous one) and point "
+                         "DIR/LATEST at it; xflow_amd.serve's refresh follows it (0: off)")
+    ap.add_argument("--serving-full-every", type=int, default=8,
+                    help="--serving-every: every K-th serving version of a chain is a full snapshot")
     ap.add_argument("--metrics", default="", help="JSON-lines metrics file (rank 0)")
     ap.add_argument("--trace-dir", default="", help="torch.profiler chrome trace directory")
     return ap
@@ -148,6 +154,7 @@ def config_from_args(a) -> TrainConfig:
         save_every=a.save_every, resume_dir=a.resume,
         save_delta=a.save_delta, delta_full_every=a.delta_full_every,
         save_serving=a.save_serving,
+        serving_every=a.serving_every, serving_full_every=a.serving_full_every,
         prune_every=a.prune_every, prune_max_n=a.prune_max_n, gauc_field=a.gauc_field,
         metrics_file=a.metrics, async_p2p=a.async_p2p, async_ps=a.async_ps,
         staleness=a.staleness,
@@ -158,7 +165,7 @@ def config_from_args(a) -> TrainConfig:
         engine=EngineConfig(table_log2_cap=a.log2_cap, sum_slices=a.sum_slices,
                             max_log2_cap=a.max_log2_cap, table_grow=not a.no_table_grow,
                             admit_min_count=a.admit_min_count, admit_log2=a.admit_log2,
-                            delta_track=a.save_delta, delta_log2=a.delta_log2))
+                            delta_track=a.save_delta or a.serving_every > 0, delta_log2=a.delta_log2))
 
 
 def main(argv=None) -> int:

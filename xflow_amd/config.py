@@ -249,6 +249,15 @@ class TrainConfig:
     # (checkpoint.save_serving: only the keys that differ from an absent key,
     # as resolved fp32 weights) into this directory; "": off
     save_serving: str = ""
+    # serving deltas (docs/DESIGN.md §2): at the end of every serving_every-th
+    # epoch every rank writes a serving version <save_serving>/epoch-XXXXXX/ and
+    # rank 0 points <save_serving>/LATEST at it -- a delta on the previous one
+    # (only the keys touched since, deletions included), every
+    # serving_full_every-th version of a chain a full snapshot.  Needs
+    # save_serving; turns engine.delta_track on.  0: off (one snapshot after
+    # the last epoch, in save_serving itself)
+    serving_every: int = 0
+    serving_full_every: int = 8
     # prune the table (Engine.prune: drop keys whose weights are all exactly
     # zero) at the end of every N-th epoch, 0: never; prune_max_n: with FTRL
     # only keys with every n <= it (negative: no bound)

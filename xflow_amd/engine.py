@@ -217,6 +217,9 @@ class Engine:
                            serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
+        # delta_clear() calls so far: a serving or checkpoint delta is only
+        # good on a base the filter was last cleared at (checkpoint.py)
+        self.delta_clears = 0
 
     # ---- properties -------------------------------------------------------
     @property
@@ -378,6 +381,7 @@ class Engine:
         """Zero the filter and reset needs_full (no-op with tracking off)."""
         self._sync_stream()
         self._e.delta_clear()
+        self.delta_clears += 1
 
     def server_slots(self, buf: int = 0) -> np.ndarray:
         """Table slots the last s_pull into server buffer ``buf`` recorded
@@ -872,6 +876,44 @@ class Engine:
         self._sync_stream()
         self._e.import_weights(np.ascontiguousarray(keys, dtype=np.uint64),
                                np.ascontiguousarray(weights, dtype=np.float32).reshape(-1))
+
+    # ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
+    def serving_delta_count(self) -> int:
+        """Entries export_weights_delta() would write (a count pass; syncs)."""
+        self._sync_stream()
+        return int(self._e.serving_delta_count())
+
+    def export_weights_delta(self):
+        """(keys u64 [n], weights f32 [n, P]) of every key of the table whose
+        touched-key bit is set (EngineConfig.delta_track), each with its P
+        resolved weights -- a key that now reads exactly as an absent key
+        included: that entry is a deletion, and nothing else marks it.  The
+        filter is not cleared.  Raises with tracking off and on a frozen
+        engine."""
+        self._sync_stream()
+        k, w = self._e.export_weights_delta()
+        return k, w.reshape(len(k), self.params_per_key)
+
+    def save_serving_delta(self, path: str) -> int:
+        """export_weights_delta() as one ``.xfwd`` file (magic "XFLOWSD1", then
+        the ``.xfw`` layout); returns the entries written."""
+        self._sync_stream()
+        return int(self._e.save_serving_delta(path))
+
+    def apply_weights_delta(self, keys, weights) -> dict:
+        """Apply a serving delta to this frozen engine: upsert every (key, P
+        weights) entry, then sweep out every slot that now reads as an absent
+        key.  Keys must be unique within one call.  Queued on the engine's
+        stream: an eval_step before it scores with the old model, one after it
+        with the new one.  Raises -- the table untouched -- when size + n would
+        pass grow_load of the slots the table may grow to.  Returns
+        {inserted, overwritten, dropped, segments_swept, upsert_seconds,
+        sweep_seconds}."""
+        self._sync_stream()
+        d = self._e.apply_weights_delta(
+            np.ascontiguousarray(keys, dtype=np.uint64),
+            np.ascontiguousarray(weights, dtype=np.float32).reshape(-1))
+        return {k: (float(v) if k.endswith("seconds") else int(v)) for k, v in d.items()}
 
     def save(self, path: str) -> None:
         self._sync_stream()

@@ -31,6 +31,16 @@ converts any checkpoint (a delta tip included) part by part: part r of N loads
 only the keys it owns (checkpoint.load's resharding) into a table sized for
 them and writes serving-r-of-N.xfw, so the peak memory is 1/N of the model.
 
+A Predictor opened on a versioned root of serving versions (the trainer's
+``--serving-every``) follows the training job: ``refresh()`` resolves LATEST
+again and, when the new version's chain of serving deltas contains the loaded
+one, applies the missing deltas to the live frozen table (inserts, overwrites
+and deletions on the device, Engine.apply_weights_delta) -- otherwise it builds
+a new engine off to the side and swaps it in.
+
+        POST /refresh                                -> refresh()'s dict
+    python -m xflow_amd.serve --checkpoint serving/ --refresh-seconds 30
+
 Rows are scored in batches of ``max_rows``; one engine serves requests one
 at a time (a lock around the device work).
 """
@@ -40,6 +50,7 @@ import argparse
 import math
 import os
 import threading
+import time
 from typing import Optional, Sequence
 
 import numpy as np
@@ -72,47 +83,119 @@ class Predictor:
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
                  max_nnz_per_row: int = 64, serve_fused: bool = True,
                  serve_unfused_rows=None, serve_unfused_rows_latent=None):
-        self.ckpt = _resolve(ckpt)
-        meta = checkpoint.load_meta(self.ckpt)
-        self.snapshot = checkpoint.is_serving(meta)
-        self.model = _fields(ModelConfig, meta["model"])
-        self.optim = _fields(OptimConfig, checkpoint.frozen_optim(meta) if self.snapshot
-                             else meta["optim"])
-        self.meta = meta
-        # the feature crosses the model was trained with (absent: none): every
-        # request is crossed the same way before it is scored
-        self.crosses, self.cross_field_base = checkpoint.crosses_of(meta)
-        # (key counts from the shard headers: nothing else is read twice; a
-        # delta version: its full base's shards plus every delta's of its
-        # chain, an upper bound -- a delta repeats keys its bases hold)
-        if self.snapshot:
-            n_keys = sum(checkpoint.serving_counts(p)[1]
-                         for p in checkpoint.serving_files(self.ckpt))
-        else:
-            n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(self.ckpt))
-        # every shard's keys in one table at load <= 0.5 (no growth while serving)
-        lg = max(16, int(math.ceil(math.log2(max(2 * n_keys, 1)))))
+        self.root = ckpt  # (refresh() resolves it again)
         if device is None:
             device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
         self.max_rows = int(max_rows)
-        self.engine = Engine(self.model, self.optim,
-                             EngineConfig(table_log2_cap=lg, max_rows=self.max_rows,
-                                          max_nnz=self.max_rows * (int(max_nnz_per_row)
-                                                                   + len(self.crosses)),
-                                          table_grow=False, serve_fused=serve_fused,
-                                          **({} if serve_unfused_rows is None else
-                                             {"serve_unfused_rows": tuple(serve_unfused_rows)}),
-                                          **({} if serve_unfused_rows_latent is None else
-                                             {"serve_unfused_rows_latent":
-                                              tuple(serve_unfused_rows_latent)})),
-                             device=device)
-        if self.snapshot:
-            checkpoint.load_serving(self.engine, self.ckpt)
-        else:
-            checkpoint.load(self.engine, self.ckpt, 0, 1)
-        self.keys = self.engine.table_size()  # (a snapshot: the keys it kept)
+        self._max_nnz_per_row = int(max_nnz_per_row)
+        self._serve_cfg = dict(serve_fused=serve_fused,
+                               **({} if serve_unfused_rows is None else
+                                  {"serve_unfused_rows": tuple(serve_unfused_rows)}),
+                               **({} if serve_unfused_rows_latent is None else
+                                  {"serve_unfused_rows_latent": tuple(serve_unfused_rows_latent)}))
         self._lock = threading.Lock()
+        self._refreshing = threading.Lock()  # (one refresh at a time)
+        self._adopt(self._load(_resolve(ckpt)))
+
+    def _load(self, ckpt_dir: str) -> dict:
+        """A new engine holding the version ``ckpt_dir``, and what describes it."""
+        meta = checkpoint.load_meta(ckpt_dir)
+        snapshot = checkpoint.is_serving(meta)
+        model = _fields(ModelConfig, meta["model"])
+        optim = _fields(OptimConfig, checkpoint.frozen_optim(meta) if snapshot else meta["optim"])
+        # the feature crosses the model was trained with (absent: none): every
+        # request is crossed the same way before it is scored
+        crosses, cross_field_base = checkpoint.crosses_of(meta)
+        # (key counts from the file headers: nothing else is read twice; a
+        # delta version: its full base's keys plus every delta's of its
+        # chain, an upper bound -- a delta repeats keys its bases hold)
+        if snapshot:
+            n_keys = checkpoint.serving_chain_keys(ckpt_dir)
+        else:
+            n_keys = sum(checkpoint.shard_keys(p) for p in checkpoint.chain_files(ckpt_dir))
+        # every shard's keys in one table at load <= 0.5.  A training
+        # checkpoint's table never grows while serving; a snapshot's may, by
+        # segment splits, when serving deltas bring more keys (refresh)
+        lg = max(16, int(math.ceil(math.log2(max(2 * n_keys, 1)))))
+        engine = Engine(model, optim,
+                        EngineConfig(table_log2_cap=lg, max_rows=self.max_rows,
+                                     max_nnz=self.max_rows * (self._max_nnz_per_row + len(crosses)),
+                                     table_grow=snapshot, **self._serve_cfg),
+                        device=self.device)
+        if snapshot:
+            checkpoint.load_serving(engine, ckpt_dir)
+        else:
+            checkpoint.load(engine, ckpt_dir, 0, 1)
+        return dict(ckpt=ckpt_dir, meta=meta, snapshot=snapshot, model=model, optim=optim,
+                    crosses=crosses, cross_field_base=cross_field_base, engine=engine,
+                    keys=engine.table_size())  # (a snapshot: the keys it kept)
+
+    def _adopt(self, v: dict) -> None:
+        for k, x in v.items():
+            setattr(self, k, x)
+
+    # ---------------------------------------------------------------- refresh
+    def refresh(self) -> dict:
+        """Follow the root this Predictor was opened on to its LATEST version.
+        Returns {version, mode, inserted, overwritten, dropped, segments_swept,
+        seconds}; mode "delta": the missing serving deltas were applied to the
+        live table under the lock (their files read before it is taken);
+        "full": a new engine was built off to the side and swapped in under
+        the lock -- the new version's chain does not contain the loaded one,
+        its model, crosses or source optimiser differ, this Predictor holds a
+        training checkpoint, or the table refused a delta for capacity;
+        "none": nothing is new.  A request sees one version or the other
+        whole, never a mix."""
+        t0 = time.perf_counter()
+        counts = {"inserted": 0, "overwritten": 0, "dropped": 0, "segments_swept": 0}
+        with self._refreshing:
+            tip = _resolve(self.root)
+            mode = "none"
+            if os.path.abspath(tip) != os.path.abspath(self.ckpt):
+                mode = "full"
+                missing = self._missing_deltas(tip)
+                if missing is not None:
+                    try:
+                        # (host reads outside the lock: requests go on meanwhile)
+                        deltas = [(d, checkpoint.read_serving_deltas(self.engine, d))
+                                  for d in missing]
+                        for d, files in deltas:
+                            with self._lock:  # a version lands whole
+                                r = checkpoint.apply_serving_deltas(self.engine, files)
+                                self.ckpt, self.meta = d, checkpoint.load_meta(d)
+                                self.keys = self.engine.table_size()
+                            for k in counts:
+                                counts[k] += r[k]
+                        mode = "delta"
+                    except RuntimeError:  # (no room for a delta: the table is at a whole version)
+                        mode = "full"
+                if mode == "full":
+                    v = self._load(tip)
+                    with self._lock:
+                        self._adopt(v)
+            return dict(version=os.path.basename(os.path.abspath(self.ckpt)), mode=mode, **counts,
+                        seconds=time.perf_counter() - t0)
+
+    def _missing_deltas(self, tip: str):
+        """The serving delta versions between the loaded version and ``tip``,
+        oldest first; None when the live table cannot be brought there by
+        deltas."""
+        if not self.snapshot:
+            return None
+        try:
+            meta = checkpoint.load_meta(tip)
+            if not checkpoint.is_serving(meta):
+                return None
+            links = [os.path.abspath(d) for d in checkpoint.serving_chain(tip)]
+        except (OSError, ValueError):
+            return None
+        cur = os.path.abspath(self.ckpt)
+        same = all(meta.get(k) == self.meta.get(k) for k in ("model", "optim")) and \
+            checkpoint.crosses_of(meta) == checkpoint.crosses_of(self.meta)
+        if cur not in links or not same:
+            return None
+        return links[links.index(cur) + 1:]
 
     # ---------------------------------------------------------------- scoring
     def predict_csr(self, keys: np.ndarray, row_ptr: np.ndarray,
@@ -190,7 +273,7 @@ class Predictor:
 
 # -------------------------------------------------------------------- service
 def make_app(pred: Predictor):
-    """FastAPI app: POST /predict, GET /health."""
+    """FastAPI app: POST /predict, POST /refresh, GET /health."""
     from fastapi import FastAPI, HTTPException
     from pydantic import create_model
 
@@ -206,7 +289,12 @@ def make_app(pred: Predictor):
     def health():
         return {"status": "ok", "model": pred.model.kind, "keys": int(pred.keys),
                 "device": str(pred.device), "checkpoint": pred.ckpt,
-                "snapshot": bool(pred.snapshot)}
+                "snapshot": bool(pred.snapshot),
+                "version": os.path.basename(os.path.abspath(pred.ckpt))}
+
+    @app.post("/refresh")
+    def refresh():
+        return pred.refresh()
 
     def predict(req):
         if (req.libffm is None) == (req.keys is None):
@@ -221,6 +309,27 @@ def make_app(pred: Predictor):
     predict.__annotations__ = {"req": Req}
     app.post("/predict")(predict)
     return app
+
+
+def poll_refresh(pred: Predictor, seconds: float, stop: Optional[threading.Event] = None):
+    """A daemon thread that calls ``pred.refresh()`` every ``seconds`` until
+    ``stop`` is set; a failed refresh is logged and the loaded version stays."""
+    import logging
+
+    stop = stop or threading.Event()
+
+    def loop():
+        while not stop.wait(seconds):
+            try:
+                r = pred.refresh()
+                if r["mode"] != "none":
+                    logging.getLogger(__name__).info("refreshed: %s", r)
+            except Exception:  # noqa: BLE001 - keep serving the loaded version
+                logging.getLogger(__name__).exception("refresh failed")
+
+    t = threading.Thread(target=loop, name="xflow-refresh", daemon=True)
+    t.start()
+    return t, stop
 
 
 def export_snapshot(ckpt: str, out: str, parts: int = 1,
@@ -280,9 +389,13 @@ def main(argv=None) -> int:
     ap.add_argument("--port", type=int, default=8080)
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--max-rows", type=int, default=65536)
+    ap.add_argument("--refresh-seconds", type=float, default=0.0,
+                    help="poll the root's LATEST this often and refresh() (0: only POST /refresh)")
     a = ap.parse_args(argv)
     pred = Predictor(a.checkpoint, device=torch.device("cpu") if a.cpu else None,
                      max_rows=a.max_rows)
+    if a.refresh_seconds > 0:
+        poll_refresh(pred, a.refresh_seconds)
     import uvicorn
 
     uvicorn.run(make_app(pred), host=a.host, port=a.port, log_level="warning")

@@ -126,6 +126,20 @@ class Trainer:
             if cfg.delta_full_every < 1:
                 raise ValueError("--delta-full-every must be >= 1")
             ecfg.delta_track = True
+        if cfg.serving_every:
+            if cfg.serving_every < 0 or cfg.serving_full_every < 1:
+                raise ValueError("--serving-every must be >= 0 and --serving-full-every >= 1")
+            if not cfg.save_serving:
+                raise ValueError("--serving-every needs --save-serving DIR (the versions' root)")
+            roots = {os.path.abspath(r) for r in (cfg.checkpoint_dir, cfg.resume_dir) if r}
+            if os.path.abspath(cfg.save_serving) in roots:
+                raise ValueError("--serving-every: --save-serving must not be the checkpoint root "
+                                 "(each has a LATEST of its own)")
+            ecfg.delta_track = True
+        # serving deltas: the serving version last written (the next one's base)
+        # and the deltas written since its chain's full snapshot
+        self._serving_base = None
+        self._serving_links = 0
         # delta checkpoints: the version last saved or resumed from (the base of
         # the next delta) and the deltas written since its chain's full version
         self._delta_base = None
@@ -510,8 +524,20 @@ class Trainer:
                                                            self.device)[0])
             root = cfg.resume_dir or cfg.checkpoint_dir
             every = cfg.save_every or (1 if os.environ.get("XFLOW_CKPT_EVERY_EPOCH") else 0)
-            if root and every and self.epoch % every == 0:
+            ckpt_now = bool(root and every and self.epoch % every == 0)
+            # One clear of the touched-key filter per version point: a serving
+            # version and a checkpoint version of the same epoch end are both
+            # written from the filter as it stands -- the serving one first,
+            # without clearing; the checkpoint's save then clears, with both
+            # durable.  Alone, the serving writer clears.
+            sdir = None
+            if cfg.serving_every and self.epoch % cfg.serving_every == 0:
+                sdir, rec["serving_kind"] = self.save_serving_versioned(cfg.save_serving,
+                                                                        clear=not ckpt_now)
+            if ckpt_now:
                 rec["ckpt_kind"], rec["ckpt_keys"] = self.save_versioned(root)
+                if sdir:
+                    checkpoint.mark_serving_tip(self.table, sdir)
             self.metrics.log(**rec)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
@@ -649,7 +675,7 @@ class Trainer:
             self.init_push()
         # cfg.epochs counts the whole run: a resumed job trains the rest
         self.train_epochs(max(0, self.cfg.epochs - self.epoch) if self.resumed else self.cfg.epochs)
-        if self.cfg.save_serving:
+        if self.cfg.save_serving and not self.cfg.serving_every:
             self.save_serving(self.cfg.save_serving)
         res = None
         if self.rank == 0:
@@ -671,18 +697,43 @@ class Trainer:
         xdist.barrier()
         return path
 
-    def save_serving(self, out_dir: str) -> str:
-        """Every rank writes its own shard's serving snapshot (no gather);
-        returns this rank's file (checkpoint.save_serving)."""
+    def save_serving(self, out_dir: str, delta_base: Optional[str] = None,
+                     clear: bool = True) -> str:
+        """Every rank writes its own shard's serving snapshot (no gather), or
+        its serving delta on ``delta_base``; returns this rank's file
+        (checkpoint.save_serving)."""
         if hasattr(self.sharded, "flush"):
             self.sharded.flush()
         path = checkpoint.save_serving(
             self.table, out_dir, self.rank, self.world,
             meta=dict({"epoch": self.epoch, "steps": self.steps},
                       **checkpoint.cross_meta(self.crosses, self._cross_base)),
-            barrier=xdist.barrier)
+            barrier=xdist.barrier, delta_base=delta_base, clear=clear)
         xdist.barrier()
         return path
+
+    def save_serving_versioned(self, root: str, clear: bool = True):
+        """``save_versioned`` for serving versions: this epoch's version under
+        ``root`` -- a serving delta on the version last written there when
+        fewer than ``serving_full_every`` - 1 deltas follow the chain's full
+        snapshot and no rank needs a full one -- then rank 0 publishes it as
+        LATEST (checkpoint.publish_serving).  Returns (its directory, "full" |
+        "delta")."""
+        d = checkpoint.version_dir(root, self.epoch)
+        base = None
+        b = self._serving_base
+        if (b and b != os.path.abspath(d) and os.path.dirname(b) == os.path.abspath(root)
+                and self._serving_links < self.cfg.serving_full_every - 1):
+            if xdist.all_sum([float(self.table.delta_needs_full)], self.device)[0] == 0:
+                base = os.path.basename(b)
+        path = self.save_serving(d, delta_base=base, clear=clear)
+        delta = path.endswith(".xfwd")
+        self._serving_base = os.path.abspath(d)
+        self._serving_links = self._serving_links + 1 if delta else 0
+        if self.rank == 0:
+            checkpoint.publish_serving(root, self.epoch)
+        xdist.barrier()
+        return d, ("delta" if delta else "full")
 
     def load(self, ckpt_dir: str) -> dict:
         # (before anything is loaded: a table trained with other crosses holds
