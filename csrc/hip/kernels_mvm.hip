@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(mvm_block_for(D, kRed)) k_mvm2(FwdArgs a) {
       // Dup-free rows: S of an occurrence is the key's own v, so the gradient
       // factorises as T_k/(1+v_k) with T = loss*M per row: the row's T goes
       // to red_rowv and the vector-record reduction (k_fm_std_red<D-1, ..,
-      // kSplit> + k_red_sum_vec<.., kMvm>) sums T per (key, slice) and
+      // kScaled> + k_red_sum_vec<.., kMvm>) sums T per (key, slice) and
       // divides once.  Rows with a repeated field (S = field sum): global
       // atomics, and T = 0 (their occurrences still leave records, for the
       // slice bits of a multi-slice step).

@@ -604,9 +604,7 @@ __global__ void __launch_bounds__(kCsrBlock) k_red_csr(const void* __restrict__ 
       pd[q] = (u32)((u64)RedRec<NV>::dest(pr[q]) - blo);
     }
   }
-  auto rank = [&](u32 d) -> u32 {
-    return wscan[d >> 5] + (u32)__popc(bits[d >> 5] & ((1u << (d & 31)) - 1u));
-  };
+  auto rank = [&](u32 d) -> u32 { return bitmap_rank(bits, wscan, d); };
   auto emit = [&](u32 o, u32 d, const long long* a) {
     const u32 slice = d & smask;
     const double rows = c.rows ? (double)c.rows[slice] : 1.0;
@@ -689,19 +687,8 @@ __global__ void __launch_bounds__(kCsrBlock) k_red_csr(const void* __restrict__ 
       for (u32 kk = (u32)tid; kk < nk; kk += kCsrBlock) {
         const u64 k = k0 + kk;
         if (k >= nuq) break;
-        const u32 o = kk << sl;
-        u32 cnt = 0, first = ~0u;
-        if (sl < 5) {  // (the key's 2^sl presence bits inside one word)
-          const u32 m = (bits[o >> 5] >> (o & 31)) & ((1u << (1u << sl)) - 1u);
-          cnt = (u32)__popc(m);
-          if (m) first = o + (u32)__ffs(m) - 1u;
-        } else {
-          for (u32 w = 0; w < (1u << (sl - 5)); ++w) {
-            const u32 x = bits[(o >> 5) + w];
-            cnt += (u32)__popc(x);
-            if (x && first == ~0u) first = o + 32u * w + (u32)__ffs(x) - 1u;
-          }
-        }
+        u32 cnt, first;
+        key_entries(bits, kk << sl, sl, cnt, first);
         c.cnt[k] = cnt;
         c.off[k] = out + (cnt ? rank(first) : 0u);
       }

@@ -1,6 +1,15 @@
 // xflow-amd: vector-record reduction of the standard-FM and MVM gradients,
-// its CSR form and MVM's repeated-field passes (gfx950).  The launcher starts
-// its producers itself, so they are here too: k_fm_std_red and k_fm_std_fwd.
+// its CSR form and MVM's repeated-field passes (gfx950).  In launch order
+// (launch_vec_reduction, the one place that starts them):
+//   k_fm_std_fwd   standard FM's forward: (loss, loss*vs_k) per row to red_rowv
+//                  (MVM's rows come from k_mvm2<.., kRed>)
+//   k_fm_std_red   the producer: one vector record per (key, slice, column)
+//   k_red_scan     per bucket, the workgroups' record counts to prefixes
+//   then either    k_scan_small + k_red_csr_vec: several slices as CSR entries
+//   or             (k_red_scatter +) k_red_sum_vec: the gradient rows
+//   k_mdup_*       MVM: the rows with a repeated field, added after
+// The segment table, the record add, the row expansion and the CSR bitmap
+// helpers the two sums share are in model_common.h.
 #include "model_common.h"
 
 namespace xflow {
@@ -30,15 +39,14 @@ namespace hip {
 // [bucket][workgroup]) and k_red_sum_vec<D, true> reads a bucket's records
 // straight from the producers' regions -- no k_red_scatter pass over the
 // (48-byte) records.
-// kSplit: the forward ran in k_fm_std_fwd (its own high-occupancy launch: this
-// kernel's LDS tables leave a CU two waves per SIMD for the row gathers), which
-// left (loss, loss*vs_k) per row in red_rowv -- the same floats the fused form
-// computes here, so both forms sum identical fixed-point values.
+// The row's vector comes from red_rowv: the forward ran before, in a launch of
+// its own (standard FM: k_fm_std_fwd, at high occupancy -- this kernel's LDS
+// tables leave a CU two waves per SIMD for the row gathers; MVM: k_mvm2).
 // kScaled (MVM): T = loss*M spans many orders of magnitude (a product over
 // fields), beyond any one static fixed-point scale: the int64 sums use the
 // step's scale (fx_scale_bits of FwdArgs::red_vmax, set by the forward).
 
-template <int D, int BLOCK, bool kSeg = false, bool kSplit = false, bool kScaled = false>
+template <int D, int BLOCK, bool kSeg, bool kScaled>
 __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
   XF_KT_DECL;
   constexpr int PS = fm_ps(D);
@@ -71,7 +79,6 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
   __shared__ int s_wmax[BLOCK / kWave];
   const BatchView& b = a.batch;
   const u32* __restrict__ pos = a.pos;
-  const float4* __restrict__ wp4 = reinterpret_cast<const float4*>(a.wpull);
   const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
   const bool active = r < b.rows;
   RowSpan rs;
@@ -107,7 +114,7 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
   XF_KT(0);
   const u32 S = (u32)a.S;
   const u32 sl = active ? (u32)slice_of(b, r, a.S) : 0u;
-  // kSplit: the row's vector (FM: loss, loss*vs_k; MVM: T_k = loss*M_k); a
+  // the row's vector (FM: loss, loss*vs_k; MVM: T_k = loss*M_k); a
   // one-slice MVM step emits nothing for an all-zero one (a zero contribution
   // -- every unique key is pushed anyway), several slices need every
   // occurrence (the records' presence gives the slice bits), and so does
@@ -115,7 +122,7 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
   // every unique-order row (the pull does not zero them, Engine::train_step)
   float t[PS];
   bool live = active;
-  if (kSplit && active) {
+  if (active) {
     const float4* rv = reinterpret_cast<const float4*>(a.red_rowv + (size_t)r * PS);
 #pragma unroll
     for (int q = 0; q < PS / 4; ++q) {
@@ -171,43 +178,12 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
     __syncthreads();
   }
   XF_KT(1);
-  StatAcc st;
-  float loss = 0.0f;
-  float vs[D];  // (kSplit: loss*vs_k)
+  float f[NV];  // (a lane past the rows: zeros)
 #pragma unroll
-  for (int k = 0; k < D; ++k) vs[k] = 0.0f;
-  if (kSplit && active) {
-    loss = t[0];
+  for (int c = 0; c < NV; ++c) f[c] = 0.0f;
+  if (active) {
 #pragma unroll
-    for (int k = 0; k < D; ++k) vs[k] = t[1 + k];
-  } else if (active) {
-    float wx = 0.0f, vp = 0.0f;
-    for (int j = 0; j < len; ++j) {
-      const float4* src = wp4 + (size_t)pos[rs.at(j)] * (PS / 4);
-      float w[PS];
-#pragma unroll
-      for (int q = 0; q < PS / 4; ++q) {
-        const float4 v4 = src[q];
-        w[4 * q] = v4.x;
-        w[4 * q + 1] = v4.y;
-        w[4 * q + 2] = v4.z;
-        w[4 * q + 3] = v4.w;
-      }
-      wx += w[0];
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        vs[k] += w[1 + k];
-        vp += w[1 + k] * w[1 + k];
-      }
-    }
-    float sq = 0.0f;
-#pragma unroll
-    for (int k = 0; k < D; ++k) sq += vs[k] * vs[k];
-    const float p = sigmoid_ref(wx + 0.5f * (sq - vp));
-    const float lab = b.labels[r];
-    loss = p - lab;
-    if (a.pctr) a.pctr[r] = p;
-    st.add(p, lab);
+    for (int c = 0; c < NV; ++c) f[c] = t[c];
   }
   const int lane = lane_id();
   u32 written = 0, bad = 0;
@@ -219,16 +195,11 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
   // column walk needs no second gather of the pulled row; k_red_sum_vec
   // expands C - v*B once per dest)
   Acc rowv[NV];
-  if constexpr (kScaled) {  // (kSplit: the row's vector, |.| <= the step's vmax)
-    rowv[0] = fx_from_rt(loss, fxs);
+  if constexpr (kScaled) {  // (|.| <= the step's vmax)
 #pragma unroll
-    for (int k = 0; k < D; ++k) rowv[1 + k] = fx_from_rt(vs[k], fxs);
+    for (int c = 0; c < NV; ++c) rowv[c] = fx_from_rt(f[c], fxs);
   } else {
     // per-component scale from the workgroup's largest |value| (see s_acc)
-    float f[NV];
-    f[0] = loss;
-#pragma unroll
-    for (int k = 0; k < D; ++k) f[1 + k] = kSplit ? vs[k] : loss * vs[k];
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       float m = f[c] == f[c] ? fabsf(f[c]) : INFINITY;
@@ -377,7 +348,8 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
       a.red_hist[at] = kSeg ? s_hist[i] - sub_start[at] : s_hist[i];
     }
   }
-  st.bad |= bad;
+  StatAcc st;  // (the forward counted the rows: only the flag)
+  st.bad = bad;
   flush_stats<BLOCK>(st, a.stats, a.fx_bad);
   XF_KT(7);
   XF_KT_FLUSH();
@@ -390,8 +362,7 @@ __global__ void __launch_bounds__(BLOCK) k_fm_std_red(FwdArgs a) {
 // kSeg: no scatter pass -- bucket bk's records are the producers' sub-ranges
 // (k_fm_std_red<.., true>): segment g holds hist[bk][g+1] - hist[bk][g]
 // records (hist: k_red_scan's exclusive prefix over the workgroups, tot[bk]
-// the total) at region(g) + subs[bk][g]; record i of the bucket is found by a
-// binary search of the LDS-staged prefix.
+// the total) at region(g) + subs[bk][g] (SegTable).
 // (kSegMaxGroups: backend.h)
 // G: segment-table capacity (groups); 512 keeps the rank-8 form at 76 KB of
 // LDS, two workgroups per CU (the per-unit phases are latency chains)
@@ -417,7 +388,6 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum_vec(const void* __restric
   constexpr int kShift = red_shift(NV);
   constexpr u32 kR = 1u << kShift;
   constexpr int kFx = FxBits<1>::kFx;
-  constexpr int W = vec_rec_words(NV);
   using Rec = typename VecRedRec<NV>::T;
   __shared__ long long acc[kR * NV];
   // MVM: the step's fixed-point scale (k_fm_std_red kScaled)
@@ -426,8 +396,7 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum_vec(const void* __restric
   // pull's zeros, so the epilogue stores without reading them
   const bool rows_zero = kMvm && dup && *dup == 0u;
   __shared__ u32 seen[kR / 32];
-  __shared__ u32 s_pre[kSeg ? G : 1];
-  __shared__ u32 s_seg[kSeg ? G : 1];
+  __shared__ SegTable<(kSeg ? G : 1)> segs;
   const Rec* src = static_cast<const Rec*>(sorted);
   const int shift = geom.shift(kShift);
   const u32 act = (u32)geom.active(shift, nb);
@@ -446,49 +415,17 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum_vec(const void* __restric
       end = start[bk + 1];
     }
     if (beg == end) continue;  // (block-uniform)
-    if constexpr (kSeg) {
-      // segment g: records [s_pre[g], s_pre[g+1]) of the bucket, at s_seg[g] + i
-      const size_t row0 = (size_t)bk * sg.groups;
-      for (int g = threadIdx.x; g < sg.groups; g += kRedBlock) {
-        const int64_t r0 = (int64_t)g * sg.rows_per_group;
-        const u32 base = (u32)(sg.b.row_ptr ? sg.b.row_ptr[r0] : r0 * sg.b.nnz_per_row);
-        const u32 p = sg.hist[row0 + g];
-        s_pre[g] = p;
-        s_seg[g] = base + sg.subs[row0 + g] - p;
-      }
-    }
+    if constexpr (kSeg) segs.stage(sg, bk);
   for (u32 sub = 0; sub < nsubs; ++sub) {
     const u64 lo = ((u64)bk << shift) + ((u64)sub << kShift);
     for (u32 i = threadIdx.x; i < kR * NV; i += kRedBlock) acc[i] = 0ll;
     for (u32 i = threadIdx.x; i < kR / 32; i += kRedBlock) seen[i] = 0u;
     lds_barrier();
     for (u32 i = beg + threadIdx.x; i < end; i += kRedBlock) {
-      u32 ri = i;
-      if constexpr (kSeg) {
-        int l0 = 0, l1 = sg.groups;  // first g with s_pre[g] > i
-        while (l0 < l1) {
-          const int m = (l0 + l1) >> 1;
-          if (s_pre[m] <= i) l0 = m + 1;
-          else l1 = m;
-        }
-        ri = s_seg[l0 - 1] + i;
-      }
-      const Rec r = src[ri];
+      const Rec r = src[kSeg ? segs.at(sg.groups, i) : i];
       const u64 l = (u64)r.q[0].x - lo;
       if (l >= kR) continue;  // (another sub-unit's dest)
-      u32 wv[W];
-#pragma unroll
-      for (int q = 0; q < W / 4; ++q) {
-        wv[4 * q] = r.q[q].x;
-        wv[4 * q + 1] = r.q[q].y;
-        wv[4 * q + 2] = r.q[q].z;
-        wv[4 * q + 3] = r.q[q].w;
-      }
-      long long* ap = acc + l * NV;
-#pragma unroll
-      for (int c = 0; c < NV; ++c)
-        atomicAdd(reinterpret_cast<unsigned long long*>(&ap[c]),
-                  (unsigned long long)fx_from_rt(__uint_as_float(wv[1 + c]), fxs));
+      vec_rec_add<NV>(r, fxs, acc + l * NV);
       atomicOr(&seen[l >> 5], 1u << (l & 31));
     }
     lds_barrier();
@@ -515,16 +452,15 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum_vec(const void* __restric
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
           const long long t = acc[l * NV + c];
-          if (t != 0 && w[c] != 0.0f) o[c] += (float)(fx_to_double_rt(t, fxs) / (1.0 + (double)w[c]));
+          if (t != 0 && w[c] != 0.0f) o[c] += (float)mvm_grad(t, w[c], fxs);
         }
 #pragma unroll
         for (int q = 0; q < PS / 4; ++q) r4[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
         continue;
       }
-      // (B, C_0..C_{D-1}) -> g_w = B, g_v[k] = C_k - v_k*B (k_fm_std_red)
       const double B = fx_to_double_rt(acc[l * NV], fxs);
       const float4* v4 = reinterpret_cast<const float4*>(wpull + ((lo + l) / (u64)S) * PS);
-      float o[PS];
+      float o[PS];  // the pulled row, then the gradient row
 #pragma unroll
       for (int q = 0; q < PS / 4; ++q) {
         const float4 v = v4[q];
@@ -535,8 +471,7 @@ __global__ void __launch_bounds__(kRedBlock) k_red_sum_vec(const void* __restric
       }
       o[0] = (float)B;
 #pragma unroll
-      for (int c = 1; c < PS; ++c)
-        o[c] = c < NV ? (float)(fx_to_double_rt(acc[l * NV + c], fxs) - (double)o[c] * B) : 0.0f;
+      for (int c = 1; c < PS; ++c) o[c] = c < NV ? (float)fm_std_grad(acc[l * NV + c], o[c], B, fxs) : 0.0f;
       float* row = grad + (lo + l) * PS;
       if (out) {  // the unique-order row (FwdArgs::red_out); S > 1: [unique][slice]
         const u64 slot = (lo + l) / (u64)S;
@@ -616,8 +551,7 @@ __global__ void __launch_bounds__(kRedBlock) k_red_csr_vec(const void* __restric
   __shared__ u32 bits[kWords];
   __shared__ u32 wscan[kWords];
   __shared__ u32 rdest[kR];
-  __shared__ u32 s_pre[G];
-  __shared__ u32 s_seg[G];
+  __shared__ SegTable<G> segs;
   __shared__ u32 s_tot;
   const Rec* src = static_cast<const Rec*>(recs);
   const int shift = geom.shift(kShift);
@@ -631,23 +565,8 @@ __global__ void __launch_bounds__(kRedBlock) k_red_csr_vec(const void* __restric
   for (u32 bk = blockIdx.x; bk < act; bk += gridDim.x) {
     const u32 nrec = sg.tot[bk];
     if (nrec == 0) continue;  // (block-uniform)
-    const size_t row0 = (size_t)bk * sg.groups;
-    for (int g = tid; g < sg.groups; g += kRedBlock) {
-      const int64_t r0 = (int64_t)g * sg.rows_per_group;
-      const u32 base = (u32)(sg.b.row_ptr ? sg.b.row_ptr[r0] : r0 * sg.b.nnz_per_row);
-      const u32 pf = sg.hist[row0 + g];
-      s_pre[g] = pf;
-      s_seg[g] = base + sg.subs[row0 + g] - pf;
-    }
-    auto rec_at = [&](u32 i) -> const Rec& {
-      int l0 = 0, l1 = sg.groups;  // first g with s_pre[g] > i
-      while (l0 < l1) {
-        const int m = (l0 + l1) >> 1;
-        if (s_pre[m] <= i) l0 = m + 1;
-        else l1 = m;
-      }
-      return src[s_seg[l0 - 1] + i];
-    };
+    segs.stage(sg, bk);
+    auto rec_at = [&](u32 i) -> const Rec& { return src[segs.at(sg.groups, i)]; };
     u32 ebase = estart[bk];
     const u64 blo = (u64)bk << shift;
     const u64 bhi = blo + (1ull << shift);
@@ -668,22 +587,13 @@ __global__ void __launch_bounds__(kRedBlock) k_red_csr_vec(const void* __restric
       lds_barrier();
       const u32 ndist = s_tot;
       if (ndist == 0) continue;  // (block-uniform)
-      auto rank = [&](u32 l) {
-        return wscan[l >> 5] + (u32)__popc(bits[l >> 5] & ((1u << (l & 31)) - 1u));
-      };
       // (3) the keys' (off, cnt): the window holds 2^(15 - slog2) keys whole
       for (u32 k = tid; k < (1u << (kCsrVecWin - sl)); k += kRedBlock) {
-        const u32 l0 = k << sl;
-        u32 cnt;
-        if (sl >= 5) {
-          cnt = 0;
-          for (u32 w = l0 >> 5; w < (l0 + (1u << sl)) >> 5; ++w) cnt += (u32)__popc(bits[w]);
-        } else {
-          cnt = (u32)__popc((bits[l0 >> 5] >> (l0 & 31)) & ((1u << (1u << sl)) - 1u));
-        }
+        u32 cnt, first;
+        key_entries(bits, k << sl, sl, cnt, first);
         if (cnt) {
-          const u32 u = (u32)((lo + l0) >> sl);
-          co.off[u] = ebase + rank(l0);
+          const u32 u = (u32)((lo + (k << sl)) >> sl);
+          co.off[u] = ebase + bitmap_rank(bits, wscan, first);
           co.cnt[u] = cnt;
         }
       }
@@ -695,23 +605,11 @@ __global__ void __launch_bounds__(kRedBlock) k_red_csr_vec(const void* __restric
           const Rec& rr = rec_at(i);
           const u64 l = (u64)rr.q[0].x - lo;
           if (l >= (1ull << kCsrVecWin)) continue;
-          const u32 r = rank((u32)l) - c0;
+          const u32 r = bitmap_rank(bits, wscan, (u32)l) - c0;
           if (r >= kR) continue;
           const Rec r4 = rr;
-          u32 wv[vec_rec_words(NV)];
-#pragma unroll
-          for (int q = 0; q < vec_rec_words(NV) / 4; ++q) {
-            wv[4 * q] = r4.q[q].x;
-            wv[4 * q + 1] = r4.q[q].y;
-            wv[4 * q + 2] = r4.q[q].z;
-            wv[4 * q + 3] = r4.q[q].w;
-          }
-          rdest[r] = wv[0];  // (every record of the rank writes the same dest)
-          long long* ap = acc + r * NV;
-#pragma unroll
-          for (int c = 0; c < NV; ++c)
-            atomicAdd(reinterpret_cast<unsigned long long*>(&ap[c]),
-                      (unsigned long long)fx_from_rt(__uint_as_float(wv[1 + c]), fxs));
+          rdest[r] = r4.q[0].x;  // (every record of the rank writes the same dest)
+          vec_rec_add<NV>(r4, fxs, acc + r * NV);
         }
         lds_barrier();
         const u32 nr = min(kR, ndist - c0);
@@ -722,21 +620,20 @@ __global__ void __launch_bounds__(kRedBlock) k_red_csr_vec(const void* __restric
           const float* v = wpull + (u64)u * PS;
           float* e = ent + (u64)(ebase + c0 + t) * (u32)ew;
           e[0] = __uint_as_float(s);
+          const long long* ap = acc + t * NV;
           if constexpr (kMvm) {
 #pragma unroll
             for (int c = 0; c < NV; ++c) {
-              const long long tc = acc[t * NV + c];
+              const long long tc = ap[c];
               if (c < P)
-                e[1 + c] = tc != 0 && v[c] != 0.0f
-                               ? (float)(fx_to_double_rt(tc, fxs) / (1.0 + (double)v[c]) / rows)
-                               : 0.0f;
+                e[1 + c] = tc != 0 && v[c] != 0.0f ? (float)(mvm_grad(tc, v[c], fxs) / rows) : 0.0f;
             }
           } else {
-            const double B = fx_to_double_rt(acc[t * NV], fxs);
+            const double B = fx_to_double_rt(ap[0], fxs);
             e[1] = (float)(B / rows);
 #pragma unroll
             for (int c = 1; c < NV; ++c)
-              if (c < P) e[1 + c] = (float)((fx_to_double_rt(acc[t * NV + c], fxs) - (double)v[c] * B) / rows);
+              if (c < P) e[1 + c] = (float)(fm_std_grad(ap[c], v[c], B, fxs) / rows);
           }
         }
         lds_barrier();  // (the next chunk reinitialises what this one read)
@@ -832,9 +729,8 @@ static void launch_mdup(const FwdArgs& a, int D, hipStream_t st) {
   hipLaunchKernelGGL(k_mdup_done, dim3(1), dim3(1), 0, st, a.mdup.n, a.mdup.vmax);
 }
 
-// Standard-math FM forward of the split form (k_fm_std_red<.., kSplit>): one
-// lane per row, the same sums in the same order as the fused kernel; writes
-// (loss, loss*vs_0 .. loss*vs_{D-1}, pad) per row to red_rowv.
+// Standard-math FM forward, ahead of the producer (k_fm_std_red): one lane per
+// row; writes (loss, loss*vs_0 .. loss*vs_{D-1}, pad) per row to red_rowv.
 template <int D>
 __global__ void __launch_bounds__(kBlock) k_fm_std_fwd(FwdArgs a) {
   constexpr int PS = fm_ps(D);
@@ -893,11 +789,11 @@ template <int D, bool kMvm>
 void launch_vec_reduction(const FwdArgs& a, hipStream_t st) {
   constexpr int BLOCK = fmstd_block(D);
   constexpr int NV = 1 + D;
-  if (kMvm && (!a.red_rowv || !a.red_vmax))
-    throw std::runtime_error("MVM vector reduction needs red_rowv and red_vmax");
+  if (!a.red_rowv || (kMvm && !a.red_vmax))
+    throw std::runtime_error("vector reduction needs the rows' vectors (red_rowv; MVM: red_vmax too)");
   const int groups = (int)((a.batch.rows + BLOCK - 1) / BLOCK);
   const RedGeom geom = red_geom(a);
-  const u32 grid = std::min<u32>((u32)(a.red_nb * a.red_nsub), (u32)device_cus());
+  const u32 units = (u32)(a.red_nb * a.red_nsub), cus = (u32)device_cus();
   if (a.red_out && a.S != 1 && !a.red_masks)
     throw std::runtime_error("vector-record red_out with several slices needs the slice bits");
   u32* masks = a.S > 1 ? a.red_masks : nullptr;
@@ -912,77 +808,59 @@ void launch_vec_reduction(const FwdArgs& a, hipStream_t st) {
                    a.red_sorted_words * 8 / (vec_rec_words(NV) * 4) < (1ll << 32);
   if (a.red_maxb > vec_red_max_buckets(D) || (!seg && a.red_maxb > kRedMaxBuckets))
     throw std::runtime_error("vector reduction: bucket cap beyond the producer's");
-  const bool split = a.red_rowv != nullptr;
-  // (one slice: the rows' only other writer is k_mvm2's repeated-field atomics)
-  const u32* dup = kMvm && a.S == 1 ? a.red_dup : nullptr;
-  if (a.red_csr.cnt) {  // several slices as CSR entries (Engine::train_step_csr)
-    if (!seg || !split || a.red_out || !a.red_nuq || a.S != (1 << a.red_csr.slog2) ||
-        (kMvm && !a.mdup.rec) ||
-        a.red_csr.slog2 > red_shift(NV) || a.red_csr.P > NV || a.red_csr.P < 1 ||
-        a.red_csr.ew < csr_row_words(a.red_csr.P))
-      throw std::runtime_error("CSR vector reduction: split scatter-free form, unique positions, "
-                               "S = 2^slog2 <= 2^shift, full-row entries (MVM: dup records)");
-  }
+  const bool csr = a.red_csr.cnt != nullptr;  // several slices as CSR entries (Engine::train_step_csr)
+  if (csr && (!seg || a.red_out || !a.red_nuq || a.S != (1 << a.red_csr.slog2) ||
+              (kMvm && !a.mdup.rec) ||
+              a.red_csr.slog2 > red_shift(NV) || a.red_csr.P > NV || a.red_csr.P < 1 ||
+              a.red_csr.ew < csr_row_words(a.red_csr.P)))
+    throw std::runtime_error("CSR vector reduction: scatter-free form, unique positions, "
+                             "S = 2^slog2 <= 2^shift, full-row entries (MVM: dup records)");
 #ifdef XFLOW_KTIMING
   ktime_dump("fmstd (init prepass rowv insert bar1 flush bar2 tail)", 8, st);
 #endif
-  if (split && !kMvm)
+  if (!kMvm)
     hipLaunchKernelGGL(k_fm_std_fwd<D>, dim3((int)((a.batch.rows + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, st, a);
-  if (a.red_csr.cnt) {
-    hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, true, true, kMvm>), dim3(groups), dim3(BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_red_scan, dim3(a.red_nb), dim3(kBlock), 0, st, a.red_hist, groups,
-                       a.red_tot, geom, red_shift(NV));
-    u32* estart = a.red_tot + a.red_nb + 1;  // (nb + 1 words: the scatter's starts, unused here)
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kRedBlock), 0, st, a.red_tot, a.red_nb, estart,
-                       geom, red_shift(NV));
-    const SegSrc sg{a.red_hist, a.red_tot, reinterpret_cast<const u32*>(a.red_sorted), a.batch,
-                    BLOCK, groups};
-    const u32 g2 = std::min<u32>((u32)a.red_nb, (u32)device_cus());
-    if (groups <= 512)
-      hipLaunchKernelGGL((k_red_csr_vec<D, 512, kMvm>), dim3(g2), dim3(kRedBlock), 0, st,
-                         static_cast<const void*>(a.red_pairs), geom, a.red_nb, sg, estart,
-                         a.red_csr, a.wpull, a.red_vmax);
-    else
-      hipLaunchKernelGGL((k_red_csr_vec<D, kSegMaxGroups, kMvm>), dim3(g2), dim3(kRedBlock), 0, st,
-                         static_cast<const void*>(a.red_pairs), geom, a.red_nb, sg, estart,
-                         a.red_csr, a.wpull, a.red_vmax);
-    if (kMvm && a.mdup.rec) launch_mdup(a, NV, st);  // (rows with a repeated field)
-    return;
-  }
-  if (seg) {
-    if (split) hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, true, true, kMvm>), dim3(groups), dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, true>), dim3(groups), dim3(BLOCK), 0, st, a);
-    hipLaunchKernelGGL(k_red_scan, dim3(a.red_nb), dim3(kBlock), 0, st, a.red_hist, groups,
-                       a.red_tot, geom, red_shift(NV));
-    const SegSrc sg{a.red_hist, a.red_tot, reinterpret_cast<const u32*>(a.red_sorted), a.batch,
-                    BLOCK, groups};
-    if (groups <= 512) {
-      const u32 grid2 = std::min<u32>((u32)(a.red_nb * a.red_nsub), 2u * (u32)device_cus());
-      hipLaunchKernelGGL((k_red_sum_vec<D, true, 512, kMvm>), dim3(grid2), dim3(kRedBlock), 0, st,
-                         static_cast<const void*>(a.red_pairs), nullptr, a.grad, geom, a.red_nb,
-                         a.red_out, a.red_inv, a.wpull, a.S, sg, masks, a.red_vmax, dup);
-    } else {
-      hipLaunchKernelGGL((k_red_sum_vec<D, true, kSegMaxGroups, kMvm>), dim3(grid), dim3(kRedBlock), 0, st,
-                         static_cast<const void*>(a.red_pairs), nullptr, a.grad, geom, a.red_nb,
-                         a.red_out, a.red_inv, a.wpull, a.S, sg, masks, a.red_vmax, dup);
-    }
-    if (kMvm && a.mdup.rec && a.red_out) launch_mdup(a, NV, st);  // (rows with a repeated field)
-    return;
-  }
-  if (split) hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, false, true, kMvm>), dim3(groups), dim3(BLOCK), 0, st, a);
-  else hipLaunchKernelGGL((k_fm_std_red<D, BLOCK>), dim3(groups), dim3(BLOCK), 0, st, a);
+  if (seg) hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, true, kMvm>), dim3(groups), dim3(BLOCK), 0, st, a);
+  else hipLaunchKernelGGL((k_fm_std_red<D, BLOCK, false, kMvm>), dim3(groups), dim3(BLOCK), 0, st, a);
   hipLaunchKernelGGL(k_red_scan, dim3(a.red_nb), dim3(kBlock), 0, st, a.red_hist, groups,
                      a.red_tot, geom, red_shift(NV));
+  // nb + 1 words: the CSR entries' bucket bases, or the scatter's bucket starts
   u32* start = a.red_tot + a.red_nb + 1;
-  hipLaunchKernelGGL((k_red_scatter<NV, VecRedRec<NV>>), dim3(groups), dim3(kRedBlock), 0, st,
-                     a.batch, BLOCK, static_cast<const void*>(a.red_pairs), a.red_count,
-                     a.red_hist, a.red_tot, start, a.red_nb, static_cast<void*>(a.red_sorted),
-                     geom);
-  hipLaunchKernelGGL((k_red_sum_vec<D, false, kSegMaxGroups, kMvm>), dim3(grid), dim3(kRedBlock), 0, st,
-                     static_cast<const void*>(a.red_sorted), start, a.grad, geom, a.red_nb,
-                     a.red_out, a.red_inv, a.wpull, a.S, SegSrc{}, masks, a.red_vmax, dup);
-  if (kMvm && a.mdup.rec && a.red_out) launch_mdup(a, NV, st);  // (rows with a repeated field)
+  const SegSrc sg{a.red_hist, a.red_tot, reinterpret_cast<const u32*>(a.red_sorted), a.batch,
+                  BLOCK, groups};
+  if (csr) {
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(kRedBlock), 0, st, a.red_tot, a.red_nb, start,
+                       geom, red_shift(NV));
+    launch_seg_groups(groups, [&](auto g) {
+      hipLaunchKernelGGL((k_red_csr_vec<D, decltype(g)::value, kMvm>),
+                         dim3(std::min<u32>((u32)a.red_nb, cus)), dim3(kRedBlock), 0, st,
+                         static_cast<const void*>(a.red_pairs), geom, a.red_nb, sg, start,
+                         a.red_csr, a.wpull, a.red_vmax);
+    });
+  } else {
+    // (one slice: the rows' only other writer is k_mvm2's repeated-field atomics)
+    const u32* dup = kMvm && a.S == 1 ? a.red_dup : nullptr;
+    auto sums = [&](auto kernel, u32 cap, const void* recs, const u32* starts, const SegSrc& s) {
+      hipLaunchKernelGGL(kernel, dim3(std::min<u32>(units, cap)), dim3(kRedBlock), 0, st, recs,
+                         starts, a.grad, geom, a.red_nb, a.red_out, a.red_inv, a.wpull, a.S, s,
+                         masks, a.red_vmax, dup);
+    };
+    if (seg) {
+      launch_seg_groups(groups, [&](auto g) {  // (the 512-group table: two workgroups per CU)
+        constexpr int G = decltype(g)::value;
+        sums(k_red_sum_vec<D, true, G, kMvm>, G == 512 ? 2u * cus : cus, a.red_pairs, nullptr, sg);
+      });
+    } else {
+      hipLaunchKernelGGL((k_red_scatter<NV, VecRedRec<NV>>), dim3(groups), dim3(kRedBlock), 0, st,
+                         a.batch, BLOCK, static_cast<const void*>(a.red_pairs), a.red_count,
+                         a.red_hist, a.red_tot, start, a.red_nb, static_cast<void*>(a.red_sorted),
+                         geom);
+      sums(k_red_sum_vec<D, false, kSegMaxGroups, kMvm>, cus, a.red_sorted, start, SegSrc{});
+    }
+  }
+  // (MVM rows with a repeated field: added to the entries, or to the unique-order rows)
+  if (kMvm && a.mdup.rec && (csr || a.red_out)) launch_mdup(a, NV, st);
 }
 #define XF_VEC_RED(D)                                                       \
   template void launch_vec_reduction<D, false>(const FwdArgs&, hipStream_t); \

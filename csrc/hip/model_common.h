@@ -615,6 +615,94 @@ struct SegSrc {
   int rows_per_group, groups;
 };
 
+// A bucket's records where the scatter-free producers left them
+// (k_fm_std_red<.., kSeg>): segment g -- producer workgroup g's sub-range of
+// bucket bk -- holds the bucket's records [pre[g], pre[g + 1]).  The table
+// lives in the kernel's LDS (G >= sg.groups; a workgroup of kRedBlock):
+// stage() fills it (a barrier before the first at()), at() gives record i's
+// index in the producers' buffer by a binary search of the prefix.
+template <int G>
+struct SegTable {
+  u32 pre[G], seg[G];
+  __device__ __forceinline__ void stage(const SegSrc& sg, u32 bk) {
+    const size_t row0 = (size_t)bk * sg.groups;
+    for (int g = threadIdx.x; g < sg.groups; g += kRedBlock) {
+      const int64_t r0 = (int64_t)g * sg.rows_per_group;
+      const u32 base = (u32)(sg.b.row_ptr ? sg.b.row_ptr[r0] : r0 * sg.b.nnz_per_row);
+      const u32 p = sg.hist[row0 + g], s = base + sg.subs[row0 + g] - p;
+      pre[g] = p;
+      seg[g] = s;
+    }
+  }
+  __device__ __forceinline__ u32 at(int groups, u32 i) const {
+    int l0 = 0, l1 = groups;  // first g with pre[g] > i
+    while (l0 < l1) {
+      const int m = (l0 + l1) >> 1;
+      if (pre[m] <= i) l0 = m + 1;
+      else l1 = m;
+    }
+    return seg[l0 - 1] + i;
+  }
+};
+
+// Adds a vector record's NV values, in fixed point at scale fxs, to a dest's
+// NV int64 LDS accumulators (order-free: deterministic).
+template <int NV>
+__device__ __forceinline__ void vec_rec_add(const typename VecRedRec<NV>::T& r, int fxs, long long* acc) {
+  constexpr int W = vec_rec_words(NV);
+  u32 wv[W];
+#pragma unroll
+  for (int q = 0; q < W / 4; ++q) {
+    wv[4 * q] = r.q[q].x;
+    wv[4 * q + 1] = r.q[q].y;
+    wv[4 * q + 2] = r.q[q].z;
+    wv[4 * q + 3] = r.q[q].w;
+  }
+#pragma unroll
+  for (int c = 0; c < NV; ++c)
+    atomicAdd(reinterpret_cast<unsigned long long*>(&acc[c]),
+              (unsigned long long)fx_from_rt(__uint_as_float(wv[1 + c]), fxs));
+}
+
+// One component of a dest's gradient from its fixed-point sums and the key's
+// pulled v, in double: the caller rounds it (the CSR entries after the
+// division by the slice's rows).
+//   standard FM  g_w = B, g_v[k] = C_k - v_k*B  (B = Σ loss, C_k = Σ loss*vs_k)
+//   MVM          g_k = T_k / (1 + v_k); none where the sum or v_k is zero
+//                (mvm_worker.cc:137-170): the caller keeps those two tests
+__device__ __forceinline__ double fm_std_grad(long long ck, float vk, double B, int fxs) {
+  return fx_to_double_rt(ck, fxs) - (double)vk * B;
+}
+__device__ __forceinline__ double mvm_grad(long long tk, float vk, int fxs) {
+  return fx_to_double_rt(tk, fxs) / (1.0 + (double)vk);
+}
+
+// CSR entries from a presence bitmap of dests key << sl | slice (k_red_csr,
+// k_red_csr_vec): the distinct present dests in dest order are the keys'
+// entries in (key, slice) order.  wscan: the exclusive prefix popcounts of
+// the bitmap's words.
+// rank of dest d: the present dests below it -- a present dest's entry index
+__device__ __forceinline__ u32 bitmap_rank(const u32* bits, const u32* wscan, u32 d) {
+  return wscan[d >> 5] + (u32)__popc(bits[d >> 5] & ((1u << (d & 31)) - 1u));
+}
+// the key whose 2^sl presence bits start at bit o: its entries, and the first
+// one's dest (~0u: none; no present dest lies between o and it)
+__device__ __forceinline__ void key_entries(const u32* bits, u32 o, int sl, u32& cnt, u32& first) {
+  cnt = 0;
+  first = ~0u;
+  if (sl < 5) {  // (the key's bits inside one word)
+    const u32 m = (bits[o >> 5] >> (o & 31)) & ((1u << (1u << sl)) - 1u);
+    cnt = (u32)__popc(m);
+    if (m) first = o + (u32)__ffs(m) - 1u;
+  } else {
+    for (u32 w = 0; w < (1u << (sl - 5)); ++w) {
+      const u32 x = bits[(o >> 5) + w];
+      cnt += (u32)__popc(x);
+      if (x && first == ~0u) first = o + 32u * w + (u32)__ffs(x) - 1u;
+    }
+  }
+}
+
 // Rows per producer workgroup on the reduction path: the model's R, or --
 // when the batch fills at most an eighth of the CUs (a slice group of a step
 // of 256 slices or more) -- halved (down to 128) until it fills them, within
@@ -648,6 +736,15 @@ inline void launch_rows(int R, F&& f) {
     case 256: f(std::integral_constant<int, 256>{}); break;
     default: f(std::integral_constant<int, 128>{}); break;
   }
+}
+
+// Calls f(std::integral_constant<int, G>) for the capacity of the LDS segment
+// table that holds `groups` producer workgroups (SegTable<G>): 512 -- which
+// keeps k_red_sum_vec at two workgroups per CU -- or kSegMaxGroups.
+template <typename F>
+inline void launch_seg_groups(int groups, F&& f) {
+  if (groups <= 512) f(std::integral_constant<int, 512>{});
+  else f(std::integral_constant<int, kSegMaxGroups>{});
 }
 
 // kernels_reduce.hip (launch_reduction: NV = 1, 2)

@@ -38,6 +38,7 @@ MODELS = {
     "fm_ref": (ModelConfig(kind="fm", v_dim=4, fm_math="reference"), OptimConfig(kind="sgd"), "fm_ref"),
     "fm_std4": (ModelConfig(kind="fm", v_dim=4, fm_math="standard"), OptimConfig(kind="sgd"), "rows"),
     "fm_std8": (ModelConfig(kind="fm", v_dim=8, fm_math="standard"), OptimConfig(kind="sgd"), "rows"),
+    "fm_std32": (ModelConfig(kind="fm", v_dim=32, fm_math="standard"), OptimConfig(kind="sgd"), "rows"),
     "mvm": (ModelConfig(kind="mvm", v_dim=4), OptimConfig(kind="sgd", sgd_v_init=0.9), "rows"),
 }
 
@@ -384,6 +385,73 @@ def test_fm_entries_within_the_ref64_bound(gpu_device, name, shape):
     assert ratio <= 1.0, (name, shape, ratio)
     again = _fused(gpu_device, name, spec, None, plant=True)
     got2, _ = _check_structure(spec, name, again)
+    np.testing.assert_array_equal(got2.bits, got.bits)
+
+
+WIDE_ROWS = 513 * 128    # fmstd_block(32) = 128 rows a producer workgroup: 513 of them
+
+
+def _wide(S):
+    """65 664 rows of two fields over 4 000 keys; S whole slices of 8 208 rows."""
+    k = _vocab(4000, 12)[np.random.default_rng(12).integers(0, 4000, size=(WIDE_ROWS, 2))]
+    return Spec(k, S, WIDE_ROWS // S, 12)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [1, 8])
+def test_fm_std_more_than_512_producer_workgroups(gpu_device, S):
+    """Standard FM at v_dim = 32 with 513 producer workgroups: the segment
+    tables of k_red_sum_vec (S = 1) and k_red_csr_vec (S = 8, CSR) take their
+    kSegMaxGroups capacity, which no other shape of the suite reaches.  Both
+    against ref64 within this file's bound for standard FM, e_g plus
+    csr_ref.quantisation_fm_std at the producer's 128 rows: the CSR entries as
+    test_fm_entries_within_the_ref64_bound checks them; the one-slice step has
+    no entries to read, so its bound goes through test_row_structures'
+    expected_update to the weights after the step.  (test_row_structures
+    itself gives expected_update e_g alone, a narrower bound: its batches have
+    a few occurrences a key, where the producer's fixed-point step -- relative
+    to the workgroup's largest value, not to the occurrence's own -- stays
+    inside e_g's slack; with ~33 occurrences a key that is not derived.)"""
+    name = "fm_std32"
+    m = MODELS[name][0]
+    spec = _wide(S)
+    assert -(-spec.rows // 128) == 513 and len(spec.keys) == 2 * WIDE_ROWS
+
+    def bound_of(ref, W):
+        sl, want, eg = csr_ref.from_ref64(ref)
+        return sl, want, eg + csr_ref.quantisation_fm_std(ref, W, spec.keys, spec.row_ptr, spec.labels,
+                                                          spec.slice_rows, spec.S, block=128)
+
+    if S == 1:
+        eng = _engine(gpu_device, name, spec)
+        _plant(eng, name, spec.ukeys)
+        W = eng.pull(spec.ukeys)
+        assert eng.native.step_plan(1)["grad"] == "unique_rows"
+        eng.train_step(spec.batch(gpu_device))
+        after = eng.pull(spec.ukeys)
+        assert not eng.overflowed() and np.isfinite(after).all()
+        ref = ref64.reference("fm", m.v_dim, spec.ukeys, W, spec.keys, spec.row_ptr, spec.fgid,
+                              spec.labels, spec.slice_rows, m.fm_math)
+        assert ref.touched.all() and len(ref.slice_rows) == 1
+        ref.e_g = bound_of(ref, W)[2].reshape(ref.e_g.shape)
+        want, tol = trs.expected_update(ref, "sgd", (W,), W, False)
+        assert np.abs(after - W).max() > 0
+        ratio = trs.worst_ratio(np.abs(after.astype(np.float64) - want), tol)
+        trs.note_ratio("grad_wide", "gpu", m, ratio)
+        assert ratio <= 1.0, ratio
+        return
+    r = _fused(gpu_device, name, spec, None, plant=True)
+    got, exp = _check_structure(spec, name, r)
+    ref = ref64.reference("fm", m.v_dim, spec.ukeys, r["W"], spec.keys, spec.row_ptr, spec.fgid,
+                          spec.labels, spec.slice_rows, m.fm_math)
+    assert len(ref.slice_rows) == spec.S
+    sl, want, bound = bound_of(ref, r["W"])
+    np.testing.assert_array_equal(sl, exp.slices)
+    assert np.isfinite(got.values).all() and np.abs(got.values).max() > 0
+    ratio = trs.worst_ratio(np.abs(got.values.astype(np.float64) - want), bound)
+    trs.note_ratio("csr_entry_wide", "gpu", m, ratio)
+    assert ratio <= 1.0, ratio
+    got2, _ = _check_structure(spec, name, _fused(gpu_device, name, spec, None, plant=True))
     np.testing.assert_array_equal(got2.bits, got.bits)
 
 
