@@ -686,4 +686,26 @@ void Engine::eval_step(const BatchView& b, float* pctr) {
   be_->forward_backward(eval_fwd_args(b, pctr));
 }
 
+bool Engine::ranks() const {
+  return frozen() && (cfg_.model.kind == kLR || cfg_.model.kind == kFM) && be_->ranks();
+}
+
+void Engine::rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_nnz, int64_t R,
+                       const int32_t* req_ptr, const BatchView& cands, float* pctr) {
+  if (!ranks())
+    throw std::runtime_error("rank_step: needs a frozen LR or FM engine on a backend that ranks");
+  RankArgs ra;
+  ra.table = table_;
+  ra.cands = cands;
+  ra.ctx_keys = ctx_keys;
+  ra.ctx_ptr = ctx_ptr;
+  ra.ctx_nnz = ctx_nnz;
+  ra.R = R;
+  ra.req_ptr = req_ptr;
+  ra.pctr = pctr;
+  ra.model = cfg_.model;
+  ra.opt = cfg_.opt;
+  be_->rank(ra);
+}
+
 }  // namespace xflow

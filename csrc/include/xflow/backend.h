@@ -698,6 +698,29 @@ struct ServeArgs {
   bool fm_vals = false;
 };
 
+// Candidate ranking from a frozen LR or FM table (Backend::rank, HIP:
+// kernels_rank.hip): R requests, each one context (CSR: ctx_ptr into
+// ctx_keys) scored against the candidate rows [req_ptr[q], req_ptr[q + 1]) of
+// `cands`.  pctr[row] is the model's prediction for the row made of the
+// context's keys followed by the candidate's: the context's sums -- LR wx, FM
+// (wx, vs[0..D), vp) -- are taken once per tile of 64 candidate rows, in an
+// association that depends on the context alone, and every candidate of the
+// request continues them in occurrence order, as k_serve_lr / k_serve_fm's
+// full rows do.  Pointer values are clamped to the arrays: malformed ctx_ptr /
+// req_ptr give wrong scores, never an access outside them.
+struct RankArgs {
+  TableView table;                 // kFrozen, TableLayout::make(model, opt)
+  BatchView cands;                 // any of the three layouts; labels unused
+  const u64* ctx_keys = nullptr;   // [ctx_nnz]
+  const int32_t* ctx_ptr = nullptr;  // [R + 1]
+  int64_t ctx_nnz = 0;
+  int64_t R = 0;                   // requests
+  const int32_t* req_ptr = nullptr;  // [R + 1], req_ptr[R] == cands.rows
+  float* pctr = nullptr;           // [cands.rows]
+  ModelSpec model;                 // kLR or kFM
+  OptSpec opt;
+};
+
 struct SynthArgs {                 // synthetic Criteo-shaped batch generator
   u64* keys = nullptr;
   float* labels = nullptr;
@@ -1106,6 +1129,12 @@ class Backend {
   virtual void serve_model(const ServeArgs& a) {
     (void)a;
     throw std::runtime_error("serve_model is not supported by this backend");
+  }
+  // Candidate ranking of LR and FM from a frozen table (RankArgs; HIP only)
+  virtual bool ranks() const { return false; }
+  virtual void rank(const RankArgs& a) {
+    (void)a;
+    throw std::runtime_error("rank is not supported by this backend");
   }
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --

@@ -534,6 +534,14 @@ class Engine {
   std::pair<int64_t, int64_t> serve_unfused_latent() const {
     return {cfg_.serve_unfused_latent_lo, cfg_.serve_unfused_latent_hi};
   }
+  // Candidate ranking (RankArgs, backend.h): R contexts (CSR, device memory),
+  // request q scored against the candidate rows [req_ptr[q], req_ptr[q + 1])
+  // of cands; pctr [cands.rows].  A frozen LR or FM engine on a backend that
+  // ranks (ranks()); throws otherwise.  fm_mfma does not matter here: there is
+  // no bit contract with the forward, only with the float64 bound.
+  bool ranks() const;
+  void rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_nnz, int64_t R,
+                 const int32_t* req_ptr, const BatchView& cands, float* pctr);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that

@@ -659,6 +659,14 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def("eval_step",
            [](Engine& e, const BatchView& b, uintptr_t pctr) { e.eval_step(b, P<float>(pctr)); },
            py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("ranks", &Engine::ranks)
+      .def("rank_step",
+           [](Engine& e, uintptr_t ctx_keys, uintptr_t ctx_ptr, int64_t ctx_nnz, int64_t R,
+              uintptr_t req_ptr, const BatchView& cands, uintptr_t pctr) {
+             e.rank_step(P<const u64>(ctx_keys), P<const int32_t>(ctx_ptr), ctx_nnz, R,
+                         P<const int32_t>(req_ptr), cands, P<float>(pctr));
+           },
+           py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)
       .def_static("slice_groups", &Engine::slice_groups)
       .def_static("group_slices", &Engine::group_slices)

@@ -20,7 +20,15 @@ prefilled to --fm-table-load); the frozen_fused column is then k_serve_fm /
 k_serve_mvm.  MVM wants --opt sgd --sgd-v-init 0.9: with the default init of
 1e-3 every field product underflows and the table never changes.
 
+--rank measures candidate ranking instead of the three columns (docs/DESIGN.md
+§2): on the snapshot's engine (default windows) ``rank_step`` -- contexts of
+--rank-ctx fields, candidates of the remaining ones -- against ``eval_step`` on
+the same rows expanded to --fields keys, timed with device events in
+alternating blocks; then ``Predictor.rank_keys`` against ``predict_keys`` from
+host lists, wall clock with the upload.
+
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
+    python tools/serve_bench.py --rank [--model fm --fm-math standard] [--out profiles/rank.txt]
 """
 from __future__ import annotations
 
@@ -38,7 +46,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from xflow_amd import checkpoint  # noqa: E402
 from xflow_amd.config import EngineConfig, ModelConfig, OptimConfig  # noqa: E402
 from xflow_amd.data.synth import SynthConfig, SyntheticCriteo  # noqa: E402
-from xflow_amd.engine import Engine  # noqa: E402
+from xflow_amd.engine import Batch, Engine  # noqa: E402
 from xflow_amd.serve import Predictor  # noqa: E402
 
 
@@ -73,6 +81,64 @@ def median(v):
     return sorted(v)[len(v) // 2]
 
 
+def rank_section(a, dev, snap_dir, synth, say):
+    """rank_step against eval_step on the expanded rows, one engine."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    e, C, F = p.engine, a.rank_ctx, a.fields
+    assert e.ranks and 0 < C < F
+    say("# ms per call, median of %d alternating blocks of device-event time (batches on the "
+        "device) | the blocks; then host lists to scores, wall clock" % a.blocks)
+    say("requests candidates rank_step eval_step_expanded ratio | blocks | "
+        "rank_keys_ms predict_keys_ms")
+    for R, per in ((1, 64), (1, 256), (1, 4096), (1, 65536), (256, 16)):
+        rows = R * per
+        if rows > a.batch:
+            continue
+        gen = SyntheticCriteo(e, rows, synth)
+        b = gen.alloc_batch()
+        gen.next(out=b)
+        keys = (b.keys.view(F, rows).t() if b.field_major else b.keys.view(rows, F)).contiguous()
+        first = torch.arange(R, device=dev) * per  # a request's context: its first row's
+        ctx = keys[first, :C].contiguous()
+        # (both batches field-major, the layout the one-lane-per-row kernels favour)
+        fm = lambda k: Batch(keys=k.t().contiguous().view(-1), labels=b.labels,
+                             nnz_per_row=k.shape[1], field_major=True)
+        full = fm(torch.cat([ctx.repeat_interleave(per, 0), keys[:, C:]], 1))
+        cand = fm(keys[:, C:])
+        cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
+        rptr = (torch.arange(R + 1, device=dev) * per).to(torch.int32)
+        out = torch.empty(rows, dtype=torch.float32, device=dev)
+        calls = (lambda: e.rank_step(ctx.view(-1), cptr, rptr, cand, out),
+                 lambda: e.eval_step(full, out))
+        reps = 200 if rows <= 4096 else 50
+        times = [[], []]
+        for blk in range(a.blocks + 1):  # (block 0: warm-up)
+            for i, f in enumerate(calls):
+                t0, t1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                t0.record()
+                for _ in range(reps):
+                    f()
+                t1.record()
+                torch.cuda.synchronize(dev)
+                if blk:
+                    times[i].append(t0.elapsed_time(t1) / reps)
+        lc, lk = ctx.cpu().tolist(), keys[:, C:].cpu().tolist()
+        host = (lambda: p.rank_keys(lc, [lk[q * per:(q + 1) * per] for q in range(R)]),
+                lambda: p.predict_keys([lc[r // per] + lk[r] for r in range(rows)]))
+        wall = [[], []]
+        for blk in range(4):
+            for i, f in enumerate(host):
+                t0 = time.perf_counter()
+                f()
+                if blk:
+                    wall[i].append(1000.0 * (time.perf_counter() - t0))
+        m = [median(t) for t in times]
+        say("%d %d %.4f %.4f %.2f | %s | %.2f %.2f"
+            % (R, per, m[0], m[1], m[1] / m[0],
+               " ; ".join(" ".join("%.4f" % x for x in t) for t in times),
+               median(wall[0]), median(wall[1])))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -92,6 +158,8 @@ def main() -> int:
     ap.add_argument("--fm-math", choices=("reference", "standard"), default="reference")
     ap.add_argument("--opt", choices=("ftrl", "sgd"), default="ftrl")
     ap.add_argument("--sgd-v-init", type=float, default=1e-3)
+    ap.add_argument("--rank", action="store_true", help="the candidate ranking section only")
+    ap.add_argument("--rank-ctx", type=int, default=26, help="context fields of --fields")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -101,6 +169,13 @@ def main() -> int:
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    def done():
+        if a.out:  # (only a run that finished writes its table)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return 0
 
     lr = a.model == "lr"
     model = ModelConfig(kind=a.model, v_dim=a.v_dim, fm_math=a.fm_math)
@@ -120,6 +195,9 @@ def main() -> int:
         m = checkpoint.load_meta(snap_dir)
         del eng
         torch.cuda.empty_cache()
+        if a.rank:
+            rank_section(a, dev, snap_dir, synth, say)
+            return done()
         say("kind keys checkpoint_bytes load_seconds device_bytes")
         arms = []
         for name, path, kw in (("full", full_dir, {}),
@@ -170,11 +248,7 @@ def main() -> int:
                                         dir_bytes(fsnap), m["keys_kept"], m["keys_total"]))
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    if a.out:  # (only a run that finished writes its table)
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    return 0
+    return done()
 
 
 if __name__ == "__main__":

@@ -46,6 +46,11 @@ HIP_FLAGS = ["--offload-arch=" + ARCH, "-ffp-contract=off", "-mcode-object-versi
              "-I" + os.path.join(CSRC, "hip"), "-Wno-unused-result"] + \
             (["-DXFLOW_KTIMING=1"] if KTIMING else [])
 
+# kernels_rank.hip sums fp32 vectors component by component: keep the
+# compiler from pairing those adds and multiplies into packed fp32
+# instructions (each sum stays the scalar IEEE operation its source names)
+HIP_FILE_FLAGS = {"kernels_rank.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
 HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/engine_step.cpp",
                 "engine/engine_sharded.cpp", "engine/engine_table.cpp", "engine/engine_input.cpp",
                 "engine/engine_io.cpp", "engine/trainer.cpp"]
@@ -85,7 +90,8 @@ def _run(cmd: list[str], verbose: bool) -> None:
 def _compile_cmd(src: str) -> list[str]:
     out = _obj_path(src)
     if src.endswith(".hip"):
-        return [HIPCC, "-c", src, "-o", out] + COMMON_FLAGS + HIP_FLAGS
+        return [HIPCC, "-c", src, "-o", out] + COMMON_FLAGS + HIP_FLAGS + \
+            HIP_FILE_FLAGS.get(os.path.basename(src), [])
     if src.endswith(("rccl_comm.cpp", "peer_window.cpp")):  # host code against the HIP runtime
         return [HIPCC, "-c", src, "-o", out] + COMMON_FLAGS
     flags = list(COMMON_FLAGS)

@@ -271,6 +271,34 @@ class Engine:
         self._e.eval_step(batch.view(), pctr.data_ptr())
         return pctr
 
+    @property
+    def ranks(self) -> bool:
+        """rank_step is available: a frozen LR or FM engine on the GPU."""
+        return bool(self._e.ranks)
+
+    def rank_step(self, ctx_keys: torch.Tensor, ctx_ptr: torch.Tensor, req_ptr: torch.Tensor,
+                  cands: Batch, pctr: torch.Tensor | None = None) -> torch.Tensor:
+        """Candidate ranking in one launch (docs/DESIGN.md §2): R contexts in
+        CSR form (ctx_keys int64 u64 bit patterns, ctx_ptr int32 [R + 1]),
+        request q scored against the rows [req_ptr[q], req_ptr[q + 1]) of
+        ``cands`` (req_ptr int32 [R + 1], its last entry the row count; the
+        labels are ignored).  pctr[row] is the model's prediction for the
+        context's keys followed by the candidate's.  Raises unless ``ranks``."""
+        cands.check(self.device)
+        for name, t, dt in (("ctx_keys", ctx_keys, torch.int64), ("ctx_ptr", ctx_ptr, torch.int32),
+                            ("req_ptr", req_ptr, torch.int32)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+        if ctx_ptr.numel() != req_ptr.numel() or req_ptr.numel() < 1:
+            raise ValueError("ctx_ptr and req_ptr must both hold requests + 1 offsets")
+        if pctr is None:
+            pctr = torch.empty(cands.rows, dtype=torch.float32, device=self.device)
+        self._sync_stream()
+        self._e.rank_step(ctx_keys.data_ptr(), ctx_ptr.data_ptr(), int(ctx_keys.numel()),
+                          int(req_ptr.numel()) - 1, req_ptr.data_ptr(), cands.view(),
+                          pctr.data_ptr())
+        return pctr
+
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""
         self._sync_stream()

@@ -13,10 +13,14 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
     p = Predictor("ckpt/")                     # or a versioned root (LATEST)
     p.predict_libffm(open("test-00000", "rb").read())   -> np.float32 [rows]
     p.predict_csr(keys_u64, row_ptr)                      -> np.float32 [rows]
+    p.rank_keys([context], [[cand, ...]])   -> [np.float32 [candidates]] (one
+        context scored against many candidates: Predictor.rank_csr)
 
     python -m xflow_amd.serve --checkpoint ckpt/ --port 8080
         POST /predict {"libffm": "1 1:123:1 2:456:1\\n..."}
                    or {"keys": [[k, ...], ...]}  -> {"pctr": [...]}
+        POST /rank    {"context": [k, ...], "candidates": [[k, ...], ...]}
+                      (+ "context_fields", "candidate_fields")  -> {"pctr": [...]}
         GET  /health
 
 A serving snapshot (checkpoint.save_serving, ``--save-serving``, or the offline
@@ -271,9 +275,129 @@ class Predictor:
         return self.predict_csr(keys, rp, fg)
 
 
+    # ---------------------------------------------------------------- ranking
+    def rank_csr(self, ctx_keys: np.ndarray, ctx_ptr: np.ndarray, cand_keys: np.ndarray,
+                 cand_ptr: np.ndarray, req_ptr: np.ndarray,
+                 ctx_fgid: Optional[np.ndarray] = None,
+                 cand_fgid: Optional[np.ndarray] = None) -> list:
+        """R ranking requests: request q is the context ctx_keys[ctx_ptr[q]:
+        ctx_ptr[q + 1]] scored against the candidate rows req_ptr[q] ..
+        req_ptr[q + 1] - 1 of the CSR batch (cand_keys, cand_ptr).  Returns one
+        float32 array per request: the model's prediction for the context's
+        keys followed by the candidate's.  A frozen LR or FM snapshot on the
+        GPU scores a request's context once per 64 candidates
+        (Engine.rank_step); every other model, a model with feature crosses, a
+        full checkpoint and the CPU expand the rows on the host and score them
+        with predict_csr (which then needs the field ids where it would)."""
+        ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
+        cand_keys = np.ascontiguousarray(cand_keys).view(np.uint64)
+        ctx_ptr, cand_ptr, req_ptr = (np.asarray(p, dtype=np.int64)
+                                      for p in (ctx_ptr, cand_ptr, req_ptr))
+        R, rows = len(req_ptr) - 1, len(cand_ptr) - 1
+        for name, p, n, end in (("req_ptr", req_ptr, R, rows), ("ctx_ptr", ctx_ptr, R, len(ctx_keys)),
+                                ("cand_ptr", cand_ptr, rows, len(cand_keys))):
+            if p.ndim != 1 or n < 0 or len(p) != n + 1 or p[0] != 0 or p[-1] != end or \
+                    (np.diff(p) < 0).any():
+                raise ValueError(f"{name} must hold {max(n, 0) + 1} non-decreasing offsets "
+                                 f"from 0 to {end}")
+        if (ctx_fgid is None) != (cand_fgid is None):
+            raise ValueError("give the field ids of both the contexts and the candidates, or neither")
+        if ctx_fgid is not None and (len(ctx_fgid) != len(ctx_keys) or len(cand_fgid) != len(cand_keys)):
+            raise ValueError("field ids must hold one id per key")
+        if self.engine.ranks and not self.crosses:
+            out = self._rank_device(ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr)
+        else:
+            # row = context then candidate, as the kernel sums them
+            req = np.repeat(np.arange(R), np.diff(req_ptr))
+            cat = lambda c, x: np.concatenate(
+                [np.concatenate([c[ctx_ptr[q]:ctx_ptr[q + 1]], x[cand_ptr[r]:cand_ptr[r + 1]]])
+                 for r, q in enumerate(req)]) if rows else x[:0]
+            rp = np.concatenate([[0], np.cumsum(np.diff(ctx_ptr)[req] + np.diff(cand_ptr))])
+            out = self.predict_csr(cat(ctx_keys, cand_keys), rp,
+                                   None if ctx_fgid is None else
+                                   cat(np.asarray(ctx_fgid, np.int32), np.asarray(cand_fgid, np.int32)))
+        return [out[req_ptr[q]:req_ptr[q + 1]] for q in range(R)]
+
+    def _rank_device(self, ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr) -> np.ndarray:
+        """Engine.rank_step over chunks of at most max_rows candidate rows and
+        the engine's max_nnz keys.  A chunk takes the contexts of the requests
+        it meets; a context's sums do not depend on which rows share its
+        launch, so the chunking cannot change a score."""
+        rows, dev = len(cand_ptr) - 1, self.device
+        out = np.empty(rows, np.float32)
+        cap_nnz = self.engine.cfg.max_nnz
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt, copy=False)).to(dev)
+        r = 0
+        with self._lock:
+            while r < rows:
+                r1 = min(rows, r + self.max_rows)
+                while r1 > r + 1 and cand_ptr[r1] - cand_ptr[r] > cap_nnz:
+                    r1 = r + (r1 - r) // 2
+                k0, k1 = int(cand_ptr[r]), int(cand_ptr[r1])
+                if k1 - k0 > cap_nnz:
+                    raise ValueError(f"candidate {r} has more than {cap_nnz} features")
+                # requests q0 .. q1 - 1 have rows in [r, r1)
+                q0 = int(np.searchsorted(req_ptr, r, side="right")) - 1
+                q1 = int(np.searchsorted(req_ptr, r1, side="left"))
+                c0, c1 = int(ctx_ptr[q0]), int(ctx_ptr[q1])
+                b = Batch(keys=up(cand_keys[k0:k1].view(np.int64), np.int64),
+                          labels=torch.zeros(r1 - r, dtype=torch.float32, device=dev),
+                          row_ptr=up(cand_ptr[r:r1 + 1] - k0, np.int32))
+                p = self.engine.rank_step(up(ctx_keys[c0:c1].view(np.int64), np.int64),
+                                          up(ctx_ptr[q0:q1 + 1] - c0, np.int32),
+                                          up(np.clip(req_ptr[q0:q1 + 1], r, r1) - r, np.int32), b)
+                out[r:r1] = p.cpu().numpy()
+                r = r1
+        return out
+
+    def rank_keys(self, contexts: Sequence[Sequence[int]],
+                  candidates: Sequence[Sequence[Sequence[int]]],
+                  context_fields: Optional[Sequence[Sequence[int]]] = None,
+                  candidate_fields: Optional[Sequence[Sequence[Sequence[int]]]] = None) -> list:
+        """rank_csr from lists: contexts[q] the (already hashed) u64 keys of
+        request q's context, candidates[q] its candidates' key lists; the
+        fields mirror their shapes (required where predict_keys requires
+        them).  One float32 array per request."""
+        if len(contexts) != len(candidates):
+            raise ValueError("give one list of candidates per context")
+        flat = [c for cs in candidates for c in cs]
+        ptr = lambda ls: np.concatenate([[0], np.cumsum([len(x) for x in ls])]).astype(np.int64)
+        arr = lambda ls, dt: np.array([k for x in ls for k in x], dtype=dt)
+        fg = [None, None]
+        if (context_fields is None) != (candidate_fields is None):
+            raise ValueError("give 'context_fields' and 'candidate_fields' together")
+        if context_fields is not None:
+            ff = [f for fs in candidate_fields for f in fs]
+            if [len(f) for f in context_fields] != [len(c) for c in contexts] or \
+                    [len(fs) for fs in candidate_fields] != [len(cs) for cs in candidates] or \
+                    [len(f) for f in ff] != [len(c) for c in flat]:
+                raise ValueError("the fields must give one field id per key")
+            fg = [arr(context_fields, np.int32), arr(ff, np.int32)]
+        return self.rank_csr(arr(contexts, np.uint64), ptr(contexts), arr(flat, np.uint64), ptr(flat),
+                             ptr(candidates), fg[0], fg[1])
+
+    def rank_libffm(self, context_line: bytes, candidate_lines: bytes) -> np.ndarray:
+        """One request from libffm text (``label fgid:fid:val ...``, the label
+        ignored): the context's features on one line, a candidate's on each
+        line of ``candidate_lines``.  pctr of every candidate."""
+        def parse(text):
+            if isinstance(text, str):
+                text = text.encode()
+            if text and not text.endswith(b"\n"):
+                text += b"\n"
+            blk = _native.load().parse_libffm(text)
+            return (np.asarray(blk["keys"]).view(np.uint64), np.asarray(blk["row_ptr"], np.int64),
+                    np.asarray(blk["fgid"]))
+        ck, cp, cf = parse(context_line)
+        if len(cp) != 2:
+            raise ValueError("the context is one libffm line")
+        k, p, f = parse(candidate_lines)
+        return self.rank_csr(ck, cp, k, p, np.array([0, len(p) - 1]), cf, f)[0]
+
+
 # -------------------------------------------------------------------- service
 def make_app(pred: Predictor):
-    """FastAPI app: POST /predict, POST /refresh, GET /health."""
+    """FastAPI app: POST /predict, POST /rank, POST /refresh, GET /health."""
     from fastapi import FastAPI, HTTPException
     from pydantic import create_model
 
@@ -308,6 +432,23 @@ def make_app(pred: Predictor):
 
     predict.__annotations__ = {"req": Req}
     app.post("/predict")(predict)
+
+    RankReq = create_model("RankRequest", context=(list[int], ...),
+                           candidates=(list[list[int]], ...),
+                           context_fields=(Optional[list[int]], None),
+                           candidate_fields=(Optional[list[list[int]]], None))
+
+    def rank(req):
+        try:
+            p = pred.rank_keys([req.context], [req.candidates],
+                               None if req.context_fields is None else [req.context_fields],
+                               None if req.candidate_fields is None else [req.candidate_fields])[0]
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        return {"pctr": [float(x) for x in p]}
+
+    rank.__annotations__ = {"req": RankReq}
+    app.post("/rank")(rank)
     return app
 
 
