@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <vector>
 #include <sys/mman.h>
@@ -903,6 +904,28 @@ class CpuBackend final : public Backend {
       for (int p = 0; p < t.L.P; ++p) n += slot_weight(sp, key, p, t.L, o) != 0.0f;
     }
     return n;
+  }
+  // per request, a partial sort on sort key << 32 | ~index, descending: the
+  // total order of TopkArgs in one integer
+  void topk(const TopkArgs& a) override {
+    if (!topk_check(a)) return;
+    std::fill(a.idx, a.idx + a.R * a.k, -1);
+    std::fill(a.score, a.score + a.R * a.k, 0.0f);
+    std::vector<u64> w;
+    for (int64_t q = 0; q < a.R && a.rows > 0; ++q) {
+      const int64_t lo = std::clamp<int64_t>(a.req_ptr[q], 0, a.rows);
+      const int64_t hi = std::clamp<int64_t>(a.req_ptr[q + 1], lo, a.rows);
+      w.resize((size_t)(hi - lo));
+      for (int64_t r = lo; r < hi; ++r)
+        w[(size_t)(r - lo)] = (u64)eval_key_bits(a.pctr[r]) << 32 | (u32)~(u32)(r - lo);
+      const size_t n = std::min<size_t>((size_t)a.k, w.size());
+      std::partial_sort(w.begin(), w.begin() + n, w.end(), std::greater<u64>());
+      for (size_t j = 0; j < n; ++j) {
+        const u32 i = ~(u32)w[j];
+        a.idx[q * a.k + (int64_t)j] = (int32_t)i;
+        a.score[q * a.k + (int64_t)j] = a.pctr[lo + i];
+      }
+    }
   }
 
  private:

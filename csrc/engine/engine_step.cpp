@@ -708,4 +708,21 @@ void Engine::rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_
   be_->rank(ra);
 }
 
+void Engine::topk_step(const float* pctr, const int32_t* req_ptr, int64_t R, int64_t rows, int k,
+                       int32_t* idx, float* score) {
+  TopkArgs ta;
+  ta.pctr = pctr;
+  ta.req_ptr = req_ptr;
+  ta.R = R;
+  ta.rows = rows;
+  ta.k = k;
+  ta.idx = idx;
+  ta.score = score;
+  if (is_gpu() && rows > kTopkTile) {
+    topk_partial_.reserve(*be_, (size_t)rows, (size_t)std::max<int64_t>(rows, cfg_.max_rows));
+    ta.partial = topk_partial_;
+  }
+  be_->topk(ta);
+}
+
 }  // namespace xflow

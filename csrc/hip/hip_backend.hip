@@ -476,6 +476,7 @@ class HipBackend final : public Backend {
   void serve_model(const ServeArgs& a) override { hip::launch_serve_model(a, stream_); }
   bool ranks() const override { return true; }
   void rank(const RankArgs& a) override { hip::launch_rank(a, stream_); }
+  void topk(const TopkArgs& a) override { hip::launch_topk(a, stream_); }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

@@ -92,6 +92,9 @@ void launch_serve_model(const ServeArgs& a, hipStream_t st);  // FM, MVM
 // kernels_rank.hip
 void launch_rank(const RankArgs& a, hipStream_t st);  // LR, FM
 
+// kernels_topk.hip
+void launch_topk(const TopkArgs& a, hipStream_t st);
+
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);
 void launch_field_major(const void* src, void* dst, int64_t rows, int F, int elem_bytes, bool widen,

@@ -721,6 +721,39 @@ struct RankArgs {
   OptSpec opt;
 };
 
+// Segmented top-k of a score array (Backend::topk, HIP: kernels_topk.hip):
+// request q owns the scores pctr[req_ptr[q] .. req_ptr[q + 1]) and gets its
+// best min(k, n_q) of them in idx[q][..] (the score's index inside the
+// request, row - req_ptr[q]) and score[q][..] (the bits of pctr[row] itself);
+// the rest of both rows is padding, -1 and +0.0f.  The order is total:
+// descending sort key (eval_key_bits below, the order of the predictions), on
+// equal keys ascending index -- so NaN, zeros and negative scores tie and rank
+// last by index, and no tiling or chunking can change the result.  req_ptr is
+// non-decreasing from 0 to rows; values that are not give wrong entries, never
+// an access outside the arrays.
+constexpr int kTopkMaxK = 1024;
+constexpr int64_t kTopkTile = 4096;  // rows one sort covers (HIP); a call of more needs `partial`
+struct TopkArgs {
+  const float* pctr = nullptr;       // [rows]
+  const int32_t* req_ptr = nullptr;  // [R + 1]
+  int64_t R = 0;
+  int64_t rows = 0;
+  int k = 0;                         // 1 .. kTopkMaxK
+  int32_t* idx = nullptr;            // [R][k]
+  float* score = nullptr;            // [R][k]
+  u64* partial = nullptr;            // [rows] scratch, HIP with rows > kTopkTile only
+};
+// what both backends refuse; false: nothing to write (no request)
+inline bool topk_check(const TopkArgs& a) {
+  if (a.k < 1 || a.k > kTopkMaxK) throw std::runtime_error("topk: k must be 1 .. 1024");
+  if (a.rows < 0 || a.rows > 0x7fffffffll || a.R < 0 || a.R > 0x7fffffffll)
+    throw std::runtime_error("topk: rows and requests are int32 offsets");
+  if (a.R == 0) return false;
+  if (!a.idx || !a.score || (a.rows > 0 && (!a.pctr || !a.req_ptr)))
+    throw std::runtime_error("topk: null array");
+  return true;
+}
+
 struct SynthArgs {                 // synthetic Criteo-shaped batch generator
   u64* keys = nullptr;
   float* labels = nullptr;
@@ -1136,6 +1169,8 @@ class Backend {
     (void)a;
     throw std::runtime_error("rank is not supported by this backend");
   }
+  // the best k scores of every request, in order (see TopkArgs)
+  virtual void topk(const TopkArgs& a) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

@@ -542,6 +542,11 @@ class Engine {
   bool ranks() const;
   void rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_nnz, int64_t R,
                  const int32_t* req_ptr, const BatchView& cands, float* pctr);
+  // The best k of every request's scores, in order (TopkArgs, backend.h):
+  // pctr [rows] and req_ptr [R + 1] as rank_step takes and leaves them, idx /
+  // score [R][k].  Any engine, either backend; stream-ordered, no sync.
+  void topk_step(const float* pctr, const int32_t* req_ptr, int64_t R, int64_t rows, int k,
+                 int32_t* idx, float* score);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that
@@ -872,6 +877,7 @@ class Engine {
   int64_t known_adds_ = 0;          // cumulative insert bound queued before it
   int64_t queued_adds_ = 0;         // cumulative insert bound queued so far
   int64_t growths_ = 0, splits_ = 0, monitor_waits_ = 0;
+  DeviceBuffer<u64> topk_partial_;  // [max_rows or more] topk_step over several tiles, on first use
   DeviceBuffer<unsigned long long> pruned_dev_;  // [1] keys dropped by prune(), cumulative
   int64_t pruned_keys_ = 0;
   double grow_s_ = 0.0;

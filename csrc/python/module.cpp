@@ -667,6 +667,13 @@ PYBIND11_MODULE(_xflow_native, m) {
                          P<const int32_t>(req_ptr), cands, P<float>(pctr));
            },
            py::call_guard<py::gil_scoped_release>())
+      .def("topk_step",
+           [](Engine& e, uintptr_t pctr, uintptr_t req_ptr, int64_t R, int64_t rows, int k,
+              uintptr_t idx, uintptr_t score) {
+             e.topk_step(P<const float>(pctr), P<const int32_t>(req_ptr), R, rows, k,
+                         P<int32_t>(idx), P<float>(score));
+           },
+           py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)
       .def_static("slice_groups", &Engine::slice_groups)
       .def_static("group_slices", &Engine::group_slices)

@@ -25,10 +25,15 @@ k_serve_mvm.  MVM wants --opt sgd --sgd-v-init 0.9: with the default init of
 --rank-ctx fields, candidates of the remaining ones -- against ``eval_step`` on
 the same rows expanded to --fields keys, timed with device events in
 alternating blocks; then ``Predictor.rank_keys`` against ``predict_keys`` from
-host lists, wall clock with the upload.
+host lists, wall clock with the upload.  --rank --top-k K[,K..] measures the
+selection of the best K instead: ``rank_topk`` on the device against
+``rank_step``, the download of every score and a vectorised selection on the
+host in the same order (what a caller does without ``topk_step``), from device
+batches and from host lists, in alternating blocks.
 
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
     python tools/serve_bench.py --rank [--model fm --fm-math standard] [--out profiles/rank.txt]
+    python tools/serve_bench.py --rank --top-k 10,100 [--out profiles/rank_topk.txt]
 """
 from __future__ import annotations
 
@@ -39,6 +44,7 @@ import sys
 import tempfile
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -139,6 +145,90 @@ def rank_section(a, dev, snap_dir, synth, say):
                median(wall[0]), median(wall[1])))
 
 
+def host_select(p, R, per, k):
+    """The best k of R requests of `per` scores each on the host, in
+    topk_step's order: what a caller of rank_step does without it (one
+    vectorised partition and sort of sort key << 32 | ~index)."""
+    skey = np.where(p > 0, p, 0).astype(np.float32).view(np.uint32).astype(np.uint64)
+    key = (skey.reshape(R, per) << np.uint64(32)) | (~np.arange(per, dtype=np.uint32)).astype(np.uint64)
+    n = min(k, per)
+    if n < per:
+        key = np.partition(key, per - n, axis=1)[:, per - n:]
+    idx = (~np.sort(key, axis=1)[:, ::-1].astype(np.uint32)).astype(np.int32)  # (the low words)
+    return idx, np.take_along_axis(p.reshape(R, per), idx, 1)
+
+
+def topk_section(a, dev, snap_dir, synth, say):
+    """rank_topk (selection on the device) against rank_step, download and
+    host_select -- the same answer, as a caller gets it without topk_step."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    e, C, F = p.engine, a.rank_ctx, a.fields
+    say("# top-k: ms per call, medians of %d alternating blocks.  device: event time of rank_step "
+        "alone and of rank_topk (rank_step + topk_step), batches on the device.  to_host: wall "
+        "clock from the same device batches to numpy results, rank_topk + download of the pairs "
+        "against rank_step + download of the scores + host_select.  lists: wall clock from host "
+        "lists, Predictor.rank_keys(top_k=k) against rank_keys() + host_select" % a.blocks)
+    say("requests candidates k | device: rank_step rank_topk | to_host: topk download_select ratio "
+        "| lists: rank_keys_topk rank_keys_select")
+    for R, per in ((1, 64), (1, 256), (1, 4096), (1, 65536), (256, 16)):
+        rows = R * per
+        if rows > a.batch:
+            continue
+        gen = SyntheticCriteo(e, rows, synth)
+        b = gen.alloc_batch()
+        gen.next(out=b)
+        keys = (b.keys.view(F, rows).t() if b.field_major else b.keys.view(rows, F)).contiguous()
+        ctx = keys[torch.arange(R, device=dev) * per, :C].contiguous()
+        cand = Batch(keys=keys[:, C:].t().contiguous().view(-1), labels=b.labels,
+                     nnz_per_row=F - C, field_major=True)
+        cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
+        rptr = (torch.arange(R + 1, device=dev) * per).to(torch.int32)
+        lc, lk = ctx.cpu().tolist(), keys[:, C:].cpu().tolist()
+        lcand = [lk[q * per:(q + 1) * per] for q in range(R)]
+        reps = 200 if rows <= 4096 else 50
+        for k in a.top_k:
+            def to_host_topk():
+                i, s = e.rank_topk(ctx.view(-1), cptr, rptr, cand, k)
+                return i.cpu().numpy(), s.cpu().numpy()
+
+            def to_host_select():
+                return host_select(e.rank_step(ctx.view(-1), cptr, rptr, cand).cpu().numpy(), R, per, k)
+
+            def lists_select():
+                return host_select(np.concatenate(p.rank_keys(lc, lcand)), R, per, k)
+
+            got, want = to_host_topk(), to_host_select()  # (the two ways agree, bit for bit)
+            n = min(k, per)
+            assert np.array_equal(got[0][:, :n], want[0]) and \
+                np.array_equal(got[1][:, :n].view(np.uint32), want[1].view(np.uint32))
+            dev_calls = (lambda: e.rank_step(ctx.view(-1), cptr, rptr, cand),
+                         lambda: e.rank_topk(ctx.view(-1), cptr, rptr, cand, k))
+            wall_calls = (to_host_topk, to_host_select, lambda: p.rank_keys(lc, lcand, top_k=k),
+                          lists_select)
+            times, wall = [[], []], [[], [], [], []]
+            for blk in range(a.blocks + 1):  # (block 0: warm-up)
+                for i, f in enumerate(dev_calls):
+                    t0, t1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                    t0.record()
+                    for _ in range(reps):
+                        f()
+                    t1.record()
+                    torch.cuda.synchronize(dev)
+                    if blk:
+                        times[i].append(t0.elapsed_time(t1) / reps)
+                for i, f in enumerate(wall_calls):
+                    n_rep = max(1, reps // 10) if i < 2 else 1
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    for _ in range(n_rep):
+                        f()
+                    if blk:
+                        wall[i].append(1000.0 * (time.perf_counter() - t0) / n_rep)
+            m, w = [median(t) for t in times], [median(t) for t in wall]
+            say("%d %d %d | %.4f %.4f | %.4f %.4f %.2f | %.2f %.2f"
+                % (R, per, k, m[0], m[1], w[0], w[1], w[1] / w[0], w[2], w[3]))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -160,6 +250,8 @@ def main() -> int:
     ap.add_argument("--sgd-v-init", type=float, default=1e-3)
     ap.add_argument("--rank", action="store_true", help="the candidate ranking section only")
     ap.add_argument("--rank-ctx", type=int, default=26, help="context fields of --fields")
+    ap.add_argument("--top-k", type=lambda s: [int(x) for x in s.split(",")], default=[],
+                    metavar="K[,K..]", help="with --rank: the top-k section instead, at these k")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -196,7 +288,7 @@ def main() -> int:
         del eng
         torch.cuda.empty_cache()
         if a.rank:
-            rank_section(a, dev, snap_dir, synth, say)
+            (topk_section if a.top_k else rank_section)(a, dev, snap_dir, synth, say)
             return done()
         say("kind keys checkpoint_bytes load_seconds device_bytes")
         arms = []

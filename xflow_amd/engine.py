@@ -299,6 +299,37 @@ class Engine:
                           pctr.data_ptr())
         return pctr
 
+    def topk_step(self, pctr: torch.Tensor, req_ptr: torch.Tensor,
+                  k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """The best ``k`` (1 .. 1024) scores of every request, selected on the
+        engine's device (docs/DESIGN.md §2): request q owns pctr[req_ptr[q]:
+        req_ptr[q + 1]] (float32; req_ptr int32 [R + 1] from 0 to
+        pctr.numel()).  Returns (idx int32 [R, k], score float32 [R, k]): the
+        scores' indices inside their request, best first, and the scores' own
+        bits; a request of fewer than k scores is padded with -1 / 0.0.  Order:
+        descending, with NaN, zeros and negative scores as equal and last; equal
+        scores by ascending index.  Any engine, either backend."""
+        for name, t, dt in (("pctr", pctr, torch.float32), ("req_ptr", req_ptr, torch.int32)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-d {dt} tensor on {self.device}")
+        if not 1 <= int(k) <= 1024:
+            raise ValueError("k must be 1 .. 1024")
+        if req_ptr.numel() < 1:
+            raise ValueError("req_ptr must hold requests + 1 offsets")
+        R = int(req_ptr.numel()) - 1
+        idx = torch.empty((R, int(k)), dtype=torch.int32, device=self.device)
+        score = torch.empty((R, int(k)), dtype=torch.float32, device=self.device)
+        self._sync_stream()
+        self._e.topk_step(pctr.data_ptr(), req_ptr.data_ptr(), R, int(pctr.numel()), int(k),
+                          idx.data_ptr(), score.data_ptr())
+        return idx, score
+
+    def rank_topk(self, ctx_keys: torch.Tensor, ctx_ptr: torch.Tensor, req_ptr: torch.Tensor,
+                  cands: Batch, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """rank_step, then topk_step on its scores, in the same stream: the best
+        k candidates of every request without their scores leaving the device."""
+        return self.topk_step(self.rank_step(ctx_keys, ctx_ptr, req_ptr, cands), req_ptr, k)
+
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""
         self._sync_stream()

@@ -21,6 +21,8 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
                    or {"keys": [[k, ...], ...]}  -> {"pctr": [...]}
         POST /rank    {"context": [k, ...], "candidates": [[k, ...], ...]}
                       (+ "context_fields", "candidate_fields")  -> {"pctr": [...]}
+                      with "top_k": K, the best K selected on the device
+                                                -> {"index": [...], "pctr": [...]}
         GET  /health
 
 A serving snapshot (checkpoint.save_serving, ``--save-serving``, or the offline
@@ -279,7 +281,7 @@ class Predictor:
     def rank_csr(self, ctx_keys: np.ndarray, ctx_ptr: np.ndarray, cand_keys: np.ndarray,
                  cand_ptr: np.ndarray, req_ptr: np.ndarray,
                  ctx_fgid: Optional[np.ndarray] = None,
-                 cand_fgid: Optional[np.ndarray] = None) -> list:
+                 cand_fgid: Optional[np.ndarray] = None, top_k: Optional[int] = None) -> list:
         """R ranking requests: request q is the context ctx_keys[ctx_ptr[q]:
         ctx_ptr[q + 1]] scored against the candidate rows req_ptr[q] ..
         req_ptr[q + 1] - 1 of the CSR batch (cand_keys, cand_ptr).  Returns one
@@ -288,7 +290,16 @@ class Predictor:
         GPU scores a request's context once per 64 candidates
         (Engine.rank_step); every other model, a model with feature crosses, a
         full checkpoint and the CPU expand the rows on the host and score them
-        with predict_csr (which then needs the field ids where it would)."""
+        with predict_csr (which then needs the field ids where it would).
+
+        With ``top_k`` (1 .. 1024) the selection happens on the device too
+        (Engine.topk_step) and request q comes back as (index int32[n], pctr
+        float32[n]), n = min(top_k, its candidates): the best candidates'
+        positions in the request, best first, and their scores.  The order is
+        total -- descending pctr with NaN and values <= 0 equal and last, equal
+        scores by ascending position -- so chunking cannot change it."""
+        if top_k is not None and not (isinstance(top_k, (int, np.integer)) and 1 <= top_k <= 1024):
+            raise ValueError("top_k must be an integer from 1 to 1024")
         ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
         cand_keys = np.ascontiguousarray(cand_keys).view(np.uint64)
         ctx_ptr, cand_ptr, req_ptr = (np.asarray(p, dtype=np.int64)
@@ -305,7 +316,9 @@ class Predictor:
         if ctx_fgid is not None and (len(ctx_fgid) != len(ctx_keys) or len(cand_fgid) != len(cand_keys)):
             raise ValueError("field ids must hold one id per key")
         if self.engine.ranks and not self.crosses:
-            out = self._rank_device(ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr)
+            out = self._rank_device(ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k)
+            if top_k is not None:
+                return out
         else:
             # row = context then candidate, as the kernel sums them
             req = np.repeat(np.arange(R), np.diff(req_ptr))
@@ -316,15 +329,51 @@ class Predictor:
             out = self.predict_csr(cat(ctx_keys, cand_keys), rp,
                                    None if ctx_fgid is None else
                                    cat(np.asarray(ctx_fgid, np.int32), np.asarray(cand_fgid, np.int32)))
+            if top_k is not None:
+                parts = [[] for _ in range(R)]
+                with self._lock:
+                    self._topk_parts(torch.from_numpy(out).to(self.device), req_ptr, int(top_k),
+                                     np.zeros(R, np.int64), parts)
+                return self._topk_merge(parts, int(top_k))
         return [out[req_ptr[q]:req_ptr[q + 1]] for q in range(R)]
 
-    def _rank_device(self, ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr) -> np.ndarray:
+    def _topk_parts(self, p, rp, k, first, parts) -> None:
+        """Engine.topk_step on the device scores ``p`` of the requests with
+        offsets ``rp`` into them; request j's pairs are appended to parts[j],
+        its indices moved by first[j] (the rows of it that came before p)."""
+        idx, sc = self.engine.topk_step(
+            p, torch.from_numpy(np.ascontiguousarray(rp, np.int32)).to(self.device), k)
+        idx, sc = idx.cpu().numpy(), sc.cpu().numpy()
+        n = np.minimum(np.diff(rp), k).tolist()
+        idx += np.asarray(first, np.int32)[:, None]  # (the padding is cut off below)
+        for j in np.flatnonzero(n).tolist():
+            parts[j].append((idx[j, :n[j]], sc[j, :n[j]]))
+
+    @staticmethod
+    def _topk_merge(parts, k) -> list:
+        """One (index, pctr) pair of arrays per request from its chunks' best
+        k: a request cut by the chunking is selected again from those pairs,
+        in topk_step's order."""
+        out = []
+        none = (np.zeros(0, np.int32), np.zeros(0, np.float32))
+        for ps in parts:
+            if len(ps) > 1:
+                i, s = (np.concatenate(x) for x in zip(*ps))
+                key = np.where(s > 0, s, 0).astype(np.float32).view(np.uint32).astype(np.int64)
+                o = np.lexsort((i, -key))[:k]
+                ps = [(i[o], s[o])]
+            out.append(ps[0] if ps else none)
+        return out
+
+    def _rank_device(self, ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k=None):
         """Engine.rank_step over chunks of at most max_rows candidate rows and
         the engine's max_nnz keys.  A chunk takes the contexts of the requests
         it meets; a context's sums do not depend on which rows share its
-        launch, so the chunking cannot change a score."""
+        launch, so the chunking cannot change a score.  With ``top_k`` only
+        each chunk's best pairs are downloaded (rank_csr's second form)."""
         rows, dev = len(cand_ptr) - 1, self.device
         out = np.empty(rows, np.float32)
+        parts = [[] for _ in range(len(req_ptr) - 1)]
         cap_nnz = self.engine.cfg.max_nnz
         up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt, copy=False)).to(dev)
         r = 0
@@ -343,21 +392,27 @@ class Predictor:
                 b = Batch(keys=up(cand_keys[k0:k1].view(np.int64), np.int64),
                           labels=torch.zeros(r1 - r, dtype=torch.float32, device=dev),
                           row_ptr=up(cand_ptr[r:r1 + 1] - k0, np.int32))
+                rp = np.clip(req_ptr[q0:q1 + 1], r, r1) - r
                 p = self.engine.rank_step(up(ctx_keys[c0:c1].view(np.int64), np.int64),
                                           up(ctx_ptr[q0:q1 + 1] - c0, np.int32),
-                                          up(np.clip(req_ptr[q0:q1 + 1], r, r1) - r, np.int32), b)
-                out[r:r1] = p.cpu().numpy()
+                                          up(rp, np.int32), b)
+                if top_k is None:
+                    out[r:r1] = p.cpu().numpy()
+                else:
+                    self._topk_parts(p, rp, int(top_k), rp[:-1] + r - req_ptr[q0:q1], parts[q0:q1])
                 r = r1
-        return out
+        return out if top_k is None else self._topk_merge(parts, int(top_k))
 
     def rank_keys(self, contexts: Sequence[Sequence[int]],
                   candidates: Sequence[Sequence[Sequence[int]]],
                   context_fields: Optional[Sequence[Sequence[int]]] = None,
-                  candidate_fields: Optional[Sequence[Sequence[Sequence[int]]]] = None) -> list:
+                  candidate_fields: Optional[Sequence[Sequence[Sequence[int]]]] = None,
+                  top_k: Optional[int] = None) -> list:
         """rank_csr from lists: contexts[q] the (already hashed) u64 keys of
         request q's context, candidates[q] its candidates' key lists; the
         fields mirror their shapes (required where predict_keys requires
-        them).  One float32 array per request."""
+        them).  One float32 array per request, or with ``top_k`` one (index,
+        pctr) pair of its best candidates (rank_csr)."""
         if len(contexts) != len(candidates):
             raise ValueError("give one list of candidates per context")
         flat = [c for cs in candidates for c in cs]
@@ -374,12 +429,14 @@ class Predictor:
                 raise ValueError("the fields must give one field id per key")
             fg = [arr(context_fields, np.int32), arr(ff, np.int32)]
         return self.rank_csr(arr(contexts, np.uint64), ptr(contexts), arr(flat, np.uint64), ptr(flat),
-                             ptr(candidates), fg[0], fg[1])
+                             ptr(candidates), fg[0], fg[1], top_k)
 
-    def rank_libffm(self, context_line: bytes, candidate_lines: bytes) -> np.ndarray:
+    def rank_libffm(self, context_line: bytes, candidate_lines: bytes,
+                    top_k: Optional[int] = None):
         """One request from libffm text (``label fgid:fid:val ...``, the label
         ignored): the context's features on one line, a candidate's on each
-        line of ``candidate_lines``.  pctr of every candidate."""
+        line of ``candidate_lines``.  pctr of every candidate, or with
+        ``top_k`` the (index, pctr) of the best (rank_csr)."""
         def parse(text):
             if isinstance(text, str):
                 text = text.encode()
@@ -392,7 +449,7 @@ class Predictor:
         if len(cp) != 2:
             raise ValueError("the context is one libffm line")
         k, p, f = parse(candidate_lines)
-        return self.rank_csr(ck, cp, k, p, np.array([0, len(p) - 1]), cf, f)[0]
+        return self.rank_csr(ck, cp, k, p, np.array([0, len(p) - 1]), cf, f, top_k)[0]
 
 
 # -------------------------------------------------------------------- service
@@ -436,15 +493,19 @@ def make_app(pred: Predictor):
     RankReq = create_model("RankRequest", context=(list[int], ...),
                            candidates=(list[list[int]], ...),
                            context_fields=(Optional[list[int]], None),
-                           candidate_fields=(Optional[list[list[int]]], None))
+                           candidate_fields=(Optional[list[list[int]]], None),
+                           top_k=(Optional[int], None))
 
     def rank(req):
         try:
             p = pred.rank_keys([req.context], [req.candidates],
                                None if req.context_fields is None else [req.context_fields],
-                               None if req.candidate_fields is None else [req.candidate_fields])[0]
+                               None if req.candidate_fields is None else [req.candidate_fields],
+                               req.top_k)[0]
         except ValueError as e:
             raise HTTPException(400, str(e))
+        if req.top_k is not None:
+            return {"index": [int(i) for i in p[0]], "pctr": [float(x) for x in p[1]]}
         return {"pctr": [float(x) for x in p]}
 
     rank.__annotations__ = {"req": RankReq}
