@@ -691,9 +691,12 @@ bool Engine::ranks() const {
 }
 
 void Engine::rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_nnz, int64_t R,
-                       const int32_t* req_ptr, const BatchView& cands, float* pctr) {
+                       const int32_t* req_ptr, const BatchView& cands, float* pctr,
+                       const int32_t* ctx_fgid, const CrossSpec& spec) {
   if (!ranks())
     throw std::runtime_error("rank_step: needs a frozen LR or FM engine on a backend that ranks");
+  if (spec.n != 0 && !cfg_.rank_cross)
+    throw std::runtime_error("rank_step: crosses are switched off (EngineConfig::rank_cross)");
   RankArgs ra;
   ra.table = table_;
   ra.cands = cands;
@@ -705,6 +708,8 @@ void Engine::rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_
   ra.pctr = pctr;
   ra.model = cfg_.model;
   ra.opt = cfg_.opt;
+  ra.ctx_fgid = ctx_fgid;
+  ra.spec = spec;
   be_->rank(ra);
 }
 

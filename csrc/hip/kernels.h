@@ -91,6 +91,8 @@ void launch_serve_model(const ServeArgs& a, hipStream_t st);  // FM, MVM
 
 // kernels_rank.hip
 void launch_rank(const RankArgs& a, hipStream_t st);  // LR, FM
+// kernels_rank_cross.hip (launch_rank's kernels for a.spec.n > 0)
+void launch_rank_cross(const RankArgs& a, hipStream_t st);
 
 // kernels_topk.hip
 void launch_topk(const TopkArgs& a, hipStream_t st);

@@ -698,29 +698,6 @@ struct ServeArgs {
   bool fm_vals = false;
 };
 
-// Candidate ranking from a frozen LR or FM table (Backend::rank, HIP:
-// kernels_rank.hip): R requests, each one context (CSR: ctx_ptr into
-// ctx_keys) scored against the candidate rows [req_ptr[q], req_ptr[q + 1]) of
-// `cands`.  pctr[row] is the model's prediction for the row made of the
-// context's keys followed by the candidate's: the context's sums -- LR wx, FM
-// (wx, vs[0..D), vp) -- are taken once per tile of 64 candidate rows, in an
-// association that depends on the context alone, and every candidate of the
-// request continues them in occurrence order, as k_serve_lr / k_serve_fm's
-// full rows do.  Pointer values are clamped to the arrays: malformed ctx_ptr /
-// req_ptr give wrong scores, never an access outside them.
-struct RankArgs {
-  TableView table;                 // kFrozen, TableLayout::make(model, opt)
-  BatchView cands;                 // any of the three layouts; labels unused
-  const u64* ctx_keys = nullptr;   // [ctx_nnz]
-  const int32_t* ctx_ptr = nullptr;  // [R + 1]
-  int64_t ctx_nnz = 0;
-  int64_t R = 0;                   // requests
-  const int32_t* req_ptr = nullptr;  // [R + 1], req_ptr[R] == cands.rows
-  float* pctr = nullptr;           // [cands.rows]
-  ModelSpec model;                 // kLR or kFM
-  OptSpec opt;
-};
-
 // Segmented top-k of a score array (Backend::topk, HIP: kernels_topk.hip):
 // request q owns the scores pctr[req_ptr[q] .. req_ptr[q + 1]) and gets its
 // best min(k, n_q) of them in idx[q][..] (the score's index inside the
@@ -901,17 +878,22 @@ inline int64_t cross_out_stride(const CrossArgs& a) {
   return a.col_stride_out > 0 ? a.col_stride_out
                               : (a.src.col_stride > 0 ? a.src.col_stride : a.src.rows);
 }
+// a spec that is one: 1..16 crosses of 2..4 non-negative field ids
+inline void check_cross_spec(const CrossSpec& x, const char* who) {
+  const std::string w(who);
+  if (x.n < 1 || x.n > kMaxCrosses) throw std::invalid_argument(w + ": 1 to 16 crosses");
+  for (int c = 0; c < x.n; ++c) {
+    if (x.arity[c] < 2 || x.arity[c] > kMaxCrossArity)
+      throw std::invalid_argument(w + ": a cross has 2 to 4 fields");
+    for (int i = 0; i < x.arity[c]; ++i)
+      if (x.field[c][i] < 0) throw std::invalid_argument(w + ": a negative field id");
+  }
+}
 // what both backends refuse
 inline void check_cross_args(const CrossArgs& a) {
   const BatchView& s = a.src;
   const CrossSpec& x = a.spec;
-  if (x.n < 1 || x.n > kMaxCrosses) throw std::invalid_argument("cross_rows: 1 to 16 crosses");
-  for (int c = 0; c < x.n; ++c) {
-    if (x.arity[c] < 2 || x.arity[c] > kMaxCrossArity)
-      throw std::invalid_argument("cross_rows: a cross has 2 to 4 fields");
-    for (int i = 0; i < x.arity[c]; ++i)
-      if (x.field[c][i] < 0) throw std::invalid_argument("cross_rows: a negative field id");
-  }
+  check_cross_spec(x, "cross_rows");
   if (s.rows < 0 || s.nnz < 0 || s.nnz + (int64_t)x.n * s.rows > 0x7fffffffll)
     throw std::invalid_argument("cross_rows: bad batch size (nnz + crosses * rows must fit int32)");
   // (a batch without entries may come without arrays)
@@ -956,6 +938,40 @@ XF_HD void row_cross_keys(const BatchView& b, int64_t r, const CrossSpec& x, u64
     out[c] = cross_key(x.field[c], ops, x.arity[c]);
   }
 }
+
+// Candidate ranking from a frozen LR or FM table (Backend::rank, HIP:
+// kernels_rank.hip): R requests, each one context (CSR: ctx_ptr into
+// ctx_keys) scored against the candidate rows [req_ptr[q], req_ptr[q + 1]) of
+// `cands`.  pctr[row] is the model's prediction for the row made of the
+// context's keys followed by the candidate's: the context's sums -- LR wx, FM
+// (wx, vs[0..D), vp) -- are taken once per tile of 64 candidate rows, in an
+// association that depends on the context alone, and every candidate of the
+// request continues them in occurrence order, as k_serve_lr / k_serve_fm's
+// full rows do.  Pointer values are clamped to the arrays: malformed ctx_ptr /
+// req_ptr give wrong scores, never an access outside them.
+//
+// With feature crosses (spec.n > 0; HIP: kernels_rank_cross.hip) the row also
+// holds the spec's cross keys of the concatenated row, as cross_rows would
+// append them: operand i of cross c is the raw key of the first occurrence of
+// field spec.field[c][i] in context ++ candidate (the context's if it has the
+// field at all, else the candidate's, else ~0), looked up by field id, so both
+// sides' field ids are required (ctx_fgid, cands.fgid).  A cross whose fields
+// all occur in the context belongs to the context's sums; the others are
+// hashed and probed per candidate.  Nothing is materialised.
+struct RankArgs {
+  TableView table;                 // kFrozen, TableLayout::make(model, opt)
+  BatchView cands;                 // any of the three layouts; labels unused
+  const u64* ctx_keys = nullptr;   // [ctx_nnz]
+  const int32_t* ctx_ptr = nullptr;  // [R + 1]
+  int64_t ctx_nnz = 0;
+  int64_t R = 0;                   // requests
+  const int32_t* req_ptr = nullptr;  // [R + 1], req_ptr[R] == cands.rows
+  float* pctr = nullptr;           // [cands.rows]
+  ModelSpec model;                 // kLR or kFM
+  OptSpec opt;
+  const int32_t* ctx_fgid = nullptr;  // [ctx_nnz], with crosses
+  CrossSpec spec;                  // spec.n == 0: no crosses (fgid_base unused)
+};
 
 class Backend {
  public:

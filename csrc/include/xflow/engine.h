@@ -150,6 +150,10 @@ struct EngineConfig {
   // Engine::serve_unfused_latent() reports the window in force.
   int64_t serve_unfused_latent_lo = -1;
   int64_t serve_unfused_latent_hi = -1;
+  // rank_step ranks a model with feature crosses on the device (RankArgs::spec,
+  // kernels_rank_cross.hip); false: rank_step refuses a cross spec, and the
+  // caller expands and crosses the rows itself (the A/B switch)
+  bool rank_cross = true;
 };
 
 // Engine::delta_stats
@@ -539,9 +543,13 @@ class Engine {
   // of cands; pctr [cands.rows].  A frozen LR or FM engine on a backend that
   // ranks (ranks()); throws otherwise.  fm_mfma does not matter here: there is
   // no bit contract with the forward, only with the float64 bound.
+  // spec.n > 0: the rows also hold the spec's cross keys of context ++
+  // candidate (RankArgs); needs ctx_fgid [ctx_nnz], cands.fgid and
+  // EngineConfig::rank_cross.
   bool ranks() const;
   void rank_step(const u64* ctx_keys, const int32_t* ctx_ptr, int64_t ctx_nnz, int64_t R,
-                 const int32_t* req_ptr, const BatchView& cands, float* pctr);
+                 const int32_t* req_ptr, const BatchView& cands, float* pctr,
+                 const int32_t* ctx_fgid = nullptr, const CrossSpec& spec = CrossSpec());
   // The best k of every request's scores, in order (TopkArgs, backend.h):
   // pctr [rows] and req_ptr [R + 1] as rank_step takes and leaves them, idx /
   // score [R][k].  Any engine, either backend; stream-ordered, no sync.

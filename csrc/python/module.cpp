@@ -147,6 +147,22 @@ StepInputs inputs_from(py::dict d) {
 
 }  // namespace
 
+// a CrossSpec from lists of field ids (the sizes it can hold; the backend checks the rest)
+static CrossSpec cross_spec_from(const std::vector<std::vector<int32_t>>& crosses,
+                                 const char* who) {
+  CrossSpec x;
+  if (crosses.size() > (size_t)kMaxCrosses)
+    throw std::invalid_argument(std::string(who) + ": 1 to 16 crosses");
+  x.n = (int)crosses.size();
+  for (size_t c = 0; c < crosses.size(); ++c) {
+    if (crosses[c].size() > (size_t)kMaxCrossArity)
+      throw std::invalid_argument(std::string(who) + ": a cross has 2 to 4 fields");
+    x.arity[c] = (int)crosses[c].size();
+    for (size_t i = 0; i < crosses[c].size(); ++i) x.field[c][i] = crosses[c][i];
+  }
+  return x;
+}
+
 PYBIND11_MODULE(_xflow_native, m) {
   m.doc() = "xflow-amd native core: HBM hash-table engine, gfx950 kernels, libffm reader";
 
@@ -428,8 +444,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        bool scratch_carry, bool red_rank, bool delta_track, int delta_log2,
                        bool red_local, bool red_apply, bool serve_fused,
                        int64_t serve_unfused_lo, int64_t serve_unfused_hi,
-                       int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi) {
+                       int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi,
+                       bool rank_cross) {
              EngineConfig c;
+             c.rank_cross = rank_cross;
              c.serve_unfused_latent_lo = serve_unfused_latent_lo;
              c.serve_unfused_latent_hi = serve_unfused_latent_hi;
              c.serve_fused = serve_fused;
@@ -474,7 +492,8 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("delta_log2") = 0, py::arg("red_local") = true,
            py::arg("red_apply") = true, py::arg("serve_fused") = true,
            py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256,
-           py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1)
+           py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1,
+           py::arg("rank_cross") = true)
       // serving snapshots (docs/DESIGN.md §2)
       .def_property_readonly("frozen", &Engine::frozen)
       .def_property_readonly("serve_fused", &Engine::serve_fused)
@@ -662,11 +681,17 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def_property_readonly("ranks", &Engine::ranks)
       .def("rank_step",
            [](Engine& e, uintptr_t ctx_keys, uintptr_t ctx_ptr, int64_t ctx_nnz, int64_t R,
-              uintptr_t req_ptr, const BatchView& cands, uintptr_t pctr) {
+              uintptr_t req_ptr, const BatchView& cands, uintptr_t pctr, uintptr_t ctx_fgid,
+              const std::vector<std::vector<int32_t>>& crosses) {
+             const CrossSpec spec = cross_spec_from(crosses, "rank_step");
+             py::gil_scoped_release nogil;
              e.rank_step(P<const u64>(ctx_keys), P<const int32_t>(ctx_ptr), ctx_nnz, R,
-                         P<const int32_t>(req_ptr), cands, P<float>(pctr));
+                         P<const int32_t>(req_ptr), cands, P<float>(pctr),
+                         P<const int32_t>(ctx_fgid), spec);
            },
-           py::call_guard<py::gil_scoped_release>())
+           py::arg("ctx_keys"), py::arg("ctx_ptr"), py::arg("ctx_nnz"), py::arg("R"),
+           py::arg("req_ptr"), py::arg("cands"), py::arg("pctr"), py::arg("ctx_fgid") = 0,
+           py::arg("crosses") = std::vector<std::vector<int32_t>>())
       .def("topk_step",
            [](Engine& e, uintptr_t pctr, uintptr_t req_ptr, int64_t R, int64_t rows, int k,
               uintptr_t idx, uintptr_t score) {
@@ -756,15 +781,7 @@ PYBIND11_MODULE(_xflow_native, m) {
              CrossArgs a;
              a.src = b;
              a.key_bytes = key_bytes;
-             if (crosses.size() > (size_t)kMaxCrosses)
-               throw std::invalid_argument("cross_rows: 1 to 16 crosses");
-             a.spec.n = (int)crosses.size();
-             for (size_t c = 0; c < crosses.size(); ++c) {
-               if (crosses[c].size() > (size_t)kMaxCrossArity)
-                 throw std::invalid_argument("cross_rows: a cross has 2 to 4 fields");
-               a.spec.arity[c] = (int)crosses[c].size();
-               for (size_t i = 0; i < crosses[c].size(); ++i) a.spec.field[c][i] = crosses[c][i];
-             }
+             a.spec = cross_spec_from(crosses, "cross_rows");
              a.spec.fgid_base = fgid_base;
              a.has_seed = !seed.is_none();
              if (a.has_seed) a.seed = seed.cast<uint64_t>();

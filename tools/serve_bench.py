@@ -29,11 +29,16 @@ host lists, wall clock with the upload.  --rank --top-k K[,K..] measures the
 selection of the best K instead: ``rank_topk`` on the device against
 ``rank_step``, the download of every score and a vectorised selection on the
 host in the same order (what a caller does without ``topk_step``), from device
-batches and from host lists, in alternating blocks.
+batches and from host lists, in alternating blocks.  --rank --cross SPEC
+(3x30,1x2) trains and exports with those feature crosses and measures crossed
+ranking: ``rank_step(crosses=...)`` against ``cross_batch`` + ``eval_step`` on
+the expanded rows of the same engine, with the uncrossed ``rank_step`` as the
+floor, then ``Predictor.rank_keys`` with ``rank_cross`` on and off.
 
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
     python tools/serve_bench.py --rank [--model fm --fm-math standard] [--out profiles/rank.txt]
     python tools/serve_bench.py --rank --top-k 10,100 [--out profiles/rank_topk.txt]
+    python tools/serve_bench.py --rank --cross 3x30,5x7 [--out profiles/rank_cross.txt]
 """
 from __future__ import annotations
 
@@ -50,7 +55,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from xflow_amd import checkpoint  # noqa: E402
-from xflow_amd.config import EngineConfig, ModelConfig, OptimConfig  # noqa: E402
+from xflow_amd.config import EngineConfig, ModelConfig, OptimConfig, parse_crosses  # noqa: E402
 from xflow_amd.data.synth import SynthConfig, SyntheticCriteo  # noqa: E402
 from xflow_amd.engine import Batch, Engine  # noqa: E402
 from xflow_amd.serve import Predictor  # noqa: E402
@@ -60,16 +65,21 @@ def dir_bytes(d):
     return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
 
 
-def trained(a, dev, model, log2_cap, load=None, optim=None):
+def trained(a, dev, model, log2_cap, load=None, optim=None, crosses=()):
     eng = Engine(model, optim or OptimConfig(),
-                 EngineConfig(table_log2_cap=log2_cap, max_rows=a.batch, max_nnz=a.batch * a.fields,
-                              table_grow=False), device=dev)
+                 EngineConfig(table_log2_cap=log2_cap, max_rows=a.batch,
+                              max_nnz=a.batch * (a.fields + len(crosses)), table_grow=False),
+                 device=dev)
     synth = SynthConfig(total_features=a.features, hash_space=a.features, seed=a.seed,
                         n_fields=a.fields)
     gen = SyntheticCriteo(eng, a.batch, synth)
     eng.prefill(int((a.table_load if load is None else load) * 2 ** log2_cap))
+    b = gen.alloc_batch() if crosses else None
     for _ in range(a.steps):
-        eng.train_view(gen.next())
+        if crosses:  # (a field's id is its position in the row)
+            eng.train_step(eng.cross_batch(gen.next(out=b), crosses))
+        else:
+            eng.train_view(gen.next())
     torch.cuda.synchronize(dev)
     return eng, synth
 
@@ -141,6 +151,81 @@ def rank_section(a, dev, snap_dir, synth, say):
         m = [median(t) for t in times]
         say("%d %d %.4f %.4f %.2f | %s | %.2f %.2f"
             % (R, per, m[0], m[1], m[1] / m[0],
+               " ; ".join(" ".join("%.4f" % x for x in t) for t in times),
+               median(wall[0]), median(wall[1])))
+
+
+def timed_blocks(calls, reps, blocks, dev):
+    """ms per call of each of `calls`, device-event time, in alternating
+    blocks of `reps` calls (block 0: warm-up)."""
+    times = [[] for _ in calls]
+    for blk in range(blocks + 1):
+        for i, f in enumerate(calls):
+            t0, t1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            t0.record()
+            for _ in range(reps):
+                f()
+            t1.record()
+            torch.cuda.synchronize(dev)
+            if blk:
+                times[i].append(t0.elapsed_time(t1) / reps)
+    return times
+
+
+def rank_cross_section(a, dev, snap_dir, synth, say):
+    """Crossed ranking: the crosses built inside the rank kernel against the
+    rows expanded on the device, crossed by cross_batch and scored by
+    eval_step, one engine; then from host lists with rank_cross on and off
+    (off: the rows are expanded on the host and uploaded)."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    off, _, _ = loaded(snap_dir, dev, a, rank_cross=False)
+    e, C, F, X = p.engine, a.rank_ctx, a.fields, p.crosses
+    assert e.ranks and 0 < C < F and X == a.cross
+    say("# crosses %s: %d of %d take every field from the context"
+        % (a.cross, sum(max(c) < C for c in X), len(X)))
+    say("# ms per call, median of %d alternating blocks of device-event time (batches on the "
+        "device): rank_step with crosses, cross_batch + eval_step on the expanded rows, "
+        "rank_step without crosses (the floor: other scores) | the blocks; then host lists to "
+        "scores, wall clock, Predictor.rank_keys with rank_cross on and off" % a.blocks)
+    say("requests candidates rank_cross expand_cross_eval ratio rank_uncrossed | blocks | "
+        "rank_keys_on_ms rank_keys_off_ms")
+    for R, per in ((1, 64), (1, 256), (1, 4096), (1, 65536), (256, 16)):
+        rows = R * per
+        if rows > a.batch:
+            continue
+        gen = SyntheticCriteo(e, rows, synth)
+        b = gen.alloc_batch()
+        gen.next(out=b)
+        keys = (b.keys.view(F, rows).t() if b.field_major else b.keys.view(rows, F)).contiguous()
+        ctx = keys[torch.arange(R, device=dev) * per, :C].contiguous()
+        fm = lambda k, **kw: Batch(keys=k.t().contiguous().view(-1), labels=b.labels,
+                                   nnz_per_row=k.shape[1], field_major=True, **kw)
+        full = fm(torch.cat([ctx.repeat_interleave(per, 0), keys[:, C:]], 1))
+        ids = torch.arange(F, dtype=torch.int32, device=dev)
+        cand = fm(keys[:, C:], fgid=ids[C:].repeat_interleave(rows))
+        cfg = ids[:C].repeat(R)
+        cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
+        rptr = (torch.arange(R + 1, device=dev) * per).to(torch.int32)
+        out = torch.empty(rows, dtype=torch.float32, device=dev)
+        calls = (lambda: e.rank_step(ctx.view(-1), cptr, rptr, cand, out, ctx_fgid=cfg, crosses=X),
+                 lambda: e.eval_step(e.cross_batch(full, X), out),
+                 lambda: e.rank_step(ctx.view(-1), cptr, rptr, cand, out))
+        want = calls[1]().clone()  # (the two routes score the same rows)
+        assert (calls[0]() - want).abs().max().item() < 1e-5
+        times = timed_blocks(calls, 200 if rows <= 4096 else 50, a.blocks, dev)
+        lc, lk = ctx.cpu().tolist(), keys[:, C:].cpu().tolist()
+        lists = (lc, [lk[q * per:(q + 1) * per] for q in range(R)],
+                 [list(range(C))] * R, [[list(range(C, F))] * per] * R)
+        wall = [[], []]
+        for blk in range(4):
+            for i, q in enumerate((p, off)):
+                t0 = time.perf_counter()
+                q.rank_keys(*lists)
+                if blk:
+                    wall[i].append(1000.0 * (time.perf_counter() - t0))
+        m = [median(t) for t in times]
+        say("%d %d %.4f %.4f %.2f %.4f | %s | %.2f %.2f"
+            % (R, per, m[0], m[1], m[1] / m[0], m[2],
                " ; ".join(" ".join("%.4f" % x for x in t) for t in times),
                median(wall[0]), median(wall[1])))
 
@@ -252,6 +337,9 @@ def main() -> int:
     ap.add_argument("--rank-ctx", type=int, default=26, help="context fields of --fields")
     ap.add_argument("--top-k", type=lambda s: [int(x) for x in s.split(",")], default=[],
                     metavar="K[,K..]", help="with --rank: the top-k section instead, at these k")
+    ap.add_argument("--cross", type=parse_crosses, default=[], metavar="SPEC",
+                    help="with --rank: train with these feature crosses (3x30,5x7) and measure "
+                         "crossed ranking")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -280,15 +368,17 @@ def main() -> int:
            torch.cuda.get_device_name(dev)))
     tmp = tempfile.mkdtemp(prefix="serve_bench_", dir=a.tmp or None)
     try:
-        eng, synth = trained(a, dev, model, log2_cap, load, optim)
+        eng, synth = trained(a, dev, model, log2_cap, load, optim, a.cross)
         full_dir, snap_dir = os.path.join(tmp, "full"), os.path.join(tmp, "snap")
         checkpoint.save(eng, full_dir, 0, 1, barrier=lambda: None)
-        checkpoint.save_serving(eng, snap_dir, 0, 1, barrier=lambda: None)
+        checkpoint.save_serving(eng, snap_dir, 0, 1, barrier=lambda: None,
+                                meta=checkpoint.cross_meta(a.cross, None) or None)
         m = checkpoint.load_meta(snap_dir)
         del eng
         torch.cuda.empty_cache()
         if a.rank:
-            (topk_section if a.top_k else rank_section)(a, dev, snap_dir, synth, say)
+            section = rank_cross_section if a.cross else (topk_section if a.top_k else rank_section)
+            section(a, dev, snap_dir, synth, say)
             return done()
         say("kind keys checkpoint_bytes load_seconds device_bytes")
         arms = []

@@ -209,6 +209,11 @@ class EngineConfig:
     # and runs only when asked for.  Engine.serve_unfused_rows_latent reports
     # the window in force
     serve_unfused_rows_latent: tuple = (-1, -1)
+    # Engine.rank_step ranks a model with feature crosses on the device: the
+    # cross keys of (context, candidate) are built inside the rank kernel
+    # (docs/DESIGN.md §2); False: rank_step refuses ``crosses`` and Predictor
+    # expands and crosses the rows before it scores them (the A/B switch)
+    rank_cross: bool = True
 
 
 @dataclass

@@ -214,7 +214,8 @@ class Engine:
                            serve_unfused_lo=int(self.cfg.serve_unfused_rows[0]),
                            serve_unfused_hi=int(self.cfg.serve_unfused_rows[1]),
                            serve_unfused_latent_lo=int(self.cfg.serve_unfused_rows_latent[0]),
-                           serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]))
+                           serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]),
+                           rank_cross=self.cfg.rank_cross)
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
         # delta_clear() calls so far: a serving or checkpoint delta is only
@@ -277,14 +278,30 @@ class Engine:
         return bool(self._e.ranks)
 
     def rank_step(self, ctx_keys: torch.Tensor, ctx_ptr: torch.Tensor, req_ptr: torch.Tensor,
-                  cands: Batch, pctr: torch.Tensor | None = None) -> torch.Tensor:
+                  cands: Batch, pctr: torch.Tensor | None = None,
+                  ctx_fgid: torch.Tensor | None = None, crosses=None) -> torch.Tensor:
         """Candidate ranking in one launch (docs/DESIGN.md §2): R contexts in
         CSR form (ctx_keys int64 u64 bit patterns, ctx_ptr int32 [R + 1]),
         request q scored against the rows [req_ptr[q], req_ptr[q + 1]) of
         ``cands`` (req_ptr int32 [R + 1], its last entry the row count; the
         labels are ignored).  pctr[row] is the model's prediction for the
-        context's keys followed by the candidate's.  Raises unless ``ranks``."""
+        context's keys followed by the candidate's.  Raises unless ``ranks``.
+
+        ``crosses`` (check_crosses): the row also holds the cross keys that
+        ``cross_batch`` would append to context + candidate -- an operand is
+        the first occurrence of its field id, the context's before the
+        candidate's -- built inside the kernel.  Needs the field ids of both
+        sides (``ctx_fgid`` int32 like ctx_keys, ``cands.fgid``) and
+        EngineConfig.rank_cross."""
         cands.check(self.device)
+        if crosses:
+            crosses = [list(c) for c in check_crosses(crosses)]
+            if ctx_fgid is None or cands.fgid is None:
+                raise ValueError("rank_step: crosses need ctx_fgid and the candidates' fgid")
+            if ctx_fgid.dtype != torch.int32 or ctx_fgid.device != self.device or \
+                    not ctx_fgid.is_contiguous() or ctx_fgid.numel() != ctx_keys.numel():
+                raise ValueError(f"ctx_fgid must be a contiguous int32 tensor on {self.device} "
+                                 "with one id per context key")
         for name, t, dt in (("ctx_keys", ctx_keys, torch.int64), ("ctx_ptr", ctx_ptr, torch.int32),
                             ("req_ptr", req_ptr, torch.int32)):
             if t.dtype != dt or t.device != self.device or not t.is_contiguous():
@@ -296,7 +313,7 @@ class Engine:
         self._sync_stream()
         self._e.rank_step(ctx_keys.data_ptr(), ctx_ptr.data_ptr(), int(ctx_keys.numel()),
                           int(req_ptr.numel()) - 1, req_ptr.data_ptr(), cands.view(),
-                          pctr.data_ptr())
+                          pctr.data_ptr(), ctx_fgid.data_ptr() if crosses else 0, crosses or [])
         return pctr
 
     def topk_step(self, pctr: torch.Tensor, req_ptr: torch.Tensor,
@@ -325,10 +342,12 @@ class Engine:
         return idx, score
 
     def rank_topk(self, ctx_keys: torch.Tensor, ctx_ptr: torch.Tensor, req_ptr: torch.Tensor,
-                  cands: Batch, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+                  cands: Batch, k: int, ctx_fgid: torch.Tensor | None = None,
+                  crosses=None) -> tuple[torch.Tensor, torch.Tensor]:
         """rank_step, then topk_step on its scores, in the same stream: the best
         k candidates of every request without their scores leaving the device."""
-        return self.topk_step(self.rank_step(ctx_keys, ctx_ptr, req_ptr, cands), req_ptr, k)
+        p = self.rank_step(ctx_keys, ctx_ptr, req_ptr, cands, ctx_fgid=ctx_fgid, crosses=crosses)
+        return self.topk_step(p, req_ptr, k)
 
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""

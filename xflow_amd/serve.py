@@ -88,14 +88,14 @@ class Predictor:
 
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
                  max_nnz_per_row: int = 64, serve_fused: bool = True,
-                 serve_unfused_rows=None, serve_unfused_rows_latent=None):
+                 serve_unfused_rows=None, serve_unfused_rows_latent=None, rank_cross: bool = True):
         self.root = ckpt  # (refresh() resolves it again)
         if device is None:
             device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
         self.max_rows = int(max_rows)
         self._max_nnz_per_row = int(max_nnz_per_row)
-        self._serve_cfg = dict(serve_fused=serve_fused,
+        self._serve_cfg = dict(serve_fused=serve_fused, rank_cross=bool(rank_cross),
                                **({} if serve_unfused_rows is None else
                                   {"serve_unfused_rows": tuple(serve_unfused_rows)}),
                                **({} if serve_unfused_rows_latent is None else
@@ -288,9 +288,11 @@ class Predictor:
         float32 array per request: the model's prediction for the context's
         keys followed by the candidate's.  A frozen LR or FM snapshot on the
         GPU scores a request's context once per 64 candidates
-        (Engine.rank_step); every other model, a model with feature crosses, a
-        full checkpoint and the CPU expand the rows on the host and score them
-        with predict_csr (which then needs the field ids where it would).
+        (Engine.rank_step), a model with feature crosses too: given the field
+        ids, its cross keys are built inside the kernel.  Every other model, a
+        full checkpoint, the CPU and a crossed model with ``rank_cross=False``
+        expand the rows on the host and score them with predict_csr (which
+        needs the field ids where it would).
 
         With ``top_k`` (1 .. 1024) the selection happens on the device too
         (Engine.topk_step) and request q comes back as (index int32[n], pctr
@@ -315,8 +317,12 @@ class Predictor:
             raise ValueError("give the field ids of both the contexts and the candidates, or neither")
         if ctx_fgid is not None and (len(ctx_fgid) != len(ctx_keys) or len(cand_fgid) != len(cand_keys)):
             raise ValueError("field ids must hold one id per key")
-        if self.engine.ranks and not self.crosses:
-            out = self._rank_device(ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k)
+        crossed = bool(self.crosses)
+        # (a crossed model without field ids: predict_csr below raises)
+        if self.engine.ranks and (not crossed or
+                                  (self.engine.cfg.rank_cross and ctx_fgid is not None)):
+            fg = (np.asarray(ctx_fgid, np.int32), np.asarray(cand_fgid, np.int32)) if crossed else None
+            out = self._rank_device(ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k, fg)
             if top_k is not None:
                 return out
         else:
@@ -365,12 +371,14 @@ class Predictor:
             out.append(ps[0] if ps else none)
         return out
 
-    def _rank_device(self, ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k=None):
+    def _rank_device(self, ctx_keys, ctx_ptr, cand_keys, cand_ptr, req_ptr, top_k=None, fgid=None):
         """Engine.rank_step over chunks of at most max_rows candidate rows and
         the engine's max_nnz keys.  A chunk takes the contexts of the requests
         it meets; a context's sums do not depend on which rows share its
         launch, so the chunking cannot change a score.  With ``top_k`` only
-        each chunk's best pairs are downloaded (rank_csr's second form)."""
+        each chunk's best pairs are downloaded (rank_csr's second form).
+        ``fgid``: the (context, candidate) field ids of a model with crosses,
+        uploaded per chunk like the keys; nothing is appended to the rows."""
         rows, dev = len(cand_ptr) - 1, self.device
         out = np.empty(rows, np.float32)
         parts = [[] for _ in range(len(req_ptr) - 1)]
@@ -391,11 +399,14 @@ class Predictor:
                 c0, c1 = int(ctx_ptr[q0]), int(ctx_ptr[q1])
                 b = Batch(keys=up(cand_keys[k0:k1].view(np.int64), np.int64),
                           labels=torch.zeros(r1 - r, dtype=torch.float32, device=dev),
-                          row_ptr=up(cand_ptr[r:r1 + 1] - k0, np.int32))
+                          row_ptr=up(cand_ptr[r:r1 + 1] - k0, np.int32),
+                          fgid=None if fgid is None else up(fgid[1][k0:k1], np.int32))
                 rp = np.clip(req_ptr[q0:q1 + 1], r, r1) - r
                 p = self.engine.rank_step(up(ctx_keys[c0:c1].view(np.int64), np.int64),
                                           up(ctx_ptr[q0:q1 + 1] - c0, np.int32),
-                                          up(rp, np.int32), b)
+                                          up(rp, np.int32), b,
+                                          ctx_fgid=None if fgid is None else up(fgid[0][c0:c1], np.int32),
+                                          crosses=self.crosses if fgid is not None else None)
                 if top_k is None:
                     out[r:r1] = p.cpu().numpy()
                 else:
