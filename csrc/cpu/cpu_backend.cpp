@@ -927,6 +927,63 @@ class CpuBackend final : public Backend {
       }
     }
   }
+  // a row's sums in one chain in occurrence order, finished as the model
+  // finishes a row; a key that is not in the table reads absent_weight
+  void pool_rows(const PoolRowsArgs& a) override {
+    if (!pool_check(a)) return;
+    const TableView& t = a.table;
+    const TableLayout& L = t.L;
+    const bool fm = a.model.kind == kFM, standard = a.model.fm_math == kFmStandard;
+    const int D = fm ? a.model.v_dim : 0, W = pool_width(a.model);
+    std::vector<float> vs((size_t)D);
+    for (int64_t r = 0; r < a.batch.rows; ++r) {
+      const RowSpan rs = row_span(a.batch, r);
+      float wx = 0.0f, vp = 0.0f;
+      std::fill(vs.begin(), vs.end(), 0.0f);
+      for (int j = 0; j < rs.len; ++j) {
+        const u64 key = sanitize_key(a.batch.keys[rs.at(j)]);
+        bool claimed = false;
+        const u32 slot = probe(t, key, false, claimed);
+        const u32* sp = slot == kNoSlot ? nullptr : t.words + (u64)slot * L.stride;
+        auto w = [&](int p) {
+          return sp ? slot_weight(sp, key, p, L, a.opt) : absent_weight(key, p, L, a.opt);
+        };
+        wx += w(0);
+        for (int k = 0; k < D; ++k) {
+          const float v = w(1 + k);
+          vs[(size_t)k] += v;
+          vp += v * v;
+        }
+      }
+      float sq = 0.0f, vsum = 0.0f;
+      for (int k = 0; k < D; ++k) {
+        sq += vs[(size_t)k] * vs[(size_t)k];
+        vsum += vs[(size_t)k];
+      }
+      float* out = a.vec + r * W;
+      std::fill(out, out + W, 0.0f);
+      out[0] = !fm ? wx : (standard ? wx + 0.5f * (sq - vp) : wx + (vsum * vsum - vp));
+      if (fm && standard) std::copy(vs.begin(), vs.end(), out + 1);
+      if (fm && !standard) out[1] = vsum;
+    }
+  }
+  // the product's definition in plain fp32: k ascending from 0.0f
+  void pool_score(const PoolScoreArgs& a) override {
+    if (!pool_check(a)) return;
+    const int Dk = pool_dk(a.model), W = pool_width(a.model);
+    const float g = pool_gain(a.model);
+    for (int64_t q = 0; q < a.R; ++q) {
+      const float* c = a.ctx + q * W;
+      for (int64_t i = 0; i < a.N; ++i) {
+        const float* p = a.pool + i * W;
+        float y = 0.0f;
+        for (int k = 0; k < Dk; ++k) y += (g * c[1 + k]) * p[1 + k];
+        y += c[0];
+        y += p[0];
+        a.pctr[q * a.N + i] = sigmoid_ref(y);
+      }
+    }
+  }
 
  private:
   std::vector<char> stage_buf_[2];

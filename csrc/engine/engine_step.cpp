@@ -730,4 +730,32 @@ void Engine::topk_step(const float* pctr, const int32_t* req_ptr, int64_t R, int
   be_->topk(ta);
 }
 
+bool Engine::pools() const {
+  const ModelSpec& m = cfg_.model;
+  return frozen() && (m.kind == kLR || (m.kind == kFM && !(m.fm_math == kFmStandard && m.fm_mfma)));
+}
+
+void Engine::pool_rows(const BatchView& b, float* vec) {
+  if (!pools()) throw std::runtime_error("pool_rows: needs a frozen LR or FM engine (no fm_mfma)");
+  PoolRowsArgs pa;
+  pa.table = table_;
+  pa.batch = b;
+  pa.vec = vec;
+  pa.model = cfg_.model;
+  pa.opt = cfg_.opt;
+  be_->pool_rows(pa);
+}
+
+void Engine::pool_score(const float* ctx, int64_t R, const float* pool, int64_t N, float* pctr) {
+  if (!pools()) throw std::runtime_error("pool_score: needs a frozen LR or FM engine (no fm_mfma)");
+  PoolScoreArgs pa;
+  pa.ctx = ctx;
+  pa.pool = pool;
+  pa.R = R;
+  pa.N = N;
+  pa.pctr = pctr;
+  pa.model = cfg_.model;
+  be_->pool_score(pa);
+}
+
 }  // namespace xflow

@@ -477,6 +477,8 @@ class HipBackend final : public Backend {
   bool ranks() const override { return true; }
   void rank(const RankArgs& a) override { hip::launch_rank(a, stream_); }
   void topk(const TopkArgs& a) override { hip::launch_topk(a, stream_); }
+  void pool_rows(const PoolRowsArgs& a) override { hip::launch_pool_rows(a, stream_); }
+  void pool_score(const PoolScoreArgs& a) override { hip::launch_pool_score(a, stream_); }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

@@ -97,6 +97,10 @@ void launch_rank_cross(const RankArgs& a, hipStream_t st);
 // kernels_topk.hip
 void launch_topk(const TopkArgs& a, hipStream_t st);
 
+// kernels_pool.hip
+void launch_pool_rows(const PoolRowsArgs& a, hipStream_t st);    // LR, FM
+void launch_pool_score(const PoolScoreArgs& a, hipStream_t st);  // LR, FM
+
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);
 void launch_field_major(const void* src, void* dst, int64_t rows, int F, int elem_bytes, bool widen,

@@ -973,6 +973,70 @@ struct RankArgs {
   CrossSpec spec;                  // spec.n == 0: no crosses (fgid_base unused)
 };
 
+// Candidate pools (Backend::pool_rows / pool_score, HIP: kernels_pool.hip).
+// Split a row into a context r and a candidate i and write c_x for the model's
+// own logit of a part alone (the model's finish over that part's sums).  Then
+//   LR                  y(r, i) = c_r + c_i
+//   FM, standard math   y(r, i) = c_r + c_i + sum_k u_r[k] * u_i[k],  u = vs[0..D)
+//   FM, reference math  y(r, i) = c_r + c_i + 2 * u_r * u_i,          u = sum_k vs[k]
+// so a part is described by 1 + Dk floats (pool_dk) and scoring R contexts
+// against N candidates is the product [R, Dk + 2] x [Dk + 2, N] of the rows
+// [g * u_r, c_r, 1] with the columns [u_i, 1, c_i] (g = pool_gain), summed in
+// ascending k from 0.0f, followed by sigmoid_ref.
+XF_HD int pool_dk(const ModelSpec& m) {
+  return m.kind != kFM ? 0 : (m.fm_math == kFmStandard ? m.kernel_dim() : 1);
+}
+XF_HD int pool_width(const ModelSpec& m) { return (1 + pool_dk(m) + 3) & ~3; }
+XF_HD float pool_gain(const ModelSpec& m) {
+  return m.kind == kFM && m.fm_math != kFmStandard ? 2.0f : 1.0f;
+}
+// pool_rows: vec[row] = {c, u[0..Dk), +0.0f ..} of every row of `batch`, each a
+// function of the row's keys in their order alone (HIP: occurrence j of a row
+// belongs to lane j % 64, which sums its share in ascending j from 0.0f; the
+// lanes' sums meet in a fixed butterfly).
+struct PoolRowsArgs {
+  TableView table;                 // kFrozen, TableLayout::make(model, opt)
+  BatchView batch;                 // any of the three layouts; labels unused
+  float* vec = nullptr;            // [batch.rows][pool_width(model)]
+  ModelSpec model;                 // kLR or kFM
+  OptSpec opt;
+};
+// pool_score: pctr[q * N + i] = sigmoid_ref(y(ctx row q, pool row i)); an
+// element depends on its own two rows alone.
+struct PoolScoreArgs {
+  const float* ctx = nullptr;      // [R][W] from pool_rows
+  const float* pool = nullptr;     // [N][W] from pool_rows
+  int64_t R = 0, N = 0;
+  float* pctr = nullptr;           // [R][N]
+  ModelSpec model;                 // kLR or kFM
+};
+// what both backends refuse; false: nothing to write
+inline void pool_check_model(const ModelSpec& m) {
+  if (m.kind != kLR && m.kind != kFM) throw std::runtime_error("pool: LR or FM");
+}
+inline bool pool_check(const PoolRowsArgs& a) {
+  const TableLayout& L = a.table.L;
+  const BatchView& b = a.batch;
+  pool_check_model(a.model);
+  if (L.opt != kFrozen || L.has_flag || L.sp != 1 || L.P != a.model.P() ||
+      L.p_w != a.model.p_w() || L.stride != ((2 + L.P + 3) & ~3))
+    throw std::runtime_error("pool_rows: needs the model's frozen table (2 + P words per slot)");
+  if (b.rows < 0 || b.rows > 0x7fffffffll || b.nnz < 0 || b.nnz > 0x7fffffffll)
+    throw std::runtime_error("pool_rows: rows and keys are int32 offsets");
+  if (b.rows == 0) return false;
+  if (!a.vec || (b.nnz > 0 && !b.keys) || (!b.row_ptr && b.nnz != b.rows * b.nnz_per_row))
+    throw std::runtime_error("pool_rows: null array or a fixed-width batch of another size");
+  return true;
+}
+inline bool pool_check(const PoolScoreArgs& a) {
+  pool_check_model(a.model);
+  if (a.R < 0 || a.N < 0 || (a.N > 0 && a.R > 0x7fffffffll / a.N))
+    throw std::runtime_error("pool_score: requests * candidates must fit int32");
+  if (a.R == 0 || a.N == 0) return false;
+  if (!a.ctx || !a.pool || !a.pctr) throw std::runtime_error("pool_score: null array");
+  return true;
+}
+
 class Backend {
  public:
   virtual ~Backend() = default;
@@ -1187,6 +1251,10 @@ class Backend {
   }
   // the best k scores of every request, in order (see TopkArgs)
   virtual void topk(const TopkArgs& a) = 0;
+  // Candidate pools of LR and FM from a frozen table (PoolRowsArgs,
+  // PoolScoreArgs): rows into pool vectors, contexts against a pool
+  virtual void pool_rows(const PoolRowsArgs& a) = 0;
+  virtual void pool_score(const PoolScoreArgs& a) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

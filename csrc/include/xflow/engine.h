@@ -555,6 +555,17 @@ class Engine {
   // score [R][k].  Any engine, either backend; stream-ordered, no sync.
   void topk_step(const float* pctr, const int32_t* req_ptr, int64_t R, int64_t rows, int k,
                  int32_t* idx, float* score);
+  // Candidate pools (PoolRowsArgs / PoolScoreArgs, backend.h): pool_rows turns
+  // the rows of b into vectors vec [b.rows][pool_width()] -- the pool's once
+  // per model version, the contexts' on every call -- and pool_score scores R
+  // context vectors against N pool vectors into pctr [R][N], request q's
+  // scores at pctr[q * N ..).  A frozen LR or FM engine on either backend,
+  // but for standard FM with fm_mfma (pools()); both throw otherwise.
+  // Stream-ordered, no sync.
+  bool pools() const;
+  int pool_width() const { return xflow::pool_width(cfg_.model); }
+  void pool_rows(const BatchView& b, float* vec);
+  void pool_score(const float* ctx, int64_t R, const float* pool, int64_t N, float* pctr);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that

@@ -699,6 +699,16 @@ PYBIND11_MODULE(_xflow_native, m) {
                          P<int32_t>(idx), P<float>(score));
            },
            py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("pools", &Engine::pools)
+      .def_property_readonly("pool_width", &Engine::pool_width)
+      .def("pool_rows",
+           [](Engine& e, const BatchView& b, uintptr_t vec) { e.pool_rows(b, P<float>(vec)); },
+           py::call_guard<py::gil_scoped_release>())
+      .def("pool_score",
+           [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t pctr) {
+             e.pool_score(P<const float>(ctx), R, P<const float>(pool), N, P<float>(pctr));
+           },
+           py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)
       .def_static("slice_groups", &Engine::slice_groups)
       .def_static("group_slices", &Engine::group_slices)

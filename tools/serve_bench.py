@@ -35,7 +35,16 @@ ranking: ``rank_step(crosses=...)`` against ``cross_batch`` + ``eval_step`` on
 the expanded rows of the same engine, with the uncrossed ``rank_step`` as the
 floor, then ``Predictor.rank_keys`` with ``rank_cross`` on and off.
 
+--pool measures candidate pools (docs/DESIGN.md §2): R contexts of --rank-ctx
+fields against a resident pool of N candidates of the remaining fields --
+``pool_rows`` on the pool (once per model version), then per call ``pool_rows``
+on the contexts + ``pool_score``, the same + ``topk_step`` (K = 100), and
+``pool_score`` alone with its store bandwidth -- against the only other way to
+serve the shape, ``rank_step`` on the pool's rows repeated once per request
+(where those R x N rows stay under --pool-expand-rows).
+
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
+    python tools/serve_bench.py --pool [--model fm --v-dim 32 --fm-math standard]
     python tools/serve_bench.py --rank [--model fm --fm-math standard] [--out profiles/rank.txt]
     python tools/serve_bench.py --rank --top-k 10,100 [--out profiles/rank_topk.txt]
     python tools/serve_bench.py --rank --cross 3x30,5x7 [--out profiles/rank_cross.txt]
@@ -314,6 +323,69 @@ def topk_section(a, dev, snap_dir, synth, say):
                 % (R, per, k, m[0], m[1], w[0], w[1], w[1] / w[0], w[2], w[3]))
 
 
+def pool_section(a, dev, snap_dir, synth, say):
+    """Candidate pools against rank_step on the repeated rows, one engine."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    e, C, F = p.engine, a.rank_ctx, a.fields
+    assert e.pools and e.ranks and 0 < C < F
+    say("# ms per call, medians of %d alternating blocks of device-event time, everything on the "
+        "device.  pool_build: pool_rows on the N candidates (once per model version).  score: "
+        "pool_rows on the R contexts + pool_score.  score_topk: the same + topk_step, K = 100.  "
+        "gemm: pool_score alone, and its R*N*4 bytes of stores per second.  rank_step: the "
+        "pool's rows repeated once per request (R*N rows of %d keys; 'does not fit': more than "
+        "%d rows)" % (a.blocks, F - C, a.pool_expand_rows))
+    say("requests candidates pool_build score score_topk gemm gemm_GB/s rank_step_repeated "
+        "rank_step/score")
+    gen = SyntheticCriteo(e, a.batch, synth)
+    b = gen.alloc_batch()
+
+    def rows_of(n):  # n rows of F keys, a batch at a time
+        parts = []
+        while sum(len(x) for x in parts) < n:
+            gen.next(out=b)
+            parts.append((b.keys.view(F, a.batch).t() if b.field_major
+                          else b.keys.view(a.batch, F)).clone())
+        return torch.cat(parts)[:n]
+
+    fm = lambda k: Batch(keys=k.t().contiguous().view(-1),
+                         labels=torch.zeros(k.shape[0], device=dev), nnz_per_row=k.shape[1],
+                         field_major=True)
+    for N in (4096, 65536, 1048576):
+        cand_keys = rows_of(N)[:, C:].contiguous()
+        pool = fm(cand_keys)
+        pv = e.pool_rows(pool)
+        build = median(timed_blocks((lambda: e.pool_rows(pool, out=pv),), 20, a.blocks, dev)[0])
+        for R in (1, 32, 256):
+            ctx_keys = rows_of(R)[:, :C].contiguous()
+            ctx = Batch(keys=ctx_keys.view(-1), labels=torch.zeros(R, device=dev), nnz_per_row=C)
+            cv, out = e.pool_rows(ctx), torch.empty((R, N), dtype=torch.float32, device=dev)
+            rptr = (torch.arange(R + 1, device=dev) * N).to(torch.int32)
+
+            def score():
+                e.pool_rows(ctx, out=cv)
+                return e.pool_score(cv, pv, out)
+
+            calls = [score, lambda: e.topk_step(score().view(-1), rptr, 100),
+                     lambda: e.pool_score(cv, pv, out)]
+            fits = R * N <= a.pool_expand_rows
+            if fits:
+                rep = fm(cand_keys.repeat(R, 1))
+                cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
+                flat = out.view(-1)
+                calls.append(lambda: e.rank_step(ctx_keys.view(-1), cptr, rptr, rep, flat))
+                want = calls[3]().clone()  # (the two routes score the same rows)
+                assert (score().view(-1) - want).abs().max().item() < 1e-5
+            reps = 200 if R * N <= 1 << 20 else (20 if R * N <= 1 << 25 else 5)
+            m = [median(t) for t in timed_blocks(calls, reps, a.blocks, dev)]
+            say("%d %d %.4f %.4f %.4f %.4f %.0f %s"
+                % (R, N, build, m[0], m[1], m[2], R * N * 4 / m[2] / 1e6,
+                   "%.4f %.2f" % (m[3], m[3] / m[0]) if fits else "does not fit -"))
+            del calls, out
+            if fits:
+                del rep, flat, want
+            torch.cuda.empty_cache()
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -340,6 +412,9 @@ def main() -> int:
     ap.add_argument("--cross", type=parse_crosses, default=[], metavar="SPEC",
                     help="with --rank: train with these feature crosses (3x30,5x7) and measure "
                          "crossed ranking")
+    ap.add_argument("--pool", action="store_true", help="the candidate pool section only")
+    ap.add_argument("--pool-expand-rows", type=int, default=1 << 25,
+                    help="with --pool: rank_step on the repeated rows runs up to this many rows")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -376,6 +451,9 @@ def main() -> int:
         m = checkpoint.load_meta(snap_dir)
         del eng
         torch.cuda.empty_cache()
+        if a.pool:
+            pool_section(a, dev, snap_dir, synth, say)
+            return done()
         if a.rank:
             section = rank_cross_section if a.cross else (topk_section if a.top_k else rank_section)
             section(a, dev, snap_dir, synth, say)

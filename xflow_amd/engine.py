@@ -349,6 +349,71 @@ class Engine:
         p = self.rank_step(ctx_keys, ctx_ptr, req_ptr, cands, ctx_fgid=ctx_fgid, crosses=crosses)
         return self.topk_step(p, req_ptr, k)
 
+    # ---- candidate pools (docs/DESIGN.md §2) ----------------------------------
+    @property
+    def pools(self) -> bool:
+        """pool_rows / pool_score are available: a frozen LR or FM engine
+        (standard FM without fm_mfma), on either backend."""
+        return bool(self._e.pools)
+
+    @property
+    def pool_width(self) -> int:
+        """Floats per pool vector: {c, u[0..Dk), 0 ..}, a multiple of 4."""
+        return int(self._e.pool_width)
+
+    def pool_rows(self, batch: Batch, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The rows of ``batch`` (any layout; labels ignored) as pool vectors,
+        float32 [rows, pool_width]: the part of the model's logit a row
+        contributes when it is one side of a (context, candidate) pair.  A
+        vector depends on its row's keys in their order alone.  Run once per
+        model version on a pool and on every call on the contexts.  Raises
+        unless ``pools``."""
+        batch.check(self.device)
+        W = self.pool_width
+        if out is None:
+            out = torch.empty((batch.rows, W), dtype=torch.float32, device=self.device)
+        self._pool_vecs("out", out, batch.rows)
+        self._sync_stream()
+        self._e.pool_rows(batch.view(), out.data_ptr())
+        return out
+
+    def _pool_vecs(self, name: str, t: torch.Tensor, rows: int | None = None) -> None:
+        if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or \
+                t.dim() != 2 or t.shape[1] != self.pool_width or rows not in (None, t.shape[0]):
+            raise ValueError(f"{name} must be a contiguous float32 [rows, {self.pool_width}] tensor "
+                             f"on {self.device}")
+
+    def pool_score(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor,
+                   pctr: torch.Tensor | None = None) -> torch.Tensor:
+        """R contexts against a pool of N candidates as one matrix product on
+        the device: pctr[q, i] is the model's prediction for context q's keys
+        followed by candidate i's, from their pool vectors (pool_rows) alone --
+        no table access.  An element depends on its own two vectors only.  The
+        sum is associated differently from rank_step's, so the bits may differ;
+        both stay within the float64 bound of the row.  R * N < 2^31."""
+        self._pool_vecs("ctx_vecs", ctx_vecs)
+        self._pool_vecs("pool_vecs", pool_vecs)
+        R, N = int(ctx_vecs.shape[0]), int(pool_vecs.shape[0])
+        if R * N > 0x7fffffff:
+            raise ValueError("pool_score: requests * candidates must stay below 2^31")
+        if pctr is None:
+            pctr = torch.empty((R, N), dtype=torch.float32, device=self.device)
+        elif pctr.dtype != torch.float32 or pctr.device != self.device or \
+                not pctr.is_contiguous() or tuple(pctr.shape) != (R, N):
+            raise ValueError(f"pctr must be a contiguous float32 [{R}, {N}] tensor on {self.device}")
+        self._sync_stream()
+        self._e.pool_score(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(), N, pctr.data_ptr())
+        return pctr
+
+    def pool_topk(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor,
+                  k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """pool_score, then topk_step on its scores in the same stream: every
+        context's best k candidates (index into the pool, score)."""
+        p = self.pool_score(ctx_vecs, pool_vecs)
+        R, N = p.shape
+        req_ptr = torch.arange(R + 1, dtype=torch.int32, device=self.device) * N
+        return self.topk_step(p.view(-1), req_ptr, k)
+
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""
         self._sync_stream()

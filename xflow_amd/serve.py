@@ -23,7 +23,21 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
                       (+ "context_fields", "candidate_fields")  -> {"pctr": [...]}
                       with "top_k": K, the best K selected on the device
                                                 -> {"index": [...], "pctr": [...]}
+        POST /pool    {"name": "ads", "candidates": [[k, ...], ...]}  -> {"name", "candidates"}
+                      registers or replaces a resident candidate pool; then
+        POST /rank    {"context": [k, ...], "pool": "ads"}  (or "contexts": [[k, ...], ...];
+                      optional "top_k")     -> as above, one entry per context with "contexts"
         GET  /health
+
+A candidate catalogue that many requests share is uploaded and probed once,
+as a ``Pool`` (docs/DESIGN.md §2, candidate pools): ``build_pool`` turns every
+candidate into 1 + Dk floats, and ``rank_pool`` scores R contexts against all
+of them as one matrix product on the device, touching the table for the
+contexts' keys alone.
+
+    pool = p.build_pool([[k, ...], ...])         # once per catalogue
+    p.rank_pool([context, ...], pool)         -> [np.float32 [len(pool)]] per context
+    p.rank_pool([context, ...], pool, top_k=K) -> [(index, pctr)] per context
 
 A serving snapshot (checkpoint.save_serving, ``--save-serving``, or the offline
 conversion below) is loaded the same way: ``Predictor(dir)`` sees "kind":
@@ -83,13 +97,29 @@ def _fields(cls, d: dict):
     return cls(**{k: v for k, v in d.items() if k in names})
 
 
+class Pool:
+    """A resident candidate pool (Predictor.build_pool): the candidates' rows on
+    the device as CSR chunks, their pool vectors [n, W] and the model version
+    of the Predictor the vectors were computed from."""
+
+    def __init__(self, chunks, n: int):
+        self.chunks, self.n = chunks, int(n)
+        self.vecs, self.version = None, None
+
+    def __len__(self) -> int:
+        return self.n
+
+
 class Predictor:
     """Scores rows with a model loaded from a checkpoint (see module doc)."""
 
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
                  max_nnz_per_row: int = 64, serve_fused: bool = True,
-                 serve_unfused_rows=None, serve_unfused_rows_latent=None, rank_cross: bool = True):
+                 serve_unfused_rows=None, serve_unfused_rows_latent=None, rank_cross: bool = True,
+                 pool_max_scores: int = 1 << 26):
         self.root = ckpt  # (refresh() resolves it again)
+        self.pool_max_scores = int(pool_max_scores)  # floats of one rank_pool chunk's scores
+        self._version = 0  # bumped whenever the model this Predictor scores with changes
         if device is None:
             device = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
         self.device = device
@@ -140,6 +170,7 @@ class Predictor:
     def _adopt(self, v: dict) -> None:
         for k, x in v.items():
             setattr(self, k, x)
+        self._version += 1
 
     # ---------------------------------------------------------------- refresh
     def refresh(self) -> dict:
@@ -171,6 +202,7 @@ class Predictor:
                                 r = checkpoint.apply_serving_deltas(self.engine, files)
                                 self.ckpt, self.meta = d, checkpoint.load_meta(d)
                                 self.keys = self.engine.table_size()
+                                self._version += 1
                             for k in counts:
                                 counts[k] += r[k]
                         mode = "delta"
@@ -462,6 +494,117 @@ class Predictor:
         k, p, f = parse(candidate_lines)
         return self.rank_csr(ck, cp, k, p, np.array([0, len(p) - 1]), cf, f, top_k)[0]
 
+    # ---------------------------------------------------------------- pools
+    def build_pool_csr(self, keys: np.ndarray, row_ptr: np.ndarray) -> Pool:
+        """A Pool of the candidates of a CSR batch (keys u64, row_ptr n + 1
+        offsets): their rows go to the device once, in chunks of at most
+        ``max_rows`` rows, and Engine.pool_rows turns them into vectors.  A
+        frozen LR or FM snapshot only, on either device; there is no host
+        fallback -- the expanded rows are what a pool exists to avoid."""
+        if self.crosses:
+            raise ValueError("this model was trained with feature crosses: a cross key depends on "
+                             "both the context and the candidate, so a candidate has no vector of "
+                             "its own -- rank with rank_keys / rank_csr")
+        if not self.engine.pools:
+            raise ValueError("candidate pools need a frozen LR or FM serving snapshot "
+                             "(not MVM, not a full checkpoint, not fm_mfma)")
+        keys = np.ascontiguousarray(keys).view(np.uint64)
+        row_ptr = np.asarray(row_ptr, dtype=np.int64)
+        n = len(row_ptr) - 1
+        if row_ptr.ndim != 1 or n < 0 or row_ptr[0] != 0 or row_ptr[-1] != len(keys) or \
+                (np.diff(row_ptr) < 0).any():
+            raise ValueError("row_ptr must hold candidates + 1 non-decreasing offsets from 0 to len(keys)")
+        chunks = []
+        for r in range(0, n, self.max_rows):
+            r1 = min(n, r + self.max_rows)
+            k0, k1 = int(row_ptr[r]), int(row_ptr[r1])
+            chunks.append(self._csr_batch(keys[k0:k1], row_ptr[r:r1 + 1] - k0))
+        pool = Pool(chunks, n)
+        with self._lock:
+            self._pool_vectors(pool)
+        return pool
+
+    def build_pool(self, rows: Sequence[Sequence[int]]) -> Pool:
+        """build_pool_csr from lists of (already hashed) u64 keys."""
+        rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        return self.build_pool_csr(np.array([k for r in rows for k in r], dtype=np.uint64), rp)
+
+    def build_pool_libffm(self, text: bytes) -> Pool:
+        """build_pool_csr from libffm text, a candidate per line (predict_libffm)."""
+        if isinstance(text, str):
+            text = text.encode()
+        if text and not text.endswith(b"\n"):
+            text += b"\n"
+        blk = _native.load().parse_libffm(text)
+        return self.build_pool_csr(np.asarray(blk["keys"]).view(np.uint64),
+                                   np.asarray(blk["row_ptr"], np.int64))
+
+    def _csr_batch(self, keys, row_ptr) -> Batch:
+        dev = self.device
+        return Batch(keys=torch.from_numpy(np.ascontiguousarray(keys).view(np.int64)).to(dev),
+                     labels=torch.zeros(len(row_ptr) - 1, dtype=torch.float32, device=dev),
+                     row_ptr=torch.from_numpy(np.ascontiguousarray(row_ptr, np.int32)).to(dev))
+
+    def _pool_vectors(self, pool: Pool) -> torch.Tensor:
+        """The pool's vectors under this Predictor's current model (lock held):
+        rebuilt from the stored rows when the version has changed -- a
+        refresh() or an engine swap -- so a pool never serves a stale model."""
+        if pool.version != self._version:
+            if not self.engine.pools or self.crosses:
+                raise ValueError("the model this Predictor now holds has no candidate pools")
+            vecs = torch.empty((pool.n, self.engine.pool_width), dtype=torch.float32,
+                               device=self.device)
+            r = 0
+            for b in pool.chunks:
+                self.engine.pool_rows(b, out=vecs[r:r + b.rows])
+                r += b.rows
+            pool.vecs, pool.version = vecs, self._version
+        return pool.vecs
+
+    def rank_pool_csr(self, ctx_keys: np.ndarray, ctx_ptr: np.ndarray, pool: Pool,
+                      top_k: Optional[int] = None) -> list:
+        """R contexts (CSR: ctx_keys u64, ctx_ptr R + 1 offsets) against every
+        candidate of ``pool``.  Returns one float32 array of len(pool) scores
+        per context -- the model's prediction for the context's keys followed
+        by the candidate's -- or with ``top_k`` (1 .. 1024) one (index int32[n],
+        pctr float32[n]) pair, n = min(top_k, len(pool)), in rank_csr's order.
+        The contexts are scored in chunks of whole requests whose scores stay
+        under ``pool_max_scores`` floats."""
+        if top_k is not None and not (isinstance(top_k, (int, np.integer)) and 1 <= top_k <= 1024):
+            raise ValueError("top_k must be an integer from 1 to 1024")
+        ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
+        ctx_ptr = np.asarray(ctx_ptr, dtype=np.int64)
+        R, N = len(ctx_ptr) - 1, pool.n
+        if ctx_ptr.ndim != 1 or R < 0 or ctx_ptr[0] != 0 or ctx_ptr[-1] != len(ctx_keys) or \
+                (np.diff(ctx_ptr) < 0).any():
+            raise ValueError("ctx_ptr must hold requests + 1 non-decreasing offsets from 0 to len(ctx_keys)")
+        per = max(1, min(self.pool_max_scores, 0x7fffffff) // max(N, 1))
+        out = []
+        with self._lock:
+            vecs = self._pool_vectors(pool)
+            for q in range(0, R, per):
+                q1 = min(R, q + per)
+                c0, c1 = int(ctx_ptr[q]), int(ctx_ptr[q1])
+                cv = self.engine.pool_rows(self._csr_batch(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0))
+                if N == 0:
+                    none = (np.zeros(0, np.int32), np.zeros(0, np.float32))
+                    out += [none if top_k is not None else none[1]] * (q1 - q)
+                elif top_k is None:
+                    out += list(self.engine.pool_score(cv, vecs).cpu().numpy())
+                else:
+                    idx, sc = (t.cpu().numpy() for t in self.engine.pool_topk(cv, vecs, int(top_k)))
+                    n = min(int(top_k), N)
+                    out += [(idx[j, :n], sc[j, :n]) for j in range(q1 - q)]
+        return out
+
+    def rank_pool(self, contexts: Sequence[Sequence[int]], pool: Pool,
+                  top_k: Optional[int] = None) -> list:
+        """rank_pool_csr from lists: contexts[q] the (already hashed) u64 keys
+        of request q's context."""
+        rp = np.concatenate([[0], np.cumsum([len(c) for c in contexts])]).astype(np.int64)
+        return self.rank_pool_csr(np.array([k for c in contexts for k in c], dtype=np.uint64), rp,
+                                  pool, top_k)
+
 
 # -------------------------------------------------------------------- service
 def make_app(pred: Predictor):
@@ -501,13 +644,49 @@ def make_app(pred: Predictor):
     predict.__annotations__ = {"req": Req}
     app.post("/predict")(predict)
 
-    RankReq = create_model("RankRequest", context=(list[int], ...),
-                           candidates=(list[list[int]], ...),
+    PoolReq = create_model("PoolRequest", name=(str, ...), candidates=(list[list[int]], ...))
+    pools = {}  # name -> Pool, registered by POST /pool
+
+    def pool(req):
+        try:
+            pools[req.name] = pred.build_pool(req.candidates)
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        return {"name": req.name, "candidates": len(pools[req.name])}
+
+    pool.__annotations__ = {"req": PoolReq}
+    app.post("/pool")(pool)
+
+    RankReq = create_model("RankRequest", context=(Optional[list[int]], None),
+                           candidates=(Optional[list[list[int]]], None),
                            context_fields=(Optional[list[int]], None),
                            candidate_fields=(Optional[list[list[int]]], None),
-                           top_k=(Optional[int], None))
+                           top_k=(Optional[int], None), pool=(Optional[str], None),
+                           contexts=(Optional[list[list[int]]], None))
+
+    def rank_pool(req):
+        """"pool": a registered pool in place of "candidates", under one
+        "context" or many "contexts" (then one entry per context)."""
+        if req.candidates is not None or (req.context is None) == (req.contexts is None):
+            raise HTTPException(400, "with 'pool' give 'context' or 'contexts', and no 'candidates'")
+        if req.pool not in pools:
+            raise HTTPException(404, f"no pool named {req.pool!r}: POST /pool first")
+        try:
+            got = pred.rank_pool(req.contexts if req.context is None else [req.context],
+                                 pools[req.pool], req.top_k)
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        if req.top_k is not None:
+            got = [{"index": [int(i) for i in g[0]], "pctr": [float(x) for x in g[1]]} for g in got]
+            return got[0] if req.context is not None else {"results": got}
+        got = [[float(x) for x in g] for g in got]
+        return {"pctr": got[0] if req.context is not None else got}
 
     def rank(req):
+        if req.pool is not None:
+            return rank_pool(req)
+        if req.context is None or req.candidates is None or req.contexts is not None:
+            raise HTTPException(400, "give 'context' and 'candidates' (or 'pool')")
         try:
             p = pred.rank_keys([req.context], [req.candidates],
                                None if req.context_fields is None else [req.context_fields],
