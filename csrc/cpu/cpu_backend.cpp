@@ -984,6 +984,32 @@ class CpuBackend final : public Backend {
       }
     }
   }
+  // pool_score, then topk on its scores: here so that the interface is whole
+  void pool_topk(const PoolTopkArgs& a) override {
+    if (!pool_check(a)) return;
+    if (a.N > 0 && a.R > 0x7fffffffll / a.N)
+      throw std::runtime_error("pool_topk: requests * candidates must fit int32 on this backend");
+    std::vector<float> p((size_t)(a.R * a.N));
+    std::vector<int32_t> rp((size_t)a.R + 1);
+    for (int64_t q = 0; q <= a.R; ++q) rp[(size_t)q] = (int32_t)(q * a.N);
+    PoolScoreArgs sa;
+    sa.ctx = a.ctx;
+    sa.pool = a.pool;
+    sa.R = a.R;
+    sa.N = a.N;
+    sa.pctr = p.data();
+    sa.model = a.model;
+    pool_score(sa);
+    TopkArgs ta;
+    ta.pctr = p.data();
+    ta.req_ptr = rp.data();
+    ta.R = a.R;
+    ta.rows = a.R * a.N;
+    ta.k = a.k;
+    ta.idx = a.idx;
+    ta.score = a.score;
+    topk(ta);
+  }
 
  private:
   std::vector<char> stage_buf_[2];

@@ -758,4 +758,34 @@ void Engine::pool_score(const float* ctx, int64_t R, const float* pool, int64_t 
   be_->pool_score(pa);
 }
 
+int64_t Engine::pool_topk_words(int64_t N, int k) const {
+  // (one request alone gets the shortest automatic strips)
+  const PoolTopkGeom g = pool_topk_geom(1, N, k, cfg_.pool_topk_strip);
+  return g.strips > 1 ? g.strips * k : 0;
+}
+
+void Engine::pool_topk(const float* ctx, int64_t R, const float* pool, int64_t N, int k,
+                       int32_t* idx, float* score) {
+  if (!pools()) throw std::runtime_error("pool_topk: needs a frozen LR or FM engine (no fm_mfma)");
+  PoolTopkArgs pa;
+  pa.ctx = ctx;
+  pa.pool = pool;
+  pa.R = R;
+  pa.N = N;
+  pa.k = k;
+  pa.idx = idx;
+  pa.score = score;
+  pa.strip = cfg_.pool_topk_strip;
+  pa.model = cfg_.model;
+  if (is_gpu() && pool_check(pa)) {
+    const PoolTopkGeom g = pool_topk_geom(R, N, k, pa.strip);
+    if (g.strips > 1) {
+      const size_t words = (size_t)R * (size_t)g.strips * (size_t)k;
+      pool_topk_partial_.reserve(*be_, words, words);
+      pa.partial = pool_topk_partial_;
+    }
+  }
+  be_->pool_topk(pa);
+}
+
 }  // namespace xflow

@@ -42,6 +42,7 @@
 //     row and candidate column alone, never on R, N, the tile or the rest of
 //     the call.  Out-of-range rows read nothing and store nothing.
 // No atomics, no scratch memory.
+#include "pool_common.h"
 #include "rank_common.h"
 
 namespace xflow {
@@ -49,10 +50,7 @@ namespace hip {
 
 constexpr int kPoolRowWaves = 4;   // rows per workgroup of the row kernels
 constexpr int kPoolTileN = 128;    // candidates per workgroup of k_pool_score
-constexpr int kPoolTileM = 32;     // requests per block (the instruction's M)
 constexpr int kPoolTargetGrid = 2048;  // workgroups wanted before gridDim.y stops growing
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // this lane's share of row rs: occurrences lane, lane + 64, ..
 __device__ __forceinline__ RowSpan pool_lane_span(const RowSpan& rs, int lane) {
@@ -103,13 +101,6 @@ __global__ void __launch_bounds__(kPoolRowWaves * kWave) k_pool_rows_fm(PoolRows
   }
   const int W = (1 + (standard ? D : 1) + 3) & ~3;
   if (lane < W) a.vec[r * W + lane] = out;
-}
-
-// word k of a part's operand: A (ctx) = {g * u, c, 1, 0 ..}, B = {u, 1, c, 0 ..}
-__device__ __forceinline__ float pool_operand(const float* v, int k, int Dk, bool ctx, float g) {
-  if (k < Dk) return ctx ? __fmul_rn(g, v[1 + k]) : v[1 + k];
-  if (k == Dk + (ctx ? 0 : 1)) return v[0];
-  return k == Dk + (ctx ? 1 : 0) ? 1.0f : 0.0f;
 }
 
 template <int KP>

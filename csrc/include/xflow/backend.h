@@ -16,6 +16,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -1036,6 +1037,63 @@ inline bool pool_check(const PoolScoreArgs& a) {
   if (!a.ctx || !a.pool || !a.pctr) throw std::runtime_error("pool_score: null array");
   return true;
 }
+// pool_topk: TopkArgs' answer for R requests that each own all N scores of
+// pool_score -- idx / score [R][k] in the same order with the same padding --
+// without an [R][N] array (HIP: kernels_pool_topk.hip selects next to the
+// accumulators; the CPU backend composes pool_score and topk).  score holds
+// pool_score's bits, but a NaN comes back with an unspecified payload.
+struct PoolTopkArgs {
+  const float* ctx = nullptr;      // [R][W] from pool_rows
+  const float* pool = nullptr;     // [N][W] from pool_rows
+  int64_t R = 0, N = 0;            // each below 2^31; R * N is not limited
+  int k = 0;                       // 1 .. kTopkMaxK
+  int32_t* idx = nullptr;          // [R][k]
+  float* score = nullptr;          // [R][k]
+  u64* partial = nullptr;          // [R][strips][k] scratch, HIP with more than one strip
+  int64_t strip = 0;               // candidates per strip, a multiple of 128; 0: automatic
+  ModelSpec model;                 // kLR or kFM
+};
+// How the HIP path splits a call: a workgroup streams one strip of candidates
+// past the lists of one group of mq requests, which share 4096 words of LDS --
+// a region of 2^lg_region >= max(2 k, 512) words each.
+constexpr int kPoolTopkStep = 128;          // candidates a workgroup scores per step
+constexpr int kPoolTopkWords = 4096;        // words of LDS the lists of a group share
+constexpr int64_t kPoolTopkMinStrip = 4096; // automatic strips are not shorter (unless N is)
+constexpr int64_t kPoolTopkGrid = 2048;     // workgroups wanted before strips stop shrinking
+struct PoolTopkGeom {
+  int lg_region = 9, mq = 8;
+  int64_t groups = 0, strip = kPoolTopkStep, strips = 1;
+};
+inline PoolTopkGeom pool_topk_geom(int64_t R, int64_t N, int k, int64_t strip) {
+  PoolTopkGeom g;
+  while ((1 << g.lg_region) < 2 * k) ++g.lg_region;
+  g.mq = kPoolTopkWords >> g.lg_region;
+  g.groups = (R + g.mq - 1) / g.mq;
+  const int64_t whole = std::max<int64_t>(1, (N + kPoolTopkStep - 1) / kPoolTopkStep) * kPoolTopkStep;
+  if (strip > 0) {
+    g.strip = strip;
+  } else {
+    const int64_t want = std::max<int64_t>(1, kPoolTopkGrid / std::max<int64_t>(1, g.groups));
+    const int64_t per = ((N + want - 1) / want + kPoolTopkStep - 1) / kPoolTopkStep * kPoolTopkStep;
+    g.strip = std::max(per, kPoolTopkMinStrip);
+  }
+  g.strip = std::min(g.strip, whole);
+  g.strips = std::max<int64_t>(1, (N + g.strip - 1) / g.strip);
+  return g;
+}
+// what both backends refuse; false: nothing to write (no request)
+inline bool pool_check(const PoolTopkArgs& a) {
+  pool_check_model(a.model);
+  if (a.k < 1 || a.k > kTopkMaxK) throw std::runtime_error("pool_topk: k must be 1 .. 1024");
+  if (a.R < 0 || a.R > 0x7fffffffll || a.N < 0 || a.N > 0x7fffffffll)
+    throw std::runtime_error("pool_topk: requests and candidates are int32 counts");
+  if (a.strip < 0 || a.strip % kPoolTopkStep != 0)
+    throw std::runtime_error("pool_topk: a strip is a multiple of 128 candidates");
+  if (a.R == 0) return false;
+  if (!a.idx || !a.score || !a.ctx || (a.N > 0 && !a.pool))
+    throw std::runtime_error("pool_topk: null array");
+  return true;
+}
 
 class Backend {
  public:
@@ -1255,6 +1313,8 @@ class Backend {
   // PoolScoreArgs): rows into pool vectors, contexts against a pool
   virtual void pool_rows(const PoolRowsArgs& a) = 0;
   virtual void pool_score(const PoolScoreArgs& a) = 0;
+  // every context's best k candidates of a pool (PoolTopkArgs)
+  virtual void pool_topk(const PoolTopkArgs& a) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

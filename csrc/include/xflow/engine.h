@@ -154,6 +154,12 @@ struct EngineConfig {
   // kernels_rank_cross.hip); false: rank_step refuses a cross spec, and the
   // caller expands and crosses the rows itself (the A/B switch)
   bool rank_cross = true;
+  // pool_topk on HIP selects inside the score kernel (PoolTopkArgs,
+  // kernels_pool_topk.hip); false: the caller composes pool_score and
+  // topk_step (the A/B switch).  pool_topk_strip: candidates per strip of that
+  // kernel, a multiple of 128; 0: automatic (pool_topk_geom)
+  bool pool_topk_fused = true;
+  int64_t pool_topk_strip = 0;
 };
 
 // Engine::delta_stats
@@ -566,6 +572,16 @@ class Engine {
   int pool_width() const { return xflow::pool_width(cfg_.model); }
   void pool_rows(const BatchView& b, float* vec);
   void pool_score(const float* ctx, int64_t R, const float* pool, int64_t N, float* pctr);
+  // Every context's best k of the pool (PoolTopkArgs): idx / score [R][k] as
+  // topk_step leaves them for pool_score's scores, with no [R][N] array and no
+  // bound on R * N.  pool_topk_fused(): this is the path the engine takes (HIP
+  // and EngineConfig::pool_topk_fused).  pool_topk_words: an upper bound, for
+  // any R, of the u64 words of scratch one request of such a call needs.
+  bool pool_topk_fused() const { return is_gpu() && cfg_.pool_topk_fused; }
+  int pool_topk_group(int k) const { return pool_topk_geom(1, 1, k, 0).mq; }
+  int64_t pool_topk_words(int64_t N, int k) const;
+  void pool_topk(const float* ctx, int64_t R, const float* pool, int64_t N, int k, int32_t* idx,
+                 float* score);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that
@@ -897,6 +913,7 @@ class Engine {
   int64_t queued_adds_ = 0;         // cumulative insert bound queued so far
   int64_t growths_ = 0, splits_ = 0, monitor_waits_ = 0;
   DeviceBuffer<u64> topk_partial_;  // [max_rows or more] topk_step over several tiles, on first use
+  DeviceBuffer<u64> pool_topk_partial_;  // [R][strips][k] pool_topk over several strips, on first use
   DeviceBuffer<unsigned long long> pruned_dev_;  // [1] keys dropped by prune(), cumulative
   int64_t pruned_keys_ = 0;
   double grow_s_ = 0.0;

@@ -445,8 +445,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        bool red_local, bool red_apply, bool serve_fused,
                        int64_t serve_unfused_lo, int64_t serve_unfused_hi,
                        int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi,
-                       bool rank_cross) {
+                       bool rank_cross, bool pool_topk_fused, int64_t pool_topk_strip) {
              EngineConfig c;
+             c.pool_topk_fused = pool_topk_fused;
+             c.pool_topk_strip = pool_topk_strip;
              c.rank_cross = rank_cross;
              c.serve_unfused_latent_lo = serve_unfused_latent_lo;
              c.serve_unfused_latent_hi = serve_unfused_latent_hi;
@@ -493,7 +495,8 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("red_apply") = true, py::arg("serve_fused") = true,
            py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256,
            py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1,
-           py::arg("rank_cross") = true)
+           py::arg("rank_cross") = true, py::arg("pool_topk_fused") = true,
+           py::arg("pool_topk_strip") = 0)
       // serving snapshots (docs/DESIGN.md §2)
       .def_property_readonly("frozen", &Engine::frozen)
       .def_property_readonly("serve_fused", &Engine::serve_fused)
@@ -707,6 +710,16 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def("pool_score",
            [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t pctr) {
              e.pool_score(P<const float>(ctx), R, P<const float>(pool), N, P<float>(pctr));
+           },
+           py::call_guard<py::gil_scoped_release>())
+      .def_property_readonly("pool_topk_fused", &Engine::pool_topk_fused)
+      .def("pool_topk_group", &Engine::pool_topk_group)
+      .def("pool_topk_words", &Engine::pool_topk_words)
+      .def("pool_topk",
+           [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, int k, uintptr_t idx,
+              uintptr_t score) {
+             e.pool_topk(P<const float>(ctx), R, P<const float>(pool), N, k, P<int32_t>(idx),
+                         P<float>(score));
            },
            py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)

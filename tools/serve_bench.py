@@ -38,7 +38,10 @@ floor, then ``Predictor.rank_keys`` with ``rank_cross`` on and off.
 --pool measures candidate pools (docs/DESIGN.md §2): R contexts of --rank-ctx
 fields against a resident pool of N candidates of the remaining fields --
 ``pool_rows`` on the pool (once per model version), then per call ``pool_rows``
-on the contexts + ``pool_score``, the same + ``topk_step`` (K = 100), and
+on the contexts + ``pool_score``, the top K (--top-k, 100) by the fused
+``pool_topk`` kernel and by ``pool_score`` + ``topk_step`` (a line for 2048
+requests on a million candidates, fused alone, and one for a pool sorted
+ascending, its worst case), and
 ``pool_score`` alone with its store bandwidth -- against the only other way to
 serve the shape, ``rank_step`` on the pool's rows repeated once per request
 (where those R x N rows stay under --pool-expand-rows).
@@ -325,17 +328,19 @@ def topk_section(a, dev, snap_dir, synth, say):
 
 def pool_section(a, dev, snap_dir, synth, say):
     """Candidate pools against rank_step on the repeated rows, one engine."""
-    p, _, _ = loaded(snap_dir, dev, a)
+    p, _, _ = loaded(snap_dir, dev, a, pool_topk_fused_min=0)  # (the kernel at every size)
     e, C, F = p.engine, a.rank_ctx, a.fields
-    assert e.pools and e.ranks and 0 < C < F
+    K = a.top_k[0] if a.top_k else 100
+    assert e.pools and e.ranks and 0 < C < F and e.pool_topk_fused
     say("# ms per call, medians of %d alternating blocks of device-event time, everything on the "
         "device.  pool_build: pool_rows on the N candidates (once per model version).  score: "
-        "pool_rows on the R contexts + pool_score.  score_topk: the same + topk_step, K = 100.  "
-        "gemm: pool_score alone, and its R*N*4 bytes of stores per second.  rank_step: the "
-        "pool's rows repeated once per request (R*N rows of %d keys; 'does not fit': more than "
-        "%d rows)" % (a.blocks, F - C, a.pool_expand_rows))
-    say("requests candidates pool_build score score_topk gemm gemm_GB/s rank_step_repeated "
-        "rank_step/score")
+        "pool_rows on the R contexts + pool_score.  topk_fused: pool_rows on the contexts + "
+        "pool_topk on the fused kernel; topk_composed: score + topk_step; both K = %d, the same "
+        "arrays.  gemm: pool_score alone, and its R*N*4 bytes of stores per second.  rank_step: "
+        "the pool's rows repeated once per request (R*N rows of %d keys; 'does not fit': more "
+        "than %d rows)" % (a.blocks, K, F - C, a.pool_expand_rows))
+    say("requests candidates pool_build score topk_fused topk_composed gemm gemm_GB/s "
+        "rank_step_repeated rank_step/score")
     gen = SyntheticCriteo(e, a.batch, synth)
     b = gen.alloc_batch()
 
@@ -365,25 +370,44 @@ def pool_section(a, dev, snap_dir, synth, say):
                 e.pool_rows(ctx, out=cv)
                 return e.pool_score(cv, pv, out)
 
-            calls = [score, lambda: e.topk_step(score().view(-1), rptr, 100),
-                     lambda: e.pool_score(cv, pv, out)]
+            def fused(vecs=pv):
+                e.pool_rows(ctx, out=cv)
+                return e.pool_topk(cv, vecs, K)
+
+            calls = [score, lambda: e.topk_step(score().view(-1), rptr, K),
+                     lambda: e.pool_score(cv, pv, out), fused]
+            for x, y in zip(calls[1](), fused()):  # (the two paths agree, bit for bit)
+                assert torch.equal(x.view(torch.int32), y.view(torch.int32))
             fits = R * N <= a.pool_expand_rows
             if fits:
                 rep = fm(cand_keys.repeat(R, 1))
                 cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
                 flat = out.view(-1)
                 calls.append(lambda: e.rank_step(ctx_keys.view(-1), cptr, rptr, rep, flat))
-                want = calls[3]().clone()  # (the two routes score the same rows)
+                want = calls[4]().clone()  # (the two routes score the same rows)
                 assert (score().view(-1) - want).abs().max().item() < 1e-5
             reps = 200 if R * N <= 1 << 20 else (20 if R * N <= 1 << 25 else 5)
             m = [median(t) for t in timed_blocks(calls, reps, a.blocks, dev)]
-            say("%d %d %.4f %.4f %.4f %.4f %.0f %s"
-                % (R, N, build, m[0], m[1], m[2], R * N * 4 / m[2] / 1e6,
-                   "%.4f %.2f" % (m[3], m[3] / m[0]) if fits else "does not fit -"))
+            say("%d %d %.4f %.4f %.4f %.4f %.4f %.0f %s"
+                % (R, N, build, m[0], m[3], m[1], m[2], R * N * 4 / m[2] / 1e6,
+                   "%.4f %.2f" % (m[4], m[4] / m[0]) if fits else "does not fit -"))
             del calls, out
             if fits:
                 del rep, flat, want
             torch.cuda.empty_cache()
+            if (R, N) == (32, 1048576):  # every score survives its filter: the fused path's worst case
+                asc = pv[pv[:, 0].argsort()].contiguous()
+                t = median(timed_blocks((lambda: fused(asc),), reps, a.blocks, dev)[0])
+                say("# %d %d, the pool sorted ascending by c (LR: by score), fused: %.4f" % (R, N, t))
+                del asc
+        if N == 1048576:  # R * N >= 2^31: the fused path alone
+            R = 2048
+            ctx_keys = rows_of(R)[:, :C].contiguous()
+            ctx = Batch(keys=ctx_keys.view(-1), labels=torch.zeros(R, device=dev), nnz_per_row=C)
+            cv = e.pool_rows(ctx)
+            t = median(timed_blocks((lambda: e.pool_topk(e.pool_rows(ctx, out=cv), pv, K),), 5,
+                                    a.blocks, dev)[0])
+            say("%d %d %.4f - %.4f - - - does not fit -" % (R, N, build, t))
 
 
 def main() -> int:

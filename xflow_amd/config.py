@@ -214,6 +214,19 @@ class EngineConfig:
     # (docs/DESIGN.md §2); False: rank_step refuses ``crosses`` and Predictor
     # expands and crosses the rows before it scores them (the A/B switch)
     rank_cross: bool = True
+    # Engine.pool_topk on HIP selects inside the score kernel: the R x N
+    # scores are never stored and R * N is not limited (docs/DESIGN.md §2);
+    # False: pool_score, then topk_step (the A/B switch).  Engine.pool_topk_fused
+    # reports the path taken
+    pool_topk_fused: bool = True
+    # candidates per strip of that kernel, a multiple of 128; 0: automatic
+    # (tests and benchmarks place strip edges with it)
+    pool_topk_strip: int = 0
+    # ... for calls of at least this many scores (requests * candidates);
+    # smaller calls are launch latency on either path and the composed one is
+    # ahead there (profiles/rank_pool_topk.txt: behind up to 32 x 65536 = 2^21,
+    # ahead from 256 x 65536 = 2^24); 0: the fused kernel at every size
+    pool_topk_fused_min: int = 1 << 23
 
 
 @dataclass

@@ -215,7 +215,9 @@ class Engine:
                            serve_unfused_hi=int(self.cfg.serve_unfused_rows[1]),
                            serve_unfused_latent_lo=int(self.cfg.serve_unfused_rows_latent[0]),
                            serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]),
-                           rank_cross=self.cfg.rank_cross)
+                           rank_cross=self.cfg.rank_cross,
+                           pool_topk_fused=self.cfg.pool_topk_fused,
+                           pool_topk_strip=int(self.cfg.pool_topk_strip))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
         # delta_clear() calls so far: a serving or checkpoint delta is only
@@ -361,6 +363,21 @@ class Engine:
         """Floats per pool vector: {c, u[0..Dk), 0 ..}, a multiple of 4."""
         return int(self._e.pool_width)
 
+    @property
+    def pool_topk_fused(self) -> bool:
+        """pool_topk takes the fused kernel: a HIP engine with
+        EngineConfig.pool_topk_fused."""
+        return bool(self._e.pool_topk_fused)
+
+    def pool_topk_group(self, k: int) -> int:
+        """Requests one workgroup of the fused pool_topk serves at this k."""
+        return int(self._e.pool_topk_group(int(k)))
+
+    def pool_topk_words(self, n: int, k: int) -> int:
+        """An upper bound of the 8-byte words of scratch one request of a fused
+        pool_topk against n candidates needs."""
+        return int(self._e.pool_topk_words(int(n), int(k)))
+
     def pool_rows(self, batch: Batch, out: torch.Tensor | None = None) -> torch.Tensor:
         """The rows of ``batch`` (any layout; labels ignored) as pool vectors,
         float32 [rows, pool_width]: the part of the model's logit a row
@@ -407,8 +424,25 @@ class Engine:
 
     def pool_topk(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor,
                   k: int) -> tuple[torch.Tensor, torch.Tensor]:
-        """pool_score, then topk_step on its scores in the same stream: every
-        context's best k candidates (index into the pool, score)."""
+        """Every context's best k candidates (index into the pool, score), int32
+        and float32 [R, k] in topk_step's order with its padding.  With
+        ``pool_topk_fused``, from EngineConfig.pool_topk_fused_min scores on, one
+        kernel scores and selects: no [R, N] array, R * N not limited, the same
+        arrays (a NaN score keeps no payload).  Otherwise pool_score, then
+        topk_step on its scores in the same stream."""
+        if self.pool_topk_fused and \
+                ctx_vecs.shape[0] * pool_vecs.shape[0] >= self.cfg.pool_topk_fused_min:
+            self._pool_vecs("ctx_vecs", ctx_vecs)
+            self._pool_vecs("pool_vecs", pool_vecs)
+            R, N = int(ctx_vecs.shape[0]), int(pool_vecs.shape[0])
+            if not 1 <= int(k) <= 1024:
+                raise ValueError("k must be 1 .. 1024")
+            idx = torch.empty((R, int(k)), dtype=torch.int32, device=self.device)
+            score = torch.empty((R, int(k)), dtype=torch.float32, device=self.device)
+            self._sync_stream()
+            self._e.pool_topk(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(), N, int(k),
+                              idx.data_ptr(), score.data_ptr())
+            return idx, score
         p = self.pool_score(ctx_vecs, pool_vecs)
         R, N = p.shape
         req_ptr = torch.arange(R + 1, dtype=torch.int32, device=self.device) * N

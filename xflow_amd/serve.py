@@ -116,7 +116,8 @@ class Predictor:
     def __init__(self, ckpt: str, device: Optional[torch.device] = None, max_rows: int = 65536,
                  max_nnz_per_row: int = 64, serve_fused: bool = True,
                  serve_unfused_rows=None, serve_unfused_rows_latent=None, rank_cross: bool = True,
-                 pool_max_scores: int = 1 << 26):
+                 pool_max_scores: int = 1 << 26, pool_topk_fused: bool = True,
+                 pool_topk_strip: int = 0, pool_topk_fused_min: Optional[int] = None):
         self.root = ckpt  # (refresh() resolves it again)
         self.pool_max_scores = int(pool_max_scores)  # floats of one rank_pool chunk's scores
         self._version = 0  # bumped whenever the model this Predictor scores with changes
@@ -126,6 +127,10 @@ class Predictor:
         self.max_rows = int(max_rows)
         self._max_nnz_per_row = int(max_nnz_per_row)
         self._serve_cfg = dict(serve_fused=serve_fused, rank_cross=bool(rank_cross),
+                               pool_topk_fused=bool(pool_topk_fused),
+                               pool_topk_strip=int(pool_topk_strip),
+                               **({} if pool_topk_fused_min is None else
+                                  {"pool_topk_fused_min": int(pool_topk_fused_min)}),
                                **({} if serve_unfused_rows is None else
                                   {"serve_unfused_rows": tuple(serve_unfused_rows)}),
                                **({} if serve_unfused_rows_latent is None else
@@ -569,7 +574,9 @@ class Predictor:
         by the candidate's -- or with ``top_k`` (1 .. 1024) one (index int32[n],
         pctr float32[n]) pair, n = min(top_k, len(pool)), in rank_csr's order.
         The contexts are scored in chunks of whole requests whose scores stay
-        under ``pool_max_scores`` floats."""
+        under ``pool_max_scores`` floats; with ``top_k`` on an engine whose
+        pool_topk is fused no scores are stored, and a chunk is bounded by the
+        kernel's scratch instead (at most 4 * pool_max_scores bytes)."""
         if top_k is not None and not (isinstance(top_k, (int, np.integer)) and 1 <= top_k <= 1024):
             raise ValueError("top_k must be an integer from 1 to 1024")
         ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
@@ -579,6 +586,9 @@ class Predictor:
                 (np.diff(ctx_ptr) < 0).any():
             raise ValueError("ctx_ptr must hold requests + 1 non-decreasing offsets from 0 to len(ctx_keys)")
         per = max(1, min(self.pool_max_scores, 0x7fffffff) // max(N, 1))
+        if top_k is not None and self.engine.pool_topk_fused:
+            words = self.engine.pool_topk_words(N, int(top_k))
+            per = max(1, min(4 * self.pool_max_scores // (8 * max(words, 1)), 0x7fffffff))
         out = []
         with self._lock:
             vecs = self._pool_vectors(pool)
