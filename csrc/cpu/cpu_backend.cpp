@@ -1010,6 +1010,29 @@ class CpuBackend final : public Backend {
     ta.score = a.score;
     topk(ta);
   }
+  // PoolSubsetArgs' definition as a plain loop: the fmaf chain over k = 0 ..
+  // Dk + 1; an index outside the pool, or an entry no request owns, is +0.0f
+  void pool_subset(const PoolSubsetArgs& a) override {
+    if (!pool_check(a)) return;
+    const int Dk = pool_dk(a.model), W = pool_width(a.model);
+    const float g = pool_gain(a.model);
+    std::fill(a.pctr, a.pctr + a.M, 0.0f);
+    for (int64_t q = 0; q < a.R; ++q) {
+      const float* c = a.ctx + q * W;
+      const int64_t lo = std::max<int64_t>(a.req_ptr[q], 0);
+      const int64_t hi = std::min<int64_t>(a.req_ptr[q + 1], a.M);
+      for (int64_t e = lo; e < hi; ++e) {
+        const int64_t i = a.index[e];
+        if (i < 0 || i >= a.N) continue;
+        const float* p = a.pool + i * W;
+        float y = 0.0f;
+        for (int k = 0; k < Dk; ++k) y = std::fmaf(g * c[1 + k], p[1 + k], y);
+        y = std::fmaf(c[0], 1.0f, y);
+        y = std::fmaf(1.0f, p[0], y);
+        a.pctr[e] = sigmoid_ref(y);
+      }
+    }
+  }
 
  private:
   std::vector<char> stage_buf_[2];

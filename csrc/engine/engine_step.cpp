@@ -788,4 +788,22 @@ void Engine::pool_topk(const float* ctx, int64_t R, const float* pool, int64_t N
   be_->pool_topk(pa);
 }
 
+void Engine::pool_subset(const float* ctx, int64_t R, const float* pool, int64_t N,
+                         const int32_t* index, const int32_t* req_ptr, int64_t M, float* pctr) {
+  if (!pools()) throw std::runtime_error("pool_subset: needs a frozen LR or FM engine (no fm_mfma)");
+  PoolSubsetArgs pa;
+  pa.ctx = ctx;
+  pa.pool = pool;
+  pa.index = index;
+  pa.req_ptr = req_ptr;
+  pa.R = R;
+  pa.N = N;
+  pa.M = M;
+  pa.pctr = pctr;
+  pa.model = cfg_.model;
+  pa.stage = cfg_.pool_subset_stage < 0 ? pool_width() >= kPoolSubsetStageMin
+                                        : cfg_.pool_subset_stage != 0;
+  be_->pool_subset(pa);
+}
+
 }  // namespace xflow

@@ -480,6 +480,7 @@ class HipBackend final : public Backend {
   void pool_rows(const PoolRowsArgs& a) override { hip::launch_pool_rows(a, stream_); }
   void pool_score(const PoolScoreArgs& a) override { hip::launch_pool_score(a, stream_); }
   void pool_topk(const PoolTopkArgs& a) override { hip::launch_pool_topk(a, stream_); }
+  void pool_subset(const PoolSubsetArgs& a) override { hip::launch_pool_subset(a, stream_); }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

@@ -102,6 +102,8 @@ void launch_pool_rows(const PoolRowsArgs& a, hipStream_t st);    // LR, FM
 void launch_pool_score(const PoolScoreArgs& a, hipStream_t st);  // LR, FM
 // kernels_pool_topk.hip
 void launch_pool_topk(const PoolTopkArgs& a, hipStream_t st);    // LR, FM
+// kernels_pool_subset.hip
+void launch_pool_subset(const PoolSubsetArgs& a, hipStream_t st);  // LR, FM
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

@@ -1094,6 +1094,38 @@ inline bool pool_check(const PoolTopkArgs& a) {
     throw std::runtime_error("pool_topk: null array");
   return true;
 }
+// pool_subset: every request against its own list of pool candidates (HIP:
+// kernels_pool_subset.hip).  index holds all lists one after another, request
+// q owning [req_ptr[q], req_ptr[q + 1]) as in RankArgs and TopkArgs, and
+// pctr[e] = sigmoid_ref(y(ctx row q, pool row index[e])) with y the chain
+// acc = fmaf(A[k], B[k], acc), k = 0 .. Dk + 1 from 0.0f, A = {g * u_q, c_q, 1},
+// B = {u_i, 1, c_i}: an element depends on its own two vectors alone.  An
+// index outside [0, N) reads nothing and scores +0.0f (last in topk's order).
+// vectors of at least this many floats are gathered through LDS by default:
+// measured on an MI355X at 1024 x 4096 entries (profiles/rank_pool_subset.txt),
+// staging is 5 to 7 % behind at 8 floats, even at 12, 3 to 68 % ahead at 20
+// and 7 to 36 % ahead at 36
+constexpr int kPoolSubsetStageMin = 20;
+struct PoolSubsetArgs {
+  const float* ctx = nullptr;        // [R][W] from pool_rows
+  const float* pool = nullptr;       // [N][W] from pool_rows
+  const int32_t* index = nullptr;    // [M] pool indices
+  const int32_t* req_ptr = nullptr;  // [R + 1] non-decreasing, 0 .. M
+  int64_t R = 0, N = 0, M = 0;
+  float* pctr = nullptr;             // [M], aligned with index
+  ModelSpec model;                   // kLR or kFM
+  bool stage = true;                 // HIP, W >= 8: gather a wave's rows through LDS
+};
+inline bool pool_check(const PoolSubsetArgs& a) {
+  pool_check_model(a.model);
+  if (a.R < 0 || a.R > 0x7fffffffll || a.N < 0 || a.N > 0x7fffffffll || a.M < 0 ||
+      a.M > 0x7fffffffll)
+    throw std::runtime_error("pool_subset: requests, candidates and entries are int32 counts");
+  if (a.M == 0) return false;
+  if (!a.index || !a.req_ptr || !a.pctr || (a.R > 0 && !a.ctx) || (a.N > 0 && !a.pool))
+    throw std::runtime_error("pool_subset: null array");
+  return true;
+}
 
 class Backend {
  public:
@@ -1315,6 +1347,8 @@ class Backend {
   virtual void pool_score(const PoolScoreArgs& a) = 0;
   // every context's best k candidates of a pool (PoolTopkArgs)
   virtual void pool_topk(const PoolTopkArgs& a) = 0;
+  // every request against its own list of pool candidates (PoolSubsetArgs)
+  virtual void pool_subset(const PoolSubsetArgs& a) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

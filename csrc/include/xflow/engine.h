@@ -160,6 +160,11 @@ struct EngineConfig {
   // kernel, a multiple of 128; 0: automatic (pool_topk_geom)
   bool pool_topk_fused = true;
   int64_t pool_topk_strip = 0;
+  // pool_subset on HIP gathers a wave's pool rows through LDS when a vector
+  // is wider than one float4 (kernels_pool_subset.hip); false: every lane
+  // loads its own row (the A/B switch; the same bits).  -1: staged from
+  // kPoolSubsetStageMin floats per vector on, where it measured ahead
+  int pool_subset_stage = -1;
 };
 
 // Engine::delta_stats
@@ -582,6 +587,11 @@ class Engine {
   int64_t pool_topk_words(int64_t N, int k) const;
   void pool_topk(const float* ctx, int64_t R, const float* pool, int64_t N, int k, int32_t* idx,
                  float* score);
+  // Every request against its own list of pool candidates (PoolSubsetArgs):
+  // index [M] pool indices, req_ptr [R + 1], pctr [M] aligned with index --
+  // the arrays topk_step takes.  Same engines as pool_score.
+  void pool_subset(const float* ctx, int64_t R, const float* pool, int64_t N, const int32_t* index,
+                   const int32_t* req_ptr, int64_t M, float* pctr);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that

@@ -445,8 +445,10 @@ PYBIND11_MODULE(_xflow_native, m) {
                        bool red_local, bool red_apply, bool serve_fused,
                        int64_t serve_unfused_lo, int64_t serve_unfused_hi,
                        int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi,
-                       bool rank_cross, bool pool_topk_fused, int64_t pool_topk_strip) {
+                       bool rank_cross, bool pool_topk_fused, int64_t pool_topk_strip,
+                       int pool_subset_stage) {
              EngineConfig c;
+             c.pool_subset_stage = pool_subset_stage;
              c.pool_topk_fused = pool_topk_fused;
              c.pool_topk_strip = pool_topk_strip;
              c.rank_cross = rank_cross;
@@ -496,7 +498,7 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256,
            py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1,
            py::arg("rank_cross") = true, py::arg("pool_topk_fused") = true,
-           py::arg("pool_topk_strip") = 0)
+           py::arg("pool_topk_strip") = 0, py::arg("pool_subset_stage") = -1)
       // serving snapshots (docs/DESIGN.md §2)
       .def_property_readonly("frozen", &Engine::frozen)
       .def_property_readonly("serve_fused", &Engine::serve_fused)
@@ -720,6 +722,13 @@ PYBIND11_MODULE(_xflow_native, m) {
               uintptr_t score) {
              e.pool_topk(P<const float>(ctx), R, P<const float>(pool), N, k, P<int32_t>(idx),
                          P<float>(score));
+           },
+           py::call_guard<py::gil_scoped_release>())
+      .def("pool_subset",
+           [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t index,
+              uintptr_t req_ptr, int64_t M, uintptr_t pctr) {
+             e.pool_subset(P<const float>(ctx), R, P<const float>(pool), N,
+                           P<const int32_t>(index), P<const int32_t>(req_ptr), M, P<float>(pctr));
            },
            py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)

@@ -44,7 +44,10 @@ requests on a million candidates, fused alone, and one for a pool sorted
 ascending, its worst case), and
 ``pool_score`` alone with its store bandwidth -- against the only other way to
 serve the shape, ``rank_step`` on the pool's rows repeated once per request
-(where those R x N rows stay under --pool-expand-rows).
+(where those R x N rows stay under --pool-expand-rows).  --pool --pool-subset
+L[,L..] measures ``pool_subset`` instead: R requests with L random pool indices
+each, against ``rank_step`` on the gathered rows, ``pool_score`` over the whole
+pool, and itself with the staged gather off.
 
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
     python tools/serve_bench.py --pool [--model fm --v-dim 32 --fm-math standard]
@@ -410,6 +413,94 @@ def pool_section(a, dev, snap_dir, synth, say):
             say("%d %d %.4f - %.4f - - - does not fit -" % (R, N, build, t))
 
 
+def pool_subset_section(a, dev, snap_dir, synth, say):
+    """Every request against its own --pool-subset candidates of a resident
+    pool: pool_subset against rank_step on the gathered rows and against
+    pool_score over the whole pool, one engine."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    e, C, F, K = p.engine, a.rank_ctx, a.fields, (a.top_k[0] if a.top_k else 100)
+    assert e.pools and e.ranks and 0 < C < F
+    wide = e.pool_width > 4
+    # (pool_subset never reads the table: empty engines serve the two forced settings)
+    st, d = (Engine(p.model, p.optim, EngineConfig(table_log2_cap=16, max_rows=16, max_nnz=1024,
+                                                   pool_subset_stage=on), device=dev)
+             for on in (True, False))
+    say("# ms per call, medians of %d alternating blocks of device-event time, everything on the "
+        "device; every request has its own L random pool indices.  subset: pool_rows on the R "
+        "contexts + pool_subset.  rank_step: the R*L gathered candidate rows of %d keys, the "
+        "gather untimed.  whole_pool: pool_rows on the contexts + pool_score over all N (R*N < "
+        "2^31).  kernel_staged / kernel_direct: pool_subset alone with pool_subset_stage True and "
+        "False (the same kernel twice when a vector is one float4; subset runs the default).  subset_topk: subset + "
+        "topk_step, K = %d" % (a.blocks, F - C, K))
+    say("candidates L requests subset rank_step whole_pool kernel_staged kernel_direct "
+        "subset_topk rank_step/subset whole_pool/subset")
+    gen = SyntheticCriteo(e, a.batch, synth)
+    b = gen.alloc_batch()
+
+    def rows_of(n):  # n rows of F keys, a batch at a time
+        parts = []
+        while sum(len(x) for x in parts) < n:
+            gen.next(out=b)
+            parts.append((b.keys.view(F, a.batch).t() if b.field_major
+                          else b.keys.view(a.batch, F)).clone())
+        return torch.cat(parts)[:n]
+
+    fm = lambda k: Batch(keys=k.t().contiguous().view(-1),
+                         labels=torch.zeros(k.shape[0], device=dev), nnz_per_row=k.shape[1],
+                         field_major=True)
+    for N in (65536, 1048576):
+        cand_keys = rows_of(N)[:, C:].contiguous()
+        pv = e.pool_rows(fm(cand_keys))
+        for L in a.pool_subset:
+            for R in (1, 32, 256):
+                ctx_keys = rows_of(R)[:, :C].contiguous()
+                ctx = Batch(keys=ctx_keys.view(-1), labels=torch.zeros(R, device=dev), nnz_per_row=C)
+                cv = e.pool_rows(ctx)
+                index = torch.randint(0, N, (R * L,), device=dev, dtype=torch.int32)
+                rptr = (torch.arange(R + 1, device=dev) * L).to(torch.int32)
+                cptr = (torch.arange(R + 1, device=dev) * C).to(torch.int32)
+                out, out2 = (torch.empty(R * L, dtype=torch.float32, device=dev) for _ in range(2))
+                rep = fm(cand_keys[index.long()])
+                whole = torch.empty((R, N), dtype=torch.float32, device=dev)
+
+                def subset():
+                    e.pool_rows(ctx, out=cv)
+                    return e.pool_subset(cv, pv, index, rptr, out)
+
+                def whole_pool():
+                    e.pool_rows(ctx, out=cv)
+                    return e.pool_score(cv, pv, whole)
+
+                calls = [subset, lambda: e.rank_step(ctx_keys.view(-1), cptr, rptr, rep, out2),
+                         whole_pool, lambda: st.pool_subset(cv, pv, index, rptr, out),
+                         lambda: d.pool_subset(cv, pv, index, rptr, out2),
+                         lambda: e.topk_step(subset(), rptr, K)]
+                # (the routes score the same rows; the two gathers leave the same bits)
+                assert (subset() - calls[1]()).abs().max().item() < 1e-5
+                assert torch.equal(calls[4]().view(torch.int32), subset().view(torch.int32))
+                rows = whole_pool().view(-1)[index.long() + (torch.arange(R * L, device=dev) // L) * N]
+                assert (subset() - rows).abs().max().item() < 1e-5
+                reps = 200 if R * L <= 1 << 16 else 50
+                m = [median(t) for t in timed_blocks(calls, reps, a.blocks, dev)]
+                say("%d %d %d %.4f %.4f %.4f %.4f %s %.4f %.2f %.2f"
+                    % (N, L, R, m[0], m[1], m[2], m[3], "%.4f" % m[4] if wide else "-", m[5],
+                       m[1] / m[0], m[2] / m[0]))
+                del calls, rep, whole, rows
+                torch.cuda.empty_cache()
+        if wide:  # the two gathers at a size that is throughput, not launch latency
+            R, L = 1024, 4096
+            cv = pv[:R].contiguous()  # (any vectors do)
+            index = torch.randint(0, N, (R * L,), device=dev, dtype=torch.int32)
+            rptr = (torch.arange(R + 1, device=dev) * L).to(torch.int32)
+            out = torch.empty(R * L, dtype=torch.float32, device=dev)
+            m = [median(t) for t in timed_blocks(
+                [lambda: st.pool_subset(cv, pv, index, rptr, out),
+                 lambda: d.pool_subset(cv, pv, index, rptr, out)], 50, a.blocks, dev)]
+            say("# %d %d %d, pool_subset alone, staged / direct: %.4f / %.4f, %.0f / %.0f GB/s of "
+                "gathered rows" % (N, L, R, m[0], m[1], R * L * e.pool_width * 4 / m[0] / 1e6,
+                                   R * L * e.pool_width * 4 / m[1] / 1e6))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -439,6 +530,9 @@ def main() -> int:
     ap.add_argument("--pool", action="store_true", help="the candidate pool section only")
     ap.add_argument("--pool-expand-rows", type=int, default=1 << 25,
                     help="with --pool: rank_step on the repeated rows runs up to this many rows")
+    ap.add_argument("--pool-subset", type=lambda s: [int(x) for x in s.split(",")], default=[],
+                    metavar="L[,L..]", help="with --pool: every request scores its own L random "
+                                            "pool indices (pool_subset) instead")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -476,7 +570,7 @@ def main() -> int:
         del eng
         torch.cuda.empty_cache()
         if a.pool:
-            pool_section(a, dev, snap_dir, synth, say)
+            (pool_subset_section if a.pool_subset else pool_section)(a, dev, snap_dir, synth, say)
             return done()
         if a.rank:
             section = rank_cross_section if a.cross else (topk_section if a.top_k else rank_section)

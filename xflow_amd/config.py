@@ -227,6 +227,14 @@ class EngineConfig:
     # ahead there (profiles/rank_pool_topk.txt: behind up to 32 x 65536 = 2^21,
     # ahead from 256 x 65536 = 2^24); 0: the fused kernel at every size
     pool_topk_fused_min: int = 1 << 23
+    # Engine.pool_subset on HIP, pool vectors wider than one float4: a wave
+    # gathers its 64 pool rows together through LDS, whole rows per load
+    # (docs/DESIGN.md §2); False: every lane loads its own row (the A/B
+    # switch: the same bits either way).  None: staged from 20 floats per
+    # vector on (FM-16 and FM-32 standard), where it measured 3 to 68 % ahead;
+    # direct loads at 8 and 12 floats, where it measured 5 to 7 % behind and
+    # even (profiles/rank_pool_subset.txt)
+    pool_subset_stage: bool | None = None
 
 
 @dataclass

@@ -217,7 +217,9 @@ class Engine:
                            serve_unfused_latent_hi=int(self.cfg.serve_unfused_rows_latent[1]),
                            rank_cross=self.cfg.rank_cross,
                            pool_topk_fused=self.cfg.pool_topk_fused,
-                           pool_topk_strip=int(self.cfg.pool_topk_strip))
+                           pool_topk_strip=int(self.cfg.pool_topk_strip),
+                           pool_subset_stage=-1 if self.cfg.pool_subset_stage is None
+                           else int(bool(self.cfg.pool_subset_stage)))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
         # delta_clear() calls so far: a serving or checkpoint delta is only
@@ -447,6 +449,36 @@ class Engine:
         R, N = p.shape
         req_ptr = torch.arange(R + 1, dtype=torch.int32, device=self.device) * N
         return self.topk_step(p.view(-1), req_ptr, k)
+
+    def pool_subset(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor, index: torch.Tensor,
+                    req_ptr: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Every request against its own list of pool candidates in one launch:
+        ``index`` (int32 [M]) holds all requests' lists of pool indices one
+        after another, request q owning index[req_ptr[q]:req_ptr[q + 1]]
+        (req_ptr int32 [R + 1] from 0 to M, as in rank_step and topk_step).
+        Returns float32 [M], aligned with index -- what topk_step takes: entry e
+        of request q is the model's prediction for context q's keys followed by
+        candidate index[e]'s, from the two pool vectors alone, whatever else the
+        call holds.  An index outside [0, len(pool_vecs)) scores +0.0.  Raises
+        unless ``pools``."""
+        self._pool_vecs("ctx_vecs", ctx_vecs)
+        self._pool_vecs("pool_vecs", pool_vecs)
+        for name, t in (("index", index), ("req_ptr", req_ptr)):
+            if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or \
+                    t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
+        R, M = int(ctx_vecs.shape[0]), int(index.numel())
+        if req_ptr.numel() != R + 1:
+            raise ValueError("req_ptr must hold one offset per context, plus one")
+        if out is None:
+            out = torch.empty(M, dtype=torch.float32, device=self.device)
+        elif out.dtype != torch.float32 or out.device != self.device or \
+                not out.is_contiguous() or tuple(out.shape) != (M,):
+            raise ValueError(f"out must be a contiguous float32 [{M}] tensor on {self.device}")
+        self._sync_stream()
+        self._e.pool_subset(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(), int(pool_vecs.shape[0]),
+                            index.data_ptr(), req_ptr.data_ptr(), M, out.data_ptr())
+        return out
 
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""

@@ -27,6 +27,8 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
                       registers or replaces a resident candidate pool; then
         POST /rank    {"context": [k, ...], "pool": "ads"}  (or "contexts": [[k, ...], ...];
                       optional "top_k")     -> as above, one entry per context with "contexts"
+                      with "pool_index": [i, ...] (under "contexts": [[i, ...], ...]) the
+                      context's own list of pool indices is scored, not the whole pool
         GET  /health
 
 A candidate catalogue that many requests share is uploaded and probed once,
@@ -71,7 +73,7 @@ import math
 import os
 import threading
 import time
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -566,8 +568,52 @@ class Predictor:
             pool.vecs, pool.version = vecs, self._version
         return pool.vecs
 
+    def _rank_pool_subsets(self, ctx_keys, ctx_ptr, pool: Pool, top_k, index, ptr) -> list:
+        """rank_pool_csr with subsets (arguments checked there but for these)."""
+        index = np.asarray(index, dtype=np.int64)
+        ptr = np.asarray(ptr, dtype=np.int64)
+        R, N = len(ctx_ptr) - 1, pool.n
+        if index.ndim != 1 or ptr.ndim != 1 or len(ptr) != R + 1 or ptr[0] != 0 or \
+                ptr[-1] != len(index) or (np.diff(ptr) < 0).any():
+            raise ValueError("subset_ptr must hold requests + 1 non-decreasing offsets from 0 to "
+                             "len(subset_index)")
+        if len(index) and (index.min() < 0 or index.max() >= N):
+            raise ValueError(f"a subset index is outside [0, {N}), the pool's candidates")
+        out = []
+        with self._lock:
+            vecs = self._pool_vectors(pool)
+            q = 0
+            while q < R:
+                # whole requests while their entries stay under pool_max_scores (one at least)
+                q1 = int(np.searchsorted(ptr, ptr[q] + min(self.pool_max_scores, 0x7fffffff),
+                                         side="right")) - 1
+                q1 = min(R, max(q1, q + 1))
+                c0, c1, m0, m1 = int(ctx_ptr[q]), int(ctx_ptr[q1]), int(ptr[q]), int(ptr[q1])
+                if m1 - m0 > 0x7fffffff:
+                    raise ValueError("one request's subset must stay below 2^31 candidates")
+                cv = self.engine.pool_rows(self._csr_batch(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0))
+                rp = ptr[q:q1 + 1] - m0
+                up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32)).to(self.device)
+                idx_d, rp_d = up(index[m0:m1]), up(rp)
+                p = self.engine.pool_subset(cv, vecs, idx_d, rp_d)
+                if top_k is None:
+                    p = p.cpu().numpy()
+                    out += [p[rp[j]:rp[j + 1]] for j in range(q1 - q)]
+                elif m1 == m0:
+                    out += [(np.zeros(0, np.int32), np.zeros(0, np.float32))] * (q1 - q)
+                else:
+                    pos, sc = self.engine.topk_step(p, rp_d, int(top_k))
+                    # positions inside a request's list -> pool indices, on the device
+                    at = (pos.clamp(min=0).long() + rp_d[:-1, None].long()).clamp(max=m1 - m0 - 1)
+                    pi, sc = idx_d[at].cpu().numpy(), sc.cpu().numpy()
+                    n = np.minimum(int(top_k), np.diff(rp))
+                    out += [(pi[j, :n[j]], sc[j, :n[j]]) for j in range(q1 - q)]
+                q = q1
+        return out
+
     def rank_pool_csr(self, ctx_keys: np.ndarray, ctx_ptr: np.ndarray, pool: Pool,
-                      top_k: Optional[int] = None) -> list:
+                      top_k: Optional[int] = None, subset_index: Optional[np.ndarray] = None,
+                      subset_ptr: Optional[np.ndarray] = None) -> list:
         """R contexts (CSR: ctx_keys u64, ctx_ptr R + 1 offsets) against every
         candidate of ``pool``.  Returns one float32 array of len(pool) scores
         per context -- the model's prediction for the context's keys followed
@@ -576,7 +622,16 @@ class Predictor:
         The contexts are scored in chunks of whole requests whose scores stay
         under ``pool_max_scores`` floats; with ``top_k`` on an engine whose
         pool_topk is fused no scores are stored, and a chunk is bounded by the
-        kernel's scratch instead (at most 4 * pool_max_scores bytes)."""
+        kernel's scratch instead (at most 4 * pool_max_scores bytes).
+
+        ``subset_index`` / ``subset_ptr`` (together): request q is scored
+        against its own list of pool indices subset_index[subset_ptr[q]:
+        subset_ptr[q + 1]] only (Engine.pool_subset) and gets one score per
+        entry of its list, in the list's order; with ``top_k`` the pair holds
+        the pool indices of the best n = min(top_k, len(list)) entries, equal
+        scores in ascending position in the list.  An index outside [0,
+        len(pool)) raises ValueError before anything is uploaded.  A chunk is
+        whole requests whose entries stay under ``pool_max_scores``."""
         if top_k is not None and not (isinstance(top_k, (int, np.integer)) and 1 <= top_k <= 1024):
             raise ValueError("top_k must be an integer from 1 to 1024")
         ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
@@ -585,6 +640,10 @@ class Predictor:
         if ctx_ptr.ndim != 1 or R < 0 or ctx_ptr[0] != 0 or ctx_ptr[-1] != len(ctx_keys) or \
                 (np.diff(ctx_ptr) < 0).any():
             raise ValueError("ctx_ptr must hold requests + 1 non-decreasing offsets from 0 to len(ctx_keys)")
+        if (subset_index is None) != (subset_ptr is None):
+            raise ValueError("give 'subset_index' and 'subset_ptr' together")
+        if subset_index is not None:
+            return self._rank_pool_subsets(ctx_keys, ctx_ptr, pool, top_k, subset_index, subset_ptr)
         per = max(1, min(self.pool_max_scores, 0x7fffffff) // max(N, 1))
         if top_k is not None and self.engine.pool_topk_fused:
             words = self.engine.pool_topk_words(N, int(top_k))
@@ -608,12 +667,19 @@ class Predictor:
         return out
 
     def rank_pool(self, contexts: Sequence[Sequence[int]], pool: Pool,
-                  top_k: Optional[int] = None) -> list:
+                  top_k: Optional[int] = None,
+                  subsets: Optional[Sequence[Sequence[int]]] = None) -> list:
         """rank_pool_csr from lists: contexts[q] the (already hashed) u64 keys
-        of request q's context."""
-        rp = np.concatenate([[0], np.cumsum([len(c) for c in contexts])]).astype(np.int64)
-        return self.rank_pool_csr(np.array([k for c in contexts for k in c], dtype=np.uint64), rp,
-                                  pool, top_k)
+        of request q's context, ``subsets[q]`` its own list of pool indices."""
+        ptr = lambda ls: np.concatenate([[0], np.cumsum([len(x) for x in ls])]).astype(np.int64)
+        sub = {}
+        if subsets is not None:
+            if len(subsets) != len(contexts):
+                raise ValueError("give one list of pool indices per context")
+            sub = dict(subset_index=np.array([i for s in subsets for i in s], dtype=np.int64),
+                       subset_ptr=ptr(subsets))
+        return self.rank_pool_csr(np.array([k for c in contexts for k in c], dtype=np.uint64),
+                                  ptr(contexts), pool, top_k, **sub)
 
 
 # -------------------------------------------------------------------- service
@@ -672,18 +738,30 @@ def make_app(pred: Predictor):
                            context_fields=(Optional[list[int]], None),
                            candidate_fields=(Optional[list[list[int]]], None),
                            top_k=(Optional[int], None), pool=(Optional[str], None),
-                           contexts=(Optional[list[list[int]]], None))
+                           contexts=(Optional[list[list[int]]], None),
+                           pool_index=(Optional[Union[list[int], list[list[int]]]], None))
 
     def rank_pool(req):
         """"pool": a registered pool in place of "candidates", under one
-        "context" or many "contexts" (then one entry per context)."""
+        "context" or many "contexts" (then one entry per context).
+        "pool_index": the context's own list of pool indices (one list per
+        context under "contexts"); the scores, or with "top_k" the best, are
+        of that list alone."""
         if req.candidates is not None or (req.context is None) == (req.contexts is None):
             raise HTTPException(400, "with 'pool' give 'context' or 'contexts', and no 'candidates'")
         if req.pool not in pools:
             raise HTTPException(404, f"no pool named {req.pool!r}: POST /pool first")
+        subsets = req.pool_index
+        if subsets is not None:
+            nested = any(isinstance(s, list) for s in subsets)
+            if req.context is not None and not nested:
+                subsets = [subsets]
+            elif req.context is not None or not all(isinstance(s, list) for s in subsets):
+                raise HTTPException(400, "'pool_index' is a list under 'context' and a list of "
+                                         "lists under 'contexts'")
         try:
             got = pred.rank_pool(req.contexts if req.context is None else [req.context],
-                                 pools[req.pool], req.top_k)
+                                 pools[req.pool], req.top_k, subsets)
         except ValueError as e:
             raise HTTPException(400, str(e))
         if req.top_k is not None:
