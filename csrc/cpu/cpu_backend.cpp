@@ -936,12 +936,25 @@ class CpuBackend final : public Backend {
     const bool fm = a.model.kind == kFM, standard = a.model.fm_math == kFmStandard;
     const int D = fm ? a.model.v_dim : 0, W = pool_width(a.model);
     std::vector<float> vs((size_t)D);
+    const CrossSpec& x = a.spec;
+    const CrossMap m = cross_map(x);
+    const int OW = cross_ops_width(m);
     for (int64_t r = 0; r < a.batch.rows; ++r) {
       const RowSpan rs = row_span(a.batch, r);
       float wx = 0.0f, vp = 0.0f;
       std::fill(vs.begin(), vs.end(), 0.0f);
-      for (int j = 0; j < rs.len; ++j) {
-        const u64 key = sanitize_key(a.batch.keys[rs.at(j)]);
+      // the row's occurrences, then (fold) its complete crosses in spec order
+      u64 xk[kMaxCrosses];
+      int nx = 0;
+      if (x.n != 0) {
+        u64* ops = a.ops + r * OW;
+        row_operands(a.batch, r, m, ops);
+        for (int c = 0; a.fold && c < x.n; ++c)
+          if ((ops[0] & cross_need(x, m, c)) == cross_need(x, m, c))
+            xk[nx++] = pair_cross_key(x, m, c, ops, nullptr);
+      }
+      for (int j = 0; j < rs.len + nx; ++j) {
+        const u64 key = sanitize_key(j < rs.len ? a.batch.keys[rs.at(j)] : xk[j - rs.len]);
         bool claimed = false;
         const u32 slot = probe(t, key, false, claimed);
         const u32* sp = slot == kNoSlot ? nullptr : t.words + (u64)slot * L.stride;
@@ -1029,12 +1042,55 @@ class CpuBackend final : public Backend {
         for (int k = 0; k < Dk; ++k) y = std::fmaf(g * c[1 + k], p[1 + k], y);
         y = std::fmaf(c[0], 1.0f, y);
         y = std::fmaf(1.0f, p[0], y);
+        if (a.spec.n != 0) y = pair_crosses(a, q, i, y);
         a.pctr[e] = sigmoid_ref(y);
       }
     }
   }
 
  private:
+  // PoolSubsetArgs with a spec: the incomplete crosses of the pair (q, i), in
+  // spec order, probed into sums of their own and joined to the base chain y0
+  float pair_crosses(const PoolSubsetArgs& a, int64_t q, int64_t i, float y0) {
+    const TableView& t = a.table;
+    const TableLayout& L = t.L;
+    const CrossSpec& x = a.spec;
+    const CrossMap m = cross_map(x);
+    const int OW = cross_ops_width(m), W = pool_width(a.model);
+    const bool fm = a.model.kind == kFM, standard = a.model.fm_math == kFmStandard;
+    const int D = fm ? a.model.v_dim : 0;
+    const u64 *qo = a.ctx_ops + q * OW, *no = a.pool_ops + i * OW;
+    std::vector<float> X((size_t)D, 0.0f);
+    float xw = 0.0f, xp = 0.0f;
+    for (int c = 0; c < x.n; ++c) {
+      const u64 need = cross_need(x, m, c);
+      if ((qo[0] & need) == need) continue;  // (inside the context vector)
+      const u64 key = pair_cross_key(x, m, c, qo, no);
+      bool claimed = false;
+      const u32 slot = probe(t, key, false, claimed);
+      const u32* sp = slot == kNoSlot ? nullptr : t.words + (u64)slot * L.stride;
+      auto w = [&](int p) {
+        return sp ? slot_weight(sp, key, p, L, a.opt) : absent_weight(key, p, L, a.opt);
+      };
+      xw += w(0);
+      for (int k = 0; k < D; ++k) {
+        const float v = w(1 + k);
+        X[(size_t)k] += v;
+        xp += v * v;
+      }
+    }
+    if (!fm) return y0 + xw;
+    const float *cv = a.ctx + q * W, *pv = a.pool + i * W;
+    float sq = 0.0f, sx = 0.0f, t2 = 0.0f;
+    for (int k = 0; k < D; ++k) {
+      sq += X[(size_t)k] * X[(size_t)k];
+      sx += X[(size_t)k];
+      if (standard) t2 = std::fmaf(cv[1 + k] + pv[1 + k], X[(size_t)k], t2);
+    }
+    if (standard) return (y0 + (xw + 0.5f * (sq - xp))) + t2;
+    return (y0 + (xw + (sx * sx - xp))) + (2.0f * (cv[1] + pv[1])) * sx;
+  }
+
   std::vector<char> stage_buf_[2];
   size_t mm_bytes_ = 0, committed_ = 0, fb_bytes_ = 0;
 };

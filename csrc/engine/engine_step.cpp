@@ -735,9 +735,14 @@ bool Engine::pools() const {
   return frozen() && (m.kind == kLR || (m.kind == kFM && !(m.fm_math == kFmStandard && m.fm_mfma)));
 }
 
-void Engine::pool_rows(const BatchView& b, float* vec) {
+void Engine::pool_rows(const BatchView& b, float* vec, const CrossSpec& spec, u64* ops, bool fold) {
   if (!pools()) throw std::runtime_error("pool_rows: needs a frozen LR or FM engine (no fm_mfma)");
+  if (spec.n != 0 && !cfg_.rank_cross)
+    throw std::runtime_error("pool_rows: crosses are switched off (EngineConfig::rank_cross)");
   PoolRowsArgs pa;
+  pa.spec = spec;
+  pa.ops = ops;
+  pa.fold = fold;
   pa.table = table_;
   pa.batch = b;
   pa.vec = vec;
@@ -789,9 +794,19 @@ void Engine::pool_topk(const float* ctx, int64_t R, const float* pool, int64_t N
 }
 
 void Engine::pool_subset(const float* ctx, int64_t R, const float* pool, int64_t N,
-                         const int32_t* index, const int32_t* req_ptr, int64_t M, float* pctr) {
+                         const int32_t* index, const int32_t* req_ptr, int64_t M, float* pctr,
+                         const CrossSpec& spec, const u64* ctx_ops, const u64* pool_ops) {
   if (!pools()) throw std::runtime_error("pool_subset: needs a frozen LR or FM engine (no fm_mfma)");
+  if (spec.n != 0 && !cfg_.rank_cross)
+    throw std::runtime_error("pool_subset: crosses are switched off (EngineConfig::rank_cross)");
   PoolSubsetArgs pa;
+  if (spec.n != 0) {
+    pa.spec = spec;
+    pa.ctx_ops = ctx_ops;
+    pa.pool_ops = pool_ops;
+    pa.table = table_;
+    pa.opt = cfg_.opt;
+  }
   pa.ctx = ctx;
   pa.pool = pool;
   pa.index = index;

@@ -104,6 +104,10 @@ void launch_pool_score(const PoolScoreArgs& a, hipStream_t st);  // LR, FM
 void launch_pool_topk(const PoolTopkArgs& a, hipStream_t st);    // LR, FM
 // kernels_pool_subset.hip
 void launch_pool_subset(const PoolSubsetArgs& a, hipStream_t st);  // LR, FM
+// kernels_pool_cross.hip (launch_pool_rows' and launch_pool_subset's kernels for
+// a.spec.n > 0; both have checked their arguments)
+void launch_pool_rows_cross(const PoolRowsArgs& a, hipStream_t st);
+void launch_pool_subset_cross(const PoolSubsetArgs& a, hipStream_t st);
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

@@ -48,18 +48,8 @@
 namespace xflow {
 namespace hip {
 
-constexpr int kPoolRowWaves = 4;   // rows per workgroup of the row kernels
 constexpr int kPoolTileN = 128;    // candidates per workgroup of k_pool_score
 constexpr int kPoolTargetGrid = 2048;  // workgroups wanted before gridDim.y stops growing
-
-// this lane's share of row rs: occurrences lane, lane + 64, ..
-__device__ __forceinline__ RowSpan pool_lane_span(const RowSpan& rs, int lane) {
-  RowSpan s;
-  s.base = rs.base + (int64_t)lane * rs.step;
-  s.step = rs.step * kWave;
-  s.len = lane < rs.len ? (rs.len - lane + kWave - 1) / kWave : 0;
-  return s;
-}
 
 __global__ void __launch_bounds__(kPoolRowWaves * kWave) k_pool_rows_lr(PoolRowsArgs a) {
   const int lane = threadIdx.x % kWave;
@@ -83,24 +73,7 @@ __global__ void __launch_bounds__(kPoolRowWaves * kWave) k_pool_rows_fm(PoolRows
   float wx = 0.0f, vp = 0.0f;
   rank_fm_sum<D>(a.table, a.opt, a.batch.keys, pool_lane_span(row_span(a.batch, r), lane), wx, vs,
                  vp);
-  wx = rank_allsum(wx);
-  vp = rank_allsum(vp);
-#pragma unroll
-  for (int k = 0; k < D; ++k) vs[k] = rank_allsum(vs[k]);
-  float out = lane == 0 ? rank_fm_finish<D>(a.model.fm_math, wx, vs, vp) : 0.0f;
-  const bool standard = a.model.fm_math == kFmStandard;
-  if (standard) {
-#pragma unroll
-    for (int k = 0; k < D; ++k)
-      if (lane == 1 + k) out = vs[k];
-  } else {
-    float vsum = 0.0f;  // (rank_fm_finish's own sum)
-#pragma unroll
-    for (int k = 0; k < D; ++k) vsum = __fadd_rn(vsum, vs[k]);
-    if (lane == 1) out = vsum;
-  }
-  const int W = (1 + (standard ? D : 1) + 3) & ~3;
-  if (lane < W) a.vec[r * W + lane] = out;
+  pool_rows_fm_store<D>(a, r, lane, wx, vs, vp);
 }
 
 template <int KP>
@@ -141,6 +114,7 @@ __global__ void __launch_bounds__(kBlock) k_pool_score(PoolScoreArgs a, int W, i
 
 void launch_pool_rows(const PoolRowsArgs& a, hipStream_t st) {
   if (!pool_check(a)) return;
+  if (a.spec.n != 0) return launch_pool_rows_cross(a, st);  // kernels_pool_cross.hip
   const dim3 g((unsigned)((a.batch.rows + kPoolRowWaves - 1) / kPoolRowWaves));
   const dim3 blk(kPoolRowWaves * kWave);
   if (a.model.kind == kLR) {

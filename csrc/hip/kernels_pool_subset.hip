@@ -49,14 +49,6 @@
 namespace xflow {
 namespace hip {
 
-constexpr int pool_subset_width(int KP) { return (KP + 2) & ~3; }  // pool_width of KP's models
-
-// float4 slot of part p of row r in a wave's region
-template <int Q>
-__device__ __forceinline__ int pool_subset_slot(int r, int p) {
-  return r * Q + (Q % 2 == 0 ? p ^ ((r >> 3) & (Q - 1)) : p);
-}
-
 template <int KP, bool STAGE>
 __global__ void __launch_bounds__(kBlock) k_pool_subset(PoolSubsetArgs a, int dk, float g) {
   constexpr int W = pool_subset_width(KP), Q = W / 4;
@@ -134,6 +126,7 @@ __global__ void __launch_bounds__(kBlock) k_pool_subset(PoolSubsetArgs a, int dk
 
 void launch_pool_subset(const PoolSubsetArgs& a, hipStream_t st) {
   if (!pool_check(a)) return;
+  if (a.spec.n != 0) return launch_pool_subset_cross(a, st);  // kernels_pool_cross.hip
   const int Dk = pool_dk(a.model);
   const float g = pool_gain(a.model);
   const int KPr = (Dk + 2 + 1) & ~1;

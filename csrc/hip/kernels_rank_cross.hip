@@ -56,14 +56,10 @@
 namespace xflow {
 namespace hip {
 
-constexpr int kRankSlots = kMaxCrosses * kMaxCrossArity;
+constexpr int kRankSlots = kCrossSlots;
 static_assert(kRankSlots == kWave, "one operand slot per lane");
 
-struct RankCrossMap {
-  int nu = 0;                              // distinct operand fields
-  int32_t ufield[kRankSlots] = {};         // [nu]
-  unsigned char slot_u[kRankSlots] = {};   // slot 4 c + k -> its field's index in ufield
-};
+using RankCrossMap = CrossMap;  // backend.h: the spec's distinct operand fields
 
 struct RankCrossLds {
   u64* cand;    // [nu][64] candidate operands
@@ -290,14 +286,7 @@ void launch_rank_cross(const RankArgs& a, hipStream_t st) {
   check_cross_spec(x, "rank");
   if ((a.ctx_nnz > 0 && !a.ctx_fgid) || (b.nnz > 0 && !b.fgid))
     throw std::invalid_argument("rank: crosses need the field ids of the contexts and the candidates");
-  RankCrossMap m;
-  for (int c = 0; c < x.n; ++c)
-    for (int k = 0; k < x.arity[c]; ++k) {
-      int u = 0;
-      while (u < m.nu && m.ufield[u] != x.field[c][k]) ++u;
-      if (u == m.nu) m.ufield[m.nu++] = x.field[c][k];
-      m.slot_u[4 * c + k] = (unsigned char)u;
-    }
+  const RankCrossMap m = cross_map(x);
   const size_t lds = rank_cross_lds_bytes(m.nu, x.n);
   const dim3 g((unsigned)((b.rows + kServeBlock - 1) / kServeBlock)), blk(kServeBlock);
   if (a.model.kind == kLR) {

@@ -940,6 +940,70 @@ XF_HD void row_cross_keys(const BatchView& b, int64_t r, const CrossSpec& x, u64
   }
 }
 
+// The distinct operand fields of a spec (both backends, the rank-cross kernels
+// and the pool kernels: one definition of "distinct field u").  An operand
+// slot is 4 c + k (cross c, operand k); ufield lists the spec's fields in the
+// order of their first slot, nu <= 64 of them, and slot_u maps a slot to its
+// field's index there.  Passed to kernels by value.
+constexpr int kCrossSlots = kMaxCrosses * kMaxCrossArity;
+struct CrossMap {
+  int nu = 0;                              // distinct operand fields
+  int32_t ufield[kCrossSlots] = {};        // [nu]
+  unsigned char slot_u[kCrossSlots] = {};  // slot 4 c + k -> its field's index in ufield
+};
+inline CrossMap cross_map(const CrossSpec& x) {
+  CrossMap m;
+  for (int c = 0; c < x.n; ++c)
+    for (int k = 0; k < x.arity[c]; ++k) {
+      int u = 0;
+      while (u < m.nu && m.ufield[u] != x.field[c][k]) ++u;
+      if (u == m.nu) m.ufield[m.nu++] = x.field[c][k];
+      m.slot_u[kMaxCrossArity * c + k] = (unsigned char)u;
+    }
+  return m;
+}
+// bit u: cross c has distinct field u among its operands
+XF_HD u64 cross_need(const CrossSpec& x, const CrossMap& m, int c) {
+  u64 need = 0;
+  for (int k = 0; k < x.arity[c]; ++k) need |= 1ull << m.slot_u[kMaxCrossArity * c + k];
+  return need;
+}
+// Operand rows (pool_rows with a spec): 1 + nu u64 words per batch row.  Word
+// 0 is the `seen` mask, bit u set when the row has distinct field u at all;
+// word 1 + u is the raw key of the field's first occurrence, ~0 when the row
+// lacks the field.  A first occurrence whose key is ~0 stays the operand: the
+// mask decides, not the value.
+XF_HD int cross_ops_width(const CrossMap& m) { return 1 + m.nu; }
+XF_HD void row_operands(const BatchView& b, int64_t r, const CrossMap& m, u64* out) {
+  const RowSpan s = row_span(b, r);
+  u64 seen = 0;
+  for (int u = 0; u < m.nu; ++u) out[1 + u] = ~0ull;
+  for (int j = 0; j < s.len; ++j)
+    for (int u = 0; u < m.nu; ++u)
+      if (b.fgid[s.at(j)] == m.ufield[u] && !((seen >> u) & 1ull)) {
+        seen |= 1ull << u;
+        out[1 + u] = b.keys[s.at(j)];
+      }
+  out[0] = seen;
+}
+// Cross c of the pair (context operand row q, candidate operand row n):
+// operand i is q's key if q has the field, else n's if n has it, else ~0.
+// n == null: the row's own cross (a complete one: every field is in q's mask).
+XF_HD u64 pair_cross_key(const CrossSpec& x, const CrossMap& m, int c, const u64* q,
+                         const u64* n) {
+  u64 ops[kMaxCrossArity];
+  for (int k = 0; k < kMaxCrossArity; ++k) {
+    u64 v = ~0ull;
+    if (k < x.arity[c]) {
+      const int u = m.slot_u[kMaxCrossArity * c + k];
+      if ((q[0] >> u) & 1ull) v = q[1 + u];
+      else if (n && ((n[0] >> u) & 1ull)) v = n[1 + u];
+    }
+    ops[k] = v;
+  }
+  return cross_key(x.field[c], ops, x.arity[c]);
+}
+
 // Candidate ranking from a frozen LR or FM table (Backend::rank, HIP:
 // kernels_rank.hip): R requests, each one context (CSR: ctx_ptr into
 // ctx_keys) scored against the candidate rows [req_ptr[q], req_ptr[q + 1]) of
@@ -1001,6 +1065,16 @@ struct PoolRowsArgs {
   float* vec = nullptr;            // [batch.rows][pool_width(model)]
   ModelSpec model;                 // kLR or kFM
   OptSpec opt;
+  // Crossed models (HIP: kernels_pool_cross.hip).  spec.n == 0: none of this
+  // is read.  With a spec, batch.fgid is required and ops receives the rows'
+  // operand rows (row_operands).  fold == false (pool rows): vec is the
+  // uncrossed row's vector, the same bits.  fold == true (context rows): every
+  // cross whose fields are all in the row's `seen` mask is hashed from the
+  // row's own operands and its probe joins the row's sums (wx, vs, vp) after
+  // the row's occurrences, in spec order, before the model's finish.
+  CrossSpec spec;
+  u64* ops = nullptr;              // [batch.rows][1 + nu]
+  bool fold = false;
 };
 // pool_score: pctr[q * N + i] = sigmoid_ref(y(ctx row q, pool row i)); an
 // element depends on its own two rows alone.
@@ -1027,6 +1101,11 @@ inline bool pool_check(const PoolRowsArgs& a) {
   if (b.rows == 0) return false;
   if (!a.vec || (b.nnz > 0 && !b.keys) || (!b.row_ptr && b.nnz != b.rows * b.nnz_per_row))
     throw std::runtime_error("pool_rows: null array or a fixed-width batch of another size");
+  if (a.spec.n != 0) {
+    check_cross_spec(a.spec, "pool_rows");
+    if (!a.ops || (b.nnz > 0 && !b.fgid))
+      throw std::invalid_argument("pool_rows: crosses need the rows' field ids and an operand array");
+  }
   return true;
 }
 inline bool pool_check(const PoolScoreArgs& a) {
@@ -1115,6 +1194,23 @@ struct PoolSubsetArgs {
   float* pctr = nullptr;             // [M], aligned with index
   ModelSpec model;                   // kLR or kFM
   bool stage = true;                 // HIP, W >= 8: gather a wave's rows through LDS
+  // Crossed models (HIP: kernels_pool_cross.hip).  spec.n == 0: none of this
+  // is read.  ctx holds folded vectors (PoolRowsArgs::fold), pool unfolded
+  // ones, ctx_ops / pool_ops their operand rows.  For entry e = (q, n), a
+  // cross whose distinct fields are all in q's `seen` mask is already inside
+  // the context vector and is skipped; every other cross, in spec order, is
+  // hashed (pair_cross_key) and its table entry -- an absent key reads the
+  // source optimiser's init -- joins xw = sum w_c, X[k] = sum v_c[k] and
+  // xp = sum v_c[k]^2, summed from 0.0f apart from the base chain y0.  Then
+  //   LR                  y = y0 + xw
+  //   FM, standard math   y = y0 + (xw + 0.5 (sum_k X[k]^2 - xp)) + sum_k (u_q[k] + u_n[k]) X[k]
+  //   FM, reference math  y = y0 + (xw + (sx^2 - xp)) + 2 (u_q + u_n) sx,  sx = sum_k X[k]
+  // and pctr[e] = sigmoid_ref(y).
+  CrossSpec spec;
+  const u64* ctx_ops = nullptr;      // [R][1 + nu]
+  const u64* pool_ops = nullptr;     // [N][1 + nu]
+  TableView table;                   // kFrozen, TableLayout::make(model, opt)
+  OptSpec opt;
 };
 inline bool pool_check(const PoolSubsetArgs& a) {
   pool_check_model(a.model);
@@ -1124,6 +1220,15 @@ inline bool pool_check(const PoolSubsetArgs& a) {
   if (a.M == 0) return false;
   if (!a.index || !a.req_ptr || !a.pctr || (a.R > 0 && !a.ctx) || (a.N > 0 && !a.pool))
     throw std::runtime_error("pool_subset: null array");
+  if (a.spec.n != 0) {
+    const TableLayout& L = a.table.L;
+    check_cross_spec(a.spec, "pool_subset");
+    if (L.opt != kFrozen || L.has_flag || L.sp != 1 || L.P != a.model.P() ||
+        L.p_w != a.model.p_w() || L.stride != ((2 + L.P + 3) & ~3))
+      throw std::runtime_error("pool_subset: crosses need the model's frozen table");
+    if ((a.R > 0 && !a.ctx_ops) || (a.N > 0 && !a.pool_ops))
+      throw std::invalid_argument("pool_subset: crosses need both sides' operand rows");
+  }
   return true;
 }
 

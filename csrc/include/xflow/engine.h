@@ -575,7 +575,13 @@ class Engine {
   // Stream-ordered, no sync.
   bool pools() const;
   int pool_width() const { return xflow::pool_width(cfg_.model); }
-  void pool_rows(const BatchView& b, float* vec);
+  // spec.n > 0 (a crossed model; needs b.fgid and EngineConfig::rank_cross):
+  // ops [b.rows][pool_ops_width(spec)] receives the rows' operand rows, and
+  // with fold -- context rows -- the crosses a row completes on its own join
+  // its vector (PoolRowsArgs); pool rows are built without fold.
+  static int pool_ops_width(const CrossSpec& spec) { return cross_ops_width(cross_map(spec)); }
+  void pool_rows(const BatchView& b, float* vec, const CrossSpec& spec = CrossSpec(),
+                 u64* ops = nullptr, bool fold = false);
   void pool_score(const float* ctx, int64_t R, const float* pool, int64_t N, float* pctr);
   // Every context's best k of the pool (PoolTopkArgs): idx / score [R][k] as
   // topk_step leaves them for pool_score's scores, with no [R][N] array and no
@@ -590,8 +596,13 @@ class Engine {
   // Every request against its own list of pool candidates (PoolSubsetArgs):
   // index [M] pool indices, req_ptr [R + 1], pctr [M] aligned with index --
   // the arrays topk_step takes.  Same engines as pool_score.
+  // spec.n > 0: ctx are folded vectors, pool unfolded ones, ctx_ops / pool_ops
+  // their operand rows from pool_rows; every pair's incomplete crosses are
+  // hashed and probed inside the kernel (PoolSubsetArgs).
   void pool_subset(const float* ctx, int64_t R, const float* pool, int64_t N, const int32_t* index,
-                   const int32_t* req_ptr, int64_t M, float* pctr);
+                   const int32_t* req_ptr, int64_t M, float* pctr,
+                   const CrossSpec& spec = CrossSpec(), const u64* ctx_ops = nullptr,
+                   const u64* pool_ops = nullptr);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that

@@ -707,8 +707,19 @@ PYBIND11_MODULE(_xflow_native, m) {
       .def_property_readonly("pools", &Engine::pools)
       .def_property_readonly("pool_width", &Engine::pool_width)
       .def("pool_rows",
-           [](Engine& e, const BatchView& b, uintptr_t vec) { e.pool_rows(b, P<float>(vec)); },
-           py::call_guard<py::gil_scoped_release>())
+           [](Engine& e, const BatchView& b, uintptr_t vec,
+              const std::vector<std::vector<int32_t>>& crosses, uintptr_t ops, bool fold) {
+             const CrossSpec spec = crosses.empty() ? CrossSpec() : cross_spec_from(crosses, "pool_rows");
+             py::gil_scoped_release nogil;
+             e.pool_rows(b, P<float>(vec), spec, P<u64>(ops), fold);
+           },
+           py::arg("batch"), py::arg("vec"),
+           py::arg("crosses") = std::vector<std::vector<int32_t>>(), py::arg("ops") = 0,
+           py::arg("fold") = false)
+      .def_static("pool_ops_width",
+                  [](const std::vector<std::vector<int32_t>>& crosses) {
+                    return Engine::pool_ops_width(cross_spec_from(crosses, "pool_ops_width"));
+                  })
       .def("pool_score",
            [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t pctr) {
              e.pool_score(P<const float>(ctx), R, P<const float>(pool), N, P<float>(pctr));
@@ -726,11 +737,19 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("pool_subset",
            [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t index,
-              uintptr_t req_ptr, int64_t M, uintptr_t pctr) {
+              uintptr_t req_ptr, int64_t M, uintptr_t pctr,
+              const std::vector<std::vector<int32_t>>& crosses, uintptr_t ctx_ops,
+              uintptr_t pool_ops) {
+             const CrossSpec spec = cross_spec_from(crosses, "pool_subset");
+             py::gil_scoped_release nogil;
              e.pool_subset(P<const float>(ctx), R, P<const float>(pool), N,
-                           P<const int32_t>(index), P<const int32_t>(req_ptr), M, P<float>(pctr));
+                           P<const int32_t>(index), P<const int32_t>(req_ptr), M, P<float>(pctr),
+                           spec, P<const u64>(ctx_ops), P<const u64>(pool_ops));
            },
-           py::call_guard<py::gil_scoped_release>())
+           py::arg("ctx"), py::arg("R"), py::arg("pool"), py::arg("N"), py::arg("index"),
+           py::arg("req_ptr"), py::arg("M"), py::arg("pctr"),
+           py::arg("crosses") = std::vector<std::vector<int32_t>>(), py::arg("ctx_ops") = 0,
+           py::arg("pool_ops") = 0)
       .def("slices_of", &Engine::slices_of)
       .def_static("slice_groups", &Engine::slice_groups)
       .def_static("group_slices", &Engine::group_slices)

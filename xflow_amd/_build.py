@@ -54,7 +54,8 @@ _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"kernels_rank.hip": _NO_PACKED_FP32, "kernels_rank_cross.hip": _NO_PACKED_FP32,
                   "kernels_topk.hip": _NO_PACKED_FP32, "kernels_pool.hip": _NO_PACKED_FP32,
                   "kernels_pool_topk.hip": _NO_PACKED_FP32,
-                  "kernels_pool_subset.hip": _NO_PACKED_FP32}
+                  "kernels_pool_subset.hip": _NO_PACKED_FP32,
+                  "kernels_pool_cross.hip": _NO_PACKED_FP32}
 
 HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/engine_step.cpp",
                 "engine/engine_sharded.cpp", "engine/engine_table.cpp", "engine/engine_input.cpp",

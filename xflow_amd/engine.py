@@ -380,21 +380,42 @@ class Engine:
         pool_topk against n candidates needs."""
         return int(self._e.pool_topk_words(int(n), int(k)))
 
-    def pool_rows(self, batch: Batch, out: torch.Tensor | None = None) -> torch.Tensor:
+    def pool_ops_width(self, crosses) -> int:
+        """int64 words of an operand row under ``crosses``: the mask of the
+        distinct operand fields a row has, then the first key of each."""
+        return int(self._e.pool_ops_width([list(c) for c in check_crosses(crosses)]))
+
+    def pool_rows(self, batch: Batch, out: torch.Tensor | None = None, crosses=None,
+                  fold: bool = False):
         """The rows of ``batch`` (any layout; labels ignored) as pool vectors,
         float32 [rows, pool_width]: the part of the model's logit a row
         contributes when it is one side of a (context, candidate) pair.  A
         vector depends on its row's keys in their order alone.  Run once per
         model version on a pool and on every call on the contexts.  Raises
-        unless ``pools``."""
+        unless ``pools``.
+
+        ``crosses`` (a crossed model; needs ``batch.fgid`` and
+        EngineConfig.rank_cross): returns ``(vecs, ops)``, ops int64 [rows,
+        pool_ops_width(crosses)] the rows' operand rows for pool_subset.
+        ``fold=True`` (context rows): the crosses whose fields all occur in the
+        row join its vector; pool rows keep the uncrossed vector."""
         batch.check(self.device)
         W = self.pool_width
         if out is None:
             out = torch.empty((batch.rows, W), dtype=torch.float32, device=self.device)
         self._pool_vecs("out", out, batch.rows)
+        if not crosses:
+            self._sync_stream()
+            self._e.pool_rows(batch.view(), out.data_ptr())
+            return out
+        crosses = [list(c) for c in check_crosses(crosses)]
+        if batch.fgid is None:
+            raise ValueError("pool_rows: crosses need the rows' field ids (batch.fgid)")
+        ops = torch.empty((batch.rows, self.pool_ops_width(crosses)), dtype=torch.int64,
+                          device=self.device)
         self._sync_stream()
-        self._e.pool_rows(batch.view(), out.data_ptr())
-        return out
+        self._e.pool_rows(batch.view(), out.data_ptr(), crosses, ops.data_ptr(), bool(fold))
+        return out, ops
 
     def _pool_vecs(self, name: str, t: torch.Tensor, rows: int | None = None) -> None:
         if t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous() or \
@@ -451,7 +472,9 @@ class Engine:
         return self.topk_step(p.view(-1), req_ptr, k)
 
     def pool_subset(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor, index: torch.Tensor,
-                    req_ptr: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+                    req_ptr: torch.Tensor, out: torch.Tensor | None = None, crosses=None,
+                    ctx_ops: torch.Tensor | None = None,
+                    pool_ops: torch.Tensor | None = None) -> torch.Tensor:
         """Every request against its own list of pool candidates in one launch:
         ``index`` (int32 [M]) holds all requests' lists of pool indices one
         after another, request q owning index[req_ptr[q]:req_ptr[q + 1]]
@@ -460,7 +483,15 @@ class Engine:
         of request q is the model's prediction for context q's keys followed by
         candidate index[e]'s, from the two pool vectors alone, whatever else the
         call holds.  An index outside [0, len(pool_vecs)) scores +0.0.  Raises
-        unless ``pools``."""
+        unless ``pools``.
+
+        ``crosses`` (a crossed model): ``ctx_vecs`` / ``ctx_ops`` come from
+        pool_rows(contexts, crosses=, fold=True), ``pool_vecs`` / ``pool_ops``
+        from pool_rows(pool, crosses=).  The crosses a context completes on its
+        own are inside its vector; every other cross key of a pair is hashed
+        from the two operand rows and probed inside the kernel, so the entry is
+        the prediction for context ++ candidate ++ their cross keys.  Needs
+        EngineConfig.rank_cross."""
         self._pool_vecs("ctx_vecs", ctx_vecs)
         self._pool_vecs("pool_vecs", pool_vecs)
         for name, t in (("index", index), ("req_ptr", req_ptr)):
@@ -475,9 +506,19 @@ class Engine:
         elif out.dtype != torch.float32 or out.device != self.device or \
                 not out.is_contiguous() or tuple(out.shape) != (M,):
             raise ValueError(f"out must be a contiguous float32 [{M}] tensor on {self.device}")
+        xargs = ()
+        if crosses:
+            crosses = [list(c) for c in check_crosses(crosses)]
+            OW = self.pool_ops_width(crosses)
+            for name, t, v in (("ctx_ops", ctx_ops, ctx_vecs), ("pool_ops", pool_ops, pool_vecs)):
+                if t is None or t.dtype != torch.int64 or t.device != self.device or \
+                        not t.is_contiguous() or tuple(t.shape) != (v.shape[0], OW):
+                    raise ValueError(f"{name} must be a contiguous int64 [{v.shape[0]}, {OW}] tensor "
+                                     f"on {self.device} (pool_rows with crosses)")
+            xargs = (crosses, ctx_ops.data_ptr(), pool_ops.data_ptr())
         self._sync_stream()
         self._e.pool_subset(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(), int(pool_vecs.shape[0]),
-                            index.data_ptr(), req_ptr.data_ptr(), M, out.data_ptr())
+                            index.data_ptr(), req_ptr.data_ptr(), M, out.data_ptr(), *xargs)
         return out
 
     def train_view(self, view) -> None:

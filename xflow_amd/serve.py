@@ -29,6 +29,9 @@ N(0,1)*scale init for latent factors, ftrl.h:110-122).
                       optional "top_k")     -> as above, one entry per context with "contexts"
                       with "pool_index": [i, ...] (under "contexts": [[i, ...], ...]) the
                       context's own list of pool indices is scored, not the whole pool
+                      a model with feature crosses: "fields": [[f, ...], ...] with
+                      POST /pool and "context_fields" (a list, or lists under
+                      "contexts") with POST /rank
         GET  /health
 
 A candidate catalogue that many requests share is uploaded and probed once,
@@ -107,6 +110,7 @@ class Pool:
     def __init__(self, chunks, n: int):
         self.chunks, self.n = chunks, int(n)
         self.vecs, self.version = None, None
+        self.ops = None  # a crossed model: the candidates' operand rows [n, 1 + nu]
 
     def __len__(self) -> int:
         return self.n
@@ -502,16 +506,28 @@ class Predictor:
         return self.rank_csr(ck, cp, k, p, np.array([0, len(p) - 1]), cf, f, top_k)[0]
 
     # ---------------------------------------------------------------- pools
-    def build_pool_csr(self, keys: np.ndarray, row_ptr: np.ndarray) -> Pool:
+    def build_pool_csr(self, keys: np.ndarray, row_ptr: np.ndarray,
+                       fgid: Optional[np.ndarray] = None) -> Pool:
         """A Pool of the candidates of a CSR batch (keys u64, row_ptr n + 1
         offsets): their rows go to the device once, in chunks of at most
         ``max_rows`` rows, and Engine.pool_rows turns them into vectors.  A
         frozen LR or FM snapshot only, on either device; there is no host
-        fallback -- the expanded rows are what a pool exists to avoid."""
-        if self.crosses:
+        fallback -- the expanded rows are what a pool exists to avoid.
+
+        A model trained with feature crosses needs ``fgid`` (int32, one field
+        id per key): the pool then keeps every candidate's cross operands next
+        to its vector, and rank_pool builds the pairs' cross keys on the
+        device (Engine.pool_subset with crosses)."""
+        if self.crosses and (fgid is None or not self.engine.cfg.rank_cross):
             raise ValueError("this model was trained with feature crosses: a cross key depends on "
                              "both the context and the candidate, so a candidate has no vector of "
-                             "its own -- rank with rank_keys / rank_csr")
+                             "its own -- rank with rank_keys / rank_csr, or give the candidates' "
+                             "field ids (fields= / fgid=, with rank_cross on) for a pool that keeps "
+                             "their cross operands")
+        if not self.crosses:
+            fgid = None
+        elif len(fgid) != len(np.ascontiguousarray(keys).reshape(-1)):
+            raise ValueError("fgid must hold one field id per key")
         if not self.engine.pools:
             raise ValueError("candidate pools need a frozen LR or FM serving snapshot "
                              "(not MVM, not a full checkpoint, not fm_mfma)")
@@ -525,16 +541,24 @@ class Predictor:
         for r in range(0, n, self.max_rows):
             r1 = min(n, r + self.max_rows)
             k0, k1 = int(row_ptr[r]), int(row_ptr[r1])
-            chunks.append(self._csr_batch(keys[k0:k1], row_ptr[r:r1 + 1] - k0))
+            chunks.append(self._csr_batch(keys[k0:k1], row_ptr[r:r1 + 1] - k0,
+                                          None if fgid is None else fgid[k0:k1]))
         pool = Pool(chunks, n)
         with self._lock:
             self._pool_vectors(pool)
         return pool
 
-    def build_pool(self, rows: Sequence[Sequence[int]]) -> Pool:
-        """build_pool_csr from lists of (already hashed) u64 keys."""
+    def build_pool(self, rows: Sequence[Sequence[int]],
+                   fields: Optional[Sequence[Sequence[int]]] = None) -> Pool:
+        """build_pool_csr from lists of (already hashed) u64 keys; ``fields``:
+        the field id of every key (a model with feature crosses)."""
         rp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
-        return self.build_pool_csr(np.array([k for r in rows for k in r], dtype=np.uint64), rp)
+        fg = None
+        if fields is not None:
+            if [len(f) for f in fields] != [len(r) for r in rows]:
+                raise ValueError("fields must hold one field id per key")
+            fg = np.array([g for f in fields for g in f], dtype=np.int32)
+        return self.build_pool_csr(np.array([k for r in rows for k in r], dtype=np.uint64), rp, fg)
 
     def build_pool_libffm(self, text: bytes) -> Pool:
         """build_pool_csr from libffm text, a candidate per line (predict_libffm)."""
@@ -544,32 +568,43 @@ class Predictor:
             text += b"\n"
         blk = _native.load().parse_libffm(text)
         return self.build_pool_csr(np.asarray(blk["keys"]).view(np.uint64),
-                                   np.asarray(blk["row_ptr"], np.int64))
+                                   np.asarray(blk["row_ptr"], np.int64), np.asarray(blk["fgid"]))
 
-    def _csr_batch(self, keys, row_ptr) -> Batch:
+    def _csr_batch(self, keys, row_ptr, fgid=None) -> Batch:
         dev = self.device
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
         return Batch(keys=torch.from_numpy(np.ascontiguousarray(keys).view(np.int64)).to(dev),
                      labels=torch.zeros(len(row_ptr) - 1, dtype=torch.float32, device=dev),
-                     row_ptr=torch.from_numpy(np.ascontiguousarray(row_ptr, np.int32)).to(dev))
+                     row_ptr=up(row_ptr, np.int32), fgid=None if fgid is None else up(fgid, np.int32))
 
     def _pool_vectors(self, pool: Pool) -> torch.Tensor:
         """The pool's vectors under this Predictor's current model (lock held):
         rebuilt from the stored rows when the version has changed -- a
         refresh() or an engine swap -- so a pool never serves a stale model."""
         if pool.version != self._version:
-            if not self.engine.pools or self.crosses:
+            X = self.crosses
+            if not self.engine.pools or \
+                    (X and not (self.engine.cfg.rank_cross and all(b.fgid is not None for b in pool.chunks))):
                 raise ValueError("the model this Predictor now holds has no candidate pools")
             vecs = torch.empty((pool.n, self.engine.pool_width), dtype=torch.float32,
                                device=self.device)
-            r = 0
-            for b in pool.chunks:
-                self.engine.pool_rows(b, out=vecs[r:r + b.rows])
+            ops, r = [], 0
+            for b in pool.chunks:  # (a crossed model: the operand rows too)
+                got = self.engine.pool_rows(b, out=vecs[r:r + b.rows], crosses=X or None)
+                if X:
+                    ops.append(got[1])
                 r += b.rows
+            pool.ops = torch.cat(ops) if ops else (
+                torch.empty((0, self.engine.pool_ops_width(X)), dtype=torch.int64,
+                            device=self.device) if X else None)
             pool.vecs, pool.version = vecs, self._version
         return pool.vecs
 
-    def _rank_pool_subsets(self, ctx_keys, ctx_ptr, pool: Pool, top_k, index, ptr) -> list:
-        """rank_pool_csr with subsets (arguments checked there but for these)."""
+    def _rank_pool_subsets(self, ctx_keys, ctx_ptr, pool: Pool, top_k, index, ptr,
+                           ctx_fgid=None) -> list:
+        """rank_pool_csr with subsets (arguments checked there but for these).
+        ctx_fgid: a crossed model -- the contexts are folded and every pair's
+        cross keys are built inside Engine.pool_subset."""
         index = np.asarray(index, dtype=np.int64)
         ptr = np.asarray(ptr, dtype=np.int64)
         R, N = len(ctx_ptr) - 1, pool.n
@@ -591,11 +626,18 @@ class Predictor:
                 c0, c1, m0, m1 = int(ctx_ptr[q]), int(ctx_ptr[q1]), int(ptr[q]), int(ptr[q1])
                 if m1 - m0 > 0x7fffffff:
                     raise ValueError("one request's subset must stay below 2^31 candidates")
-                cv = self.engine.pool_rows(self._csr_batch(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0))
+                xkw = {}
+                if ctx_fgid is None:
+                    cv = self.engine.pool_rows(self._csr_batch(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0))
+                else:
+                    cv, co = self.engine.pool_rows(
+                        self._csr_batch(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0, ctx_fgid[c0:c1]),
+                        crosses=self.crosses, fold=True)
+                    xkw = dict(crosses=self.crosses, ctx_ops=co, pool_ops=pool.ops)
                 rp = ptr[q:q1 + 1] - m0
                 up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32)).to(self.device)
                 idx_d, rp_d = up(index[m0:m1]), up(rp)
-                p = self.engine.pool_subset(cv, vecs, idx_d, rp_d)
+                p = self.engine.pool_subset(cv, vecs, idx_d, rp_d, **xkw)
                 if top_k is None:
                     p = p.cpu().numpy()
                     out += [p[rp[j]:rp[j + 1]] for j in range(q1 - q)]
@@ -613,7 +655,8 @@ class Predictor:
 
     def rank_pool_csr(self, ctx_keys: np.ndarray, ctx_ptr: np.ndarray, pool: Pool,
                       top_k: Optional[int] = None, subset_index: Optional[np.ndarray] = None,
-                      subset_ptr: Optional[np.ndarray] = None) -> list:
+                      subset_ptr: Optional[np.ndarray] = None,
+                      ctx_fgid: Optional[np.ndarray] = None) -> list:
         """R contexts (CSR: ctx_keys u64, ctx_ptr R + 1 offsets) against every
         candidate of ``pool``.  Returns one float32 array of len(pool) scores
         per context -- the model's prediction for the context's keys followed
@@ -631,7 +674,13 @@ class Predictor:
         the pool indices of the best n = min(top_k, len(list)) entries, equal
         scores in ascending position in the list.  An index outside [0,
         len(pool)) raises ValueError before anything is uploaded.  A chunk is
-        whole requests whose entries stay under ``pool_max_scores``."""
+        whole requests whose entries stay under ``pool_max_scores``.
+
+        A model with feature crosses (a pool built with field ids) needs
+        ``ctx_fgid``, one field id per context key, and raises ValueError
+        without it.  Its scores are those of the row context + candidate +
+        cross keys; without subsets every request's list is the whole pool,
+        through the same kernel."""
         if top_k is not None and not (isinstance(top_k, (int, np.integer)) and 1 <= top_k <= 1024):
             raise ValueError("top_k must be an integer from 1 to 1024")
         ctx_keys = np.ascontiguousarray(ctx_keys).view(np.uint64)
@@ -642,9 +691,30 @@ class Predictor:
             raise ValueError("ctx_ptr must hold requests + 1 non-decreasing offsets from 0 to len(ctx_keys)")
         if (subset_index is None) != (subset_ptr is None):
             raise ValueError("give 'subset_index' and 'subset_ptr' together")
+        if self.crosses:
+            if ctx_fgid is None:
+                raise ValueError("this model was trained with feature crosses: give the contexts' "
+                                 "field ids (context_fields= / ctx_fgid=)")
+            ctx_fgid = np.asarray(ctx_fgid, dtype=np.int32)
+            if ctx_fgid.shape != ctx_keys.shape:
+                raise ValueError("ctx_fgid must hold one field id per context key")
+        else:
+            ctx_fgid = None
         if subset_index is not None:
-            return self._rank_pool_subsets(ctx_keys, ctx_ptr, pool, top_k, subset_index, subset_ptr)
+            return self._rank_pool_subsets(ctx_keys, ctx_ptr, pool, top_k, subset_index, subset_ptr,
+                                           ctx_fgid)
         per = max(1, min(self.pool_max_scores, 0x7fffffff) // max(N, 1))
+        if self.crosses:
+            # the whole pool as every request's list (the matrix-core kernels
+            # take no crosses): chunks of whole requests, built as they go
+            out = []
+            for q in range(0, R, per):
+                q1 = min(R, q + per)
+                c0, c1 = int(ctx_ptr[q]), int(ctx_ptr[q1])
+                out += self._rank_pool_subsets(ctx_keys[c0:c1], ctx_ptr[q:q1 + 1] - c0, pool, top_k,
+                                               np.tile(np.arange(N), q1 - q),
+                                               np.arange(q1 - q + 1) * N, ctx_fgid[c0:c1])
+            return out
         if top_k is not None and self.engine.pool_topk_fused:
             words = self.engine.pool_topk_words(N, int(top_k))
             per = max(1, min(4 * self.pool_max_scores // (8 * max(words, 1)), 0x7fffffff))
@@ -668,15 +738,21 @@ class Predictor:
 
     def rank_pool(self, contexts: Sequence[Sequence[int]], pool: Pool,
                   top_k: Optional[int] = None,
-                  subsets: Optional[Sequence[Sequence[int]]] = None) -> list:
+                  subsets: Optional[Sequence[Sequence[int]]] = None,
+                  context_fields: Optional[Sequence[Sequence[int]]] = None) -> list:
         """rank_pool_csr from lists: contexts[q] the (already hashed) u64 keys
-        of request q's context, ``subsets[q]`` its own list of pool indices."""
+        of request q's context, ``subsets[q]`` its own list of pool indices,
+        ``context_fields[q]`` the field id of every key (a crossed model)."""
         ptr = lambda ls: np.concatenate([[0], np.cumsum([len(x) for x in ls])]).astype(np.int64)
         sub = {}
+        if context_fields is not None:
+            if [len(f) for f in context_fields] != [len(c) for c in contexts]:
+                raise ValueError("context_fields must hold one field id per context key")
+            sub["ctx_fgid"] = np.array([g for f in context_fields for g in f], dtype=np.int32)
         if subsets is not None:
             if len(subsets) != len(contexts):
                 raise ValueError("give one list of pool indices per context")
-            sub = dict(subset_index=np.array([i for s in subsets for i in s], dtype=np.int64),
+            sub.update(subset_index=np.array([i for s in subsets for i in s], dtype=np.int64),
                        subset_ptr=ptr(subsets))
         return self.rank_pool_csr(np.array([k for c in contexts for k in c], dtype=np.uint64),
                                   ptr(contexts), pool, top_k, **sub)
@@ -720,12 +796,13 @@ def make_app(pred: Predictor):
     predict.__annotations__ = {"req": Req}
     app.post("/predict")(predict)
 
-    PoolReq = create_model("PoolRequest", name=(str, ...), candidates=(list[list[int]], ...))
+    PoolReq = create_model("PoolRequest", name=(str, ...), candidates=(list[list[int]], ...),
+                           fields=(Optional[list[list[int]]], None))
     pools = {}  # name -> Pool, registered by POST /pool
 
     def pool(req):
         try:
-            pools[req.name] = pred.build_pool(req.candidates)
+            pools[req.name] = pred.build_pool(req.candidates, req.fields)
         except ValueError as e:
             raise HTTPException(400, str(e))
         return {"name": req.name, "candidates": len(pools[req.name])}
@@ -735,7 +812,7 @@ def make_app(pred: Predictor):
 
     RankReq = create_model("RankRequest", context=(Optional[list[int]], None),
                            candidates=(Optional[list[list[int]]], None),
-                           context_fields=(Optional[list[int]], None),
+                           context_fields=(Optional[Union[list[int], list[list[int]]]], None),
                            candidate_fields=(Optional[list[list[int]]], None),
                            top_k=(Optional[int], None), pool=(Optional[str], None),
                            contexts=(Optional[list[list[int]]], None),
@@ -759,9 +836,17 @@ def make_app(pred: Predictor):
             elif req.context is not None or not all(isinstance(s, list) for s in subsets):
                 raise HTTPException(400, "'pool_index' is a list under 'context' and a list of "
                                          "lists under 'contexts'")
+        fields = req.context_fields  # (a crossed model: a list under 'context', lists under 'contexts')
+        if fields is not None:
+            nested = all(isinstance(f, list) for f in fields)
+            if req.context is not None and not any(isinstance(f, list) for f in fields):
+                fields = [fields]
+            elif req.context is not None or not nested:
+                raise HTTPException(400, "'context_fields' is a list under 'context' and a list of "
+                                         "lists under 'contexts'")
         try:
             got = pred.rank_pool(req.contexts if req.context is None else [req.context],
-                                 pools[req.pool], req.top_k, subsets)
+                                 pools[req.pool], req.top_k, subsets, fields)
         except ValueError as e:
             raise HTTPException(400, str(e))
         if req.top_k is not None:
