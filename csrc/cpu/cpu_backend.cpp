@@ -1047,6 +1047,46 @@ class CpuBackend final : public Backend {
       }
     }
   }
+  // pool_subset, then topk on its scores, then positions into pool indices; a
+  // score of the last tie class comes back as +0.0f (PoolSubsetTopkArgs)
+  void pool_subset_topk(const PoolSubsetTopkArgs& a) override {
+    if (!pool_check(a)) return;
+    std::vector<float> p((size_t)a.M);
+    PoolSubsetArgs sa;
+    sa.ctx = a.ctx;
+    sa.pool = a.pool;
+    sa.index = a.index;
+    sa.req_ptr = a.req_ptr;
+    sa.R = a.R;
+    sa.N = a.N;
+    sa.M = a.M;
+    sa.pctr = p.data();
+    sa.model = a.model;
+    pool_subset(sa);
+    TopkArgs ta;
+    ta.pctr = p.data();
+    ta.req_ptr = a.req_ptr;
+    ta.R = a.R;
+    ta.rows = a.M;
+    ta.k = a.k;
+    ta.idx = a.idx;
+    ta.score = a.score;
+    topk(ta);
+    pool_subset_map(a.idx, a.req_ptr, a.index, a.R, a.k, a.M);
+    for (int64_t j = 0; j < a.R * a.k; ++j)
+      if (eval_key_bits(a.score[j]) == 0) a.score[j] = 0.0f;
+  }
+  void pool_subset_map(int32_t* idx, const int32_t* req_ptr, const int32_t* index, int64_t R, int k,
+                       int64_t M) override {
+    for (int64_t q = 0; q < R && M > 0; ++q) {
+      const int64_t lo = std::clamp<int64_t>(req_ptr[q], 0, M);
+      const int64_t hi = std::clamp<int64_t>(req_ptr[q + 1], lo, M);
+      for (int j = 0; j < k; ++j) {
+        int32_t& x = idx[q * k + j];
+        if (x >= 0) x = lo + x < hi ? index[lo + x] : -1;
+      }
+    }
+  }
 
  private:
   // PoolSubsetArgs with a spec: the incomplete crosses of the pair (q, i), in

@@ -821,4 +821,41 @@ void Engine::pool_subset(const float* ctx, int64_t R, const float* pool, int64_t
   be_->pool_subset(pa);
 }
 
+void Engine::pool_subset_topk(const float* ctx, int64_t R, const float* pool, int64_t N,
+                              const int32_t* index, const int32_t* req_ptr, int64_t M, int k,
+                              int32_t* idx, float* score) {
+  if (!pools())
+    throw std::runtime_error("pool_subset_topk: needs a frozen LR or FM engine (no fm_mfma)");
+  PoolSubsetTopkArgs pa;
+  pa.ctx = ctx;
+  pa.pool = pool;
+  pa.index = index;
+  pa.req_ptr = req_ptr;
+  pa.R = R;
+  pa.N = N;
+  pa.M = M;
+  pa.k = k;
+  pa.idx = idx;
+  pa.score = score;
+  pa.model = cfg_.model;
+  pa.stage = cfg_.pool_subset_stage < 0 ? pool_width() >= kPoolSubsetStageMin
+                                        : cfg_.pool_subset_stage != 0;
+  const bool fused = cfg_.pool_subset_topk_fused &&
+                     (cfg_.pool_subset_topk_fused_max <= 0 || M <= cfg_.pool_subset_topk_fused_max);
+  if (!is_gpu() || fused) {
+    if (is_gpu() && M > kTopkTile && M <= 0x7fffffffll) {
+      pool_subset_partial_.reserve(*be_, (size_t)M, (size_t)M);
+      pa.partial = pool_subset_partial_;
+    }
+    be_->pool_subset_topk(pa);
+    return;
+  }
+  // composed on the device: the scores, their top-k, positions -> pool indices
+  if (!pool_check(pa)) return;
+  pool_subset_scores_.reserve(*be_, (size_t)M, (size_t)M);
+  pool_subset(ctx, R, pool, N, index, req_ptr, M, pool_subset_scores_);
+  topk_step(pool_subset_scores_, req_ptr, R, M, k, idx, score);
+  be_->pool_subset_map(idx, req_ptr, index, R, k, M);
+}
+
 }  // namespace xflow

@@ -481,6 +481,13 @@ class HipBackend final : public Backend {
   void pool_score(const PoolScoreArgs& a) override { hip::launch_pool_score(a, stream_); }
   void pool_topk(const PoolTopkArgs& a) override { hip::launch_pool_topk(a, stream_); }
   void pool_subset(const PoolSubsetArgs& a) override { hip::launch_pool_subset(a, stream_); }
+  void pool_subset_topk(const PoolSubsetTopkArgs& a) override {
+    hip::launch_pool_subset_topk(a, stream_);
+  }
+  void pool_subset_map(int32_t* idx, const int32_t* req_ptr, const int32_t* index, int64_t R, int k,
+                       int64_t M) override {
+    hip::launch_pool_subset_map(idx, req_ptr, index, R, k, M, stream_);
+  }
   int64_t delta_popcount(const u32* bits, int L) override {
     hip::launch_delta_popcount(bits, L, counter_, stream_);
     unsigned long long n = 0;

@@ -96,6 +96,8 @@ void launch_rank_cross(const RankArgs& a, hipStream_t st);
 
 // kernels_topk.hip
 void launch_topk(const TopkArgs& a, hipStream_t st);
+// the padding of n result entries: idx -1, score +0.0f
+void launch_topk_fill(int32_t* idx, float* score, int64_t n, hipStream_t st);
 
 // kernels_pool.hip
 void launch_pool_rows(const PoolRowsArgs& a, hipStream_t st);    // LR, FM
@@ -108,6 +110,10 @@ void launch_pool_subset(const PoolSubsetArgs& a, hipStream_t st);  // LR, FM
 // a.spec.n > 0; both have checked their arguments)
 void launch_pool_rows_cross(const PoolRowsArgs& a, hipStream_t st);
 void launch_pool_subset_cross(const PoolSubsetArgs& a, hipStream_t st);
+// kernels_pool_subset_topk.hip
+void launch_pool_subset_topk(const PoolSubsetTopkArgs& a, hipStream_t st);  // LR, FM
+void launch_pool_subset_map(int32_t* idx, const int32_t* req_ptr, const int32_t* index, int64_t R,
+                            int k, int64_t M, hipStream_t st);
 
 // kernels_layout.hip
 void launch_unpack_block(const UnpackArgs& a, hipStream_t st);

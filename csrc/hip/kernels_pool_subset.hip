@@ -83,44 +83,14 @@ __global__ void __launch_bounds__(kBlock) k_pool_subset(PoolSubsetArgs a, int dk
   float bv[W];
   if constexpr (kStaged) {
     __shared__ float4 s_rows[kBlock * Q];
-    float4* mine = s_rows + wave * (kWave * Q);
-#pragma unroll
-    for (int j = 0; j < Q; ++j) {
-      const int t = lane + kWave * j, r = t / Q, p = t % Q;
-      const int ri = __shfl(i, r);
-      mine[pool_subset_slot<Q>(r, p)] =
-          ri >= 0 ? pool4[(int64_t)ri * Q + p] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();  // (every thread of the workgroup is here)
-#pragma unroll
-    for (int p = 0; p < Q; ++p) {
-      const float4 v = mine[pool_subset_slot<Q>(lane, p)];
-      bv[4 * p] = v.x, bv[4 * p + 1] = v.y, bv[4 * p + 2] = v.z, bv[4 * p + 3] = v.w;
-    }
+    pool_subset_gather<Q, true>(pool4, i, lane, s_rows + wave * (kWave * Q), bv);
   } else {
-#pragma unroll
-    for (int p = 0; p < Q; ++p) {
-      const float4 v = i >= 0 ? pool4[(int64_t)i * Q + p] : make_float4(0.f, 0.f, 0.f, 0.f);
-      bv[4 * p] = v.x, bv[4 * p + 1] = v.y, bv[4 * p + 2] = v.z, bv[4 * p + 3] = v.w;
-    }
+    pool_subset_gather<Q, false>(pool4, i, lane, nullptr, bv);
   }
   if (e >= a.M) return;
   float out = 0.0f;
-  if (i >= 0) {
-    const float4* ctx4 = reinterpret_cast<const float4*>(a.ctx) + q * Q;
-    float av[W];
-#pragma unroll
-    for (int p = 0; p < Q; ++p) {
-      const float4 v = ctx4[p];
-      av[4 * p] = v.x, av[4 * p + 1] = v.y, av[4 * p + 2] = v.z, av[4 * p + 3] = v.w;
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < KP; ++k)  // (constant k: av and bv stay in registers)
-      if (k < Dk + 2)
-        acc = __fmaf_rn(pool_operand(av, k, Dk, true, g), pool_operand(bv, k, Dk, false, g), acc);
-    out = sigmoid_ref(acc);
-  }
+  if (i >= 0)
+    out = pool_subset_score<KP>(reinterpret_cast<const float4*>(a.ctx) + q * Q, bv, Dk, g);
   a.pctr[e] = out;
 }
 

@@ -42,17 +42,6 @@ namespace hip {
 
 namespace {
 
-// first request that ends past `row` (R: none)
-__device__ __forceinline__ int64_t topk_request(const TopkArgs& a, int64_t row) {
-  int64_t l0 = 0, l1 = a.R;
-  while (l0 < l1) {
-    const int64_t m = (l0 + l1) >> 1;
-    if ((int64_t)a.req_ptr[m + 1] > row) l1 = m;
-    else l0 = m + 1;
-  }
-  return l0;
-}
-
 __global__ void __launch_bounds__(kBlock) k_topk_fill(int32_t* idx, float* score, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kBlock) {
@@ -67,7 +56,7 @@ __global__ void __launch_bounds__(kBlock) k_topk_tile(TopkArgs a) {
   const int64_t tend = t0 + kTopkT < a.rows ? t0 + kTopkT : a.rows;
   const u32 rel0 = threadIdx.x * kTopkPer;
   const int64_t r0 = t0 + rel0;  // this thread's first row and, after the sort, position
-  const int64_t q0 = topk_request(a, r0);
+  const int64_t q0 = topk_request(a.req_ptr, a.R, r0);
   u64 v[kTopkPer];
   int64_t q = q0;
 #pragma unroll
@@ -115,37 +104,10 @@ __global__ void __launch_bounds__(kBlock) k_topk_tile(TopkArgs a) {
 
 __global__ void __launch_bounds__(kBlock) k_topk_merge(TopkArgs a) {
   __shared__ u64 lds[kTopkT];
-  const int64_t edge = ((int64_t)blockIdx.x + 1) * kTopkT;  // (< rows)
-  const int64_t q = topk_request(a, edge);  // holds row `edge`
-  if (q >= a.R) return;
-  const int64_t qa = a.req_ptr[q];
-  const int64_t qb = (int64_t)a.req_ptr[q + 1] < a.rows ? (int64_t)a.req_ptr[q + 1] : a.rows;
-  // owned here: starts inside the tile before this edge
-  if (qa < edge - kTopkT || qa >= edge || qb <= edge) return;
-  const u32 k = (u32)a.k, S = (u32)kTopkT / k;
-  const int64_t tlast = (qb - 1) / kTopkT;
-  const u32 rel0 = threadIdx.x * kTopkPer;
+  const u32 k = (u32)a.k, rel0 = threadIdx.x * kTopkPer;
   u64 v[kTopkPer];
-#pragma unroll
-  for (int e = 0; e < kTopkPer; ++e) v[e] = 0;  // (below every partial: an index is < 2^31)
-  // words [0, k): the best so far; [s k, (s + 1) k), s >= 1: the list of tile tb + s - 1
-  for (int64_t tb = blockIdx.x; tb <= tlast; tb += S - 1) {
-    const int64_t lists = tlast - tb + 1 < (int64_t)(S - 1) ? tlast - tb + 1 : (int64_t)(S - 1);
-#pragma unroll
-    for (int e = 0; e < kTopkPer; ++e) {
-      const u32 p = rel0 + e, s = p / k, off = p - s * k;
-      if (s == 0) continue;
-      u64 x = 0;
-      if ((int64_t)s <= lists) {
-        const int64_t t = tb + s - 1;
-        const int64_t lo = qa > t * kTopkT ? qa : t * kTopkT;
-        const int64_t hi = qb < (t + 1) * kTopkT ? qb : (t + 1) * kTopkT;
-        if ((int64_t)off < hi - lo) x = a.partial[lo + off];
-      }
-      v[e] = x;
-    }
-    topk_sort(v, topk_pow2((lists + 1) * (int64_t)k), lds);
-  }
+  int64_t q, qa, qb;
+  if (!topk_merge_edge(a.req_ptr, a.R, a.rows, k, a.partial, v, lds, q, qa, qb)) return;
 #pragma unroll
   for (int e = 0; e < kTopkPer; ++e) {
     const u32 p = rel0 + e, ci = ~(u32)v[e];
@@ -158,13 +120,16 @@ __global__ void __launch_bounds__(kBlock) k_topk_merge(TopkArgs a) {
 
 }  // namespace
 
+void launch_topk_fill(int32_t* idx, float* score, int64_t n, hipStream_t st) {
+  hipLaunchKernelGGL(k_topk_fill, dim3(grid_for(n)), dim3(kBlock), 0, st, idx, score, n);
+}
+
 void launch_topk(const TopkArgs& a, hipStream_t st) {
   if (!topk_check(a)) return;
   const int64_t tiles = (a.rows + kTopkT - 1) / kTopkT;
   if (tiles > 1 && !a.partial) throw std::runtime_error("topk: more than one tile needs the scratch");
   // (one launch pads both arrays; the sort kernels then write the entries that exist)
-  const int64_t n = a.R * a.k;
-  hipLaunchKernelGGL(k_topk_fill, dim3(grid_for(n)), dim3(kBlock), 0, st, a.idx, a.score, n);
+  launch_topk_fill(a.idx, a.score, a.R * a.k, st);
   if (tiles > 0) hipLaunchKernelGGL(k_topk_tile, dim3((unsigned)tiles), dim3(kBlock), 0, st, a);
   if (tiles > 1) hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)(tiles - 1)), dim3(kBlock), 0, st, a);
   XF_HIP_CHECK(hipGetLastError());

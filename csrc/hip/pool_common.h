@@ -1,6 +1,7 @@
 // xflow-amd: device code shared by the candidate-pool kernels (kernels_pool.hip:
 // the score matrix; kernels_pool_topk.hip: score and select in one kernel;
-// kernels_pool_subset.hip and kernels_pool_cross.hip: a request's own list).
+// kernels_pool_subset.hip and kernels_pool_cross.hip: a request's own list;
+// kernels_pool_subset_topk.hip: that list scored and selected in one kernel).
 // Included by .hip files only.
 #pragma once
 #include "hip_util.h"
@@ -61,6 +62,59 @@ constexpr int pool_subset_width(int KP) { return (KP + 2) & ~3; }  // pool_width
 template <int Q>
 __device__ __forceinline__ int pool_subset_slot(int r, int p) {
   return r * Q + (Q % 2 == 0 ? p ^ ((r >> 3) & (Q - 1)) : p);
+}
+
+// pool row i (-1: none, zeros) of this lane into bv.  STAGED: the wave's 64
+// rows are loaded together, whole rows per instruction, into its LDS region
+// `mine` (64 * Q float4s) and lane l reads row l back; the barrier inside is
+// for every thread of the workgroup.  Otherwise the lane's own Q loads: the
+// same values either way.
+template <int Q, bool STAGED>
+__device__ __forceinline__ void pool_subset_gather(const float4* pool4, int i, int lane,
+                                                   float4* mine, float (&bv)[4 * Q]) {
+  if constexpr (STAGED) {
+#pragma unroll
+    for (int j = 0; j < Q; ++j) {
+      const int t = lane + kWave * j, r = t / Q, p = t % Q;
+      const int ri = __shfl(i, r);
+      mine[pool_subset_slot<Q>(r, p)] =
+          ri >= 0 ? pool4[(int64_t)ri * Q + p] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();  // (every thread of the workgroup is here)
+#pragma unroll
+    for (int p = 0; p < Q; ++p) {
+      const float4 v = mine[pool_subset_slot<Q>(lane, p)];
+      bv[4 * p] = v.x, bv[4 * p + 1] = v.y, bv[4 * p + 2] = v.z, bv[4 * p + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < Q; ++p) {
+      const float4 v = i >= 0 ? pool4[(int64_t)i * Q + p] : make_float4(0.f, 0.f, 0.f, 0.f);
+      bv[4 * p] = v.x, bv[4 * p + 1] = v.y, bv[4 * p + 2] = v.z, bv[4 * p + 3] = v.w;
+    }
+  }
+}
+
+// PoolSubsetArgs' score of one pair: the context vector at ctx4 against the
+// pool row in bv, acc = fma(A[k], B[k], acc) over pool_operand's words from
+// 0.0f, then sigmoid_ref
+template <int KP>
+__device__ __forceinline__ float pool_subset_score(const float4* ctx4,
+                                                   const float (&bv)[pool_subset_width(KP)], int Dk,
+                                                   float g) {
+  constexpr int W = pool_subset_width(KP), Q = W / 4;
+  float av[W];
+#pragma unroll
+  for (int p = 0; p < Q; ++p) {
+    const float4 v = ctx4[p];
+    av[4 * p] = v.x, av[4 * p + 1] = v.y, av[4 * p + 2] = v.z, av[4 * p + 3] = v.w;
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < KP; ++k)  // (constant k: av and bv stay in registers)
+    if (k < Dk + 2)
+      acc = __fmaf_rn(pool_operand(av, k, Dk, true, g), pool_operand(bv, k, Dk, false, g), acc);
+  return sigmoid_ref(acc);
 }
 
 }  // namespace hip

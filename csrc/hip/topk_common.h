@@ -1,6 +1,8 @@
 // xflow-amd: the 4096-word bitonic network shared by the top-k kernels
 // (kernels_topk.hip: segmented top-k of a score array; kernels_pool_topk.hip:
-// the merge of a pool's strip lists).  Included by .hip files only.
+// the merge of a pool's strip lists; kernels_pool_subset_topk.hip: a tile's
+// scores computed into the network's registers), and the walk and the merge
+// rounds of the two kernels that tile a flat list.  Included by .hip files only.
 #pragma once
 #include "hip_util.h"
 
@@ -77,6 +79,62 @@ __device__ __forceinline__ u32 topk_pow2(int64_t x) {
   u32 n = kTopkPer;
   while ((int64_t)n < x) n <<= 1;
   return n;
+}
+
+// first request that ends past `row` (R: none)
+__device__ __forceinline__ int64_t topk_request(const int32_t* req_ptr, int64_t R, int64_t row) {
+  int64_t l0 = 0, l1 = R;
+  while (l0 < l1) {
+    const int64_t m = (l0 + l1) >> 1;
+    if ((int64_t)req_ptr[m + 1] > row) l1 = m;
+    else l0 = m + 1;
+  }
+  return l0;
+}
+
+// The merge of one tile edge (k_topk_merge, k_pool_subset_topk_merge; one
+// workgroup per edge, blockIdx.x + 1 the tile behind it).  At most one request
+// crosses an edge, and the workgroup of the first edge a request crosses owns
+// it.  false: nothing owned here (the same in every thread).  true: q, qa, qb
+// are the request and its rows, and words [0, k) of the workgroup's 4096 (word
+// i in v[i % 16] of thread i / 16) are its best partial words in order, 0 where
+// it has fewer: the request's sorted partial lists (min(k, rows in the tile)
+// words from the start of its rows in each tile) pass S - 1 per round next to
+// the best k so far, S = 4096 / k >= 4, through topk_sort.
+__device__ __forceinline__ bool topk_merge_edge(const int32_t* req_ptr, int64_t R, int64_t rows,
+                                                u32 k, const u64* partial, u64 (&v)[kTopkPer],
+                                                u64* lds, int64_t& q, int64_t& qa, int64_t& qb) {
+  const int64_t edge = ((int64_t)blockIdx.x + 1) * kTopkT;  // (< rows)
+  q = topk_request(req_ptr, R, edge);  // holds row `edge`
+  if (q >= R) return false;
+  qa = req_ptr[q];
+  qb = (int64_t)req_ptr[q + 1] < rows ? (int64_t)req_ptr[q + 1] : rows;
+  // owned here: starts inside the tile before this edge
+  if (qa < edge - kTopkT || qa >= edge || qb <= edge) return false;
+  const u32 S = (u32)kTopkT / k;
+  const int64_t tlast = (qb - 1) / kTopkT;
+  const u32 rel0 = threadIdx.x * kTopkPer;
+#pragma unroll
+  for (int e = 0; e < kTopkPer; ++e) v[e] = 0;  // (below every partial: an index is < 2^31)
+  // words [0, k): the best so far; [s k, (s + 1) k), s >= 1: the list of tile tb + s - 1
+  for (int64_t tb = blockIdx.x; tb <= tlast; tb += S - 1) {
+    const int64_t lists = tlast - tb + 1 < (int64_t)(S - 1) ? tlast - tb + 1 : (int64_t)(S - 1);
+#pragma unroll
+    for (int e = 0; e < kTopkPer; ++e) {
+      const u32 p = rel0 + e, s = p / k, off = p - s * k;
+      if (s == 0) continue;
+      u64 x = 0;
+      if ((int64_t)s <= lists) {
+        const int64_t t = tb + s - 1;
+        const int64_t lo = qa > t * kTopkT ? qa : t * kTopkT;
+        const int64_t hi = qb < (t + 1) * kTopkT ? qb : (t + 1) * kTopkT;
+        if ((int64_t)off < hi - lo) x = partial[lo + off];
+      }
+      v[e] = x;
+    }
+    topk_sort(v, topk_pow2((lists + 1) * (int64_t)k), lds);
+  }
+  return true;
 }
 
 }  // namespace hip

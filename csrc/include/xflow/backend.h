@@ -1231,6 +1231,40 @@ inline bool pool_check(const PoolSubsetArgs& a) {
   }
   return true;
 }
+// pool_subset_topk: TopkArgs' answer for pool_subset's scores -- request q's
+// best min(k, n_q) entries of its own list, idx / score [R][k] in topk's order
+// with its padding -- without an [M] score array, and with idx the pool index
+// index[e] itself, not the entry's position in the list (HIP:
+// kernels_pool_subset_topk.hip computes a tile's scores into the registers it
+// sorts; the CPU backend composes pool_subset and topk).  score holds
+// pool_subset's bits, but a score of topk's last tie class (NaN, zero or
+// negative: sort key 0) comes back as +0.0f.  No crosses.
+struct PoolSubsetTopkArgs {
+  const float* ctx = nullptr;        // [R][W] from pool_rows
+  const float* pool = nullptr;       // [N][W] from pool_rows
+  const int32_t* index = nullptr;    // [M] pool indices
+  const int32_t* req_ptr = nullptr;  // [R + 1] non-decreasing, 0 .. M
+  int64_t R = 0, N = 0, M = 0;
+  int k = 0;                         // 1 .. kTopkMaxK
+  int32_t* idx = nullptr;            // [R][k]
+  float* score = nullptr;            // [R][k]
+  u64* partial = nullptr;            // [M] scratch, HIP with M > kTopkTile only
+  ModelSpec model;                   // kLR or kFM
+  bool stage = true;                 // as PoolSubsetArgs::stage
+};
+// what both backends refuse; false: nothing to write (no request)
+inline bool pool_check(const PoolSubsetTopkArgs& a) {
+  pool_check_model(a.model);
+  if (a.k < 1 || a.k > kTopkMaxK) throw std::runtime_error("pool_subset_topk: k must be 1 .. 1024");
+  if (a.R < 0 || a.R > 0x7fffffffll || a.N < 0 || a.N > 0x7fffffffll || a.M < 0 ||
+      a.M > 0x7fffffffll)
+    throw std::runtime_error("pool_subset_topk: requests, candidates and entries are int32 counts");
+  if (a.R == 0) return false;
+  if (!a.idx || !a.score || !a.ctx ||
+      (a.M > 0 && (!a.index || !a.req_ptr || (a.N > 0 && !a.pool))))
+    throw std::runtime_error("pool_subset_topk: null array");
+  return true;
+}
 
 class Backend {
  public:
@@ -1454,6 +1488,13 @@ class Backend {
   virtual void pool_topk(const PoolTopkArgs& a) = 0;
   // every request against its own list of pool candidates (PoolSubsetArgs)
   virtual void pool_subset(const PoolSubsetArgs& a) = 0;
+  // every request's best k of its own list, as pool indices (PoolSubsetTopkArgs)
+  virtual void pool_subset_topk(const PoolSubsetTopkArgs& a) = 0;
+  // topk's positions into pool indices: idx[q][j] >= 0 becomes index[req_ptr[q] +
+  // idx[q][j]] (the composed path of Engine::pool_subset_topk); a position
+  // outside the request's entries, which topk never writes, becomes -1
+  virtual void pool_subset_map(int32_t* idx, const int32_t* req_ptr, const int32_t* index, int64_t R,
+                               int k, int64_t M) = 0;
   // Insert n synthetic keys (1 << 62 | hash(seed, i) >> 2: disjoint from any
   // key below 2^62, e.g. hashed features) with zero state, marked pushed --
   // keys a long run has accumulated but the current batches do not touch

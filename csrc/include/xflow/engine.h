@@ -165,6 +165,16 @@ struct EngineConfig {
   // loads its own row (the A/B switch; the same bits).  -1: staged from
   // kPoolSubsetStageMin floats per vector on, where it measured ahead
   int pool_subset_stage = -1;
+  // pool_subset_topk on HIP scores and selects a tile of the list in one
+  // kernel (PoolSubsetTopkArgs, kernels_pool_subset_topk.hip); false: the
+  // engine runs pool_subset into a scratch score array, then topk, then maps
+  // positions to pool indices (the A/B switch)
+  bool pool_subset_topk_fused = true;
+  // ... for calls of at most this many entries; 0: at every size.  One
+  // workgroup walks a tile's 16 rounds one after another, and measured
+  // (profiles/rank_pool_subset_topk.txt) the kernel is 1.04x to 1.17x ahead of
+  // the composed path up to 512 entries and 0.51x to 0.98x, behind, from 2048 on
+  int64_t pool_subset_topk_fused_max = 1024;
 };
 
 // Engine::delta_stats
@@ -603,6 +613,16 @@ class Engine {
                    const int32_t* req_ptr, int64_t M, float* pctr,
                    const CrossSpec& spec = CrossSpec(), const u64* ctx_ops = nullptr,
                    const u64* pool_ops = nullptr);
+  // Every request's best k entries of its own list (PoolSubsetTopkArgs): idx /
+  // score [R][k] as topk_step leaves them for pool_subset's scores, but idx
+  // holds pool indices (index[e]), not positions.  pool_subset_topk_fused():
+  // one kernel scores and selects (HIP and EngineConfig::pool_subset_topk_fused;
+  // a score of the last tie class comes back as +0.0f); otherwise pool_subset
+  // into a scratch array, topk and the map of positions.  No crosses.
+  bool pool_subset_topk_fused() const { return is_gpu() && cfg_.pool_subset_topk_fused; }
+  void pool_subset_topk(const float* ctx, int64_t R, const float* pool, int64_t N,
+                        const int32_t* index, const int32_t* req_ptr, int64_t M, int k,
+                        int32_t* idx, float* score);
   // ---- serving deltas (docs/DESIGN.md §2) -----------------------------------
   // Producer, on a training engine with delta_track: (key, P resolved weights)
   // of every key of the table whose touched-key bit is set -- the keys that
@@ -935,6 +955,8 @@ class Engine {
   int64_t growths_ = 0, splits_ = 0, monitor_waits_ = 0;
   DeviceBuffer<u64> topk_partial_;  // [max_rows or more] topk_step over several tiles, on first use
   DeviceBuffer<u64> pool_topk_partial_;  // [R][strips][k] pool_topk over several strips, on first use
+  DeviceBuffer<u64> pool_subset_partial_;  // [M] pool_subset_topk over several tiles, on first use
+  DeviceBuffer<float> pool_subset_scores_;  // [M] its composed path's scores, on first use
   DeviceBuffer<unsigned long long> pruned_dev_;  // [1] keys dropped by prune(), cumulative
   int64_t pruned_keys_ = 0;
   double grow_s_ = 0.0;

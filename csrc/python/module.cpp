@@ -446,8 +446,11 @@ PYBIND11_MODULE(_xflow_native, m) {
                        int64_t serve_unfused_lo, int64_t serve_unfused_hi,
                        int64_t serve_unfused_latent_lo, int64_t serve_unfused_latent_hi,
                        bool rank_cross, bool pool_topk_fused, int64_t pool_topk_strip,
-                       int pool_subset_stage) {
+                       int pool_subset_stage, bool pool_subset_topk_fused,
+                       int64_t pool_subset_topk_fused_max) {
              EngineConfig c;
+             c.pool_subset_topk_fused_max = pool_subset_topk_fused_max;
+             c.pool_subset_topk_fused = pool_subset_topk_fused;
              c.pool_subset_stage = pool_subset_stage;
              c.pool_topk_fused = pool_topk_fused;
              c.pool_topk_strip = pool_topk_strip;
@@ -498,7 +501,9 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("serve_unfused_lo") = 64, py::arg("serve_unfused_hi") = 256,
            py::arg("serve_unfused_latent_lo") = -1, py::arg("serve_unfused_latent_hi") = -1,
            py::arg("rank_cross") = true, py::arg("pool_topk_fused") = true,
-           py::arg("pool_topk_strip") = 0, py::arg("pool_subset_stage") = -1)
+           py::arg("pool_topk_strip") = 0, py::arg("pool_subset_stage") = -1,
+           py::arg("pool_subset_topk_fused") = true,
+           py::arg("pool_subset_topk_fused_max") = 1024)
       // serving snapshots (docs/DESIGN.md §2)
       .def_property_readonly("frozen", &Engine::frozen)
       .def_property_readonly("serve_fused", &Engine::serve_fused)
@@ -750,6 +755,15 @@ PYBIND11_MODULE(_xflow_native, m) {
            py::arg("req_ptr"), py::arg("M"), py::arg("pctr"),
            py::arg("crosses") = std::vector<std::vector<int32_t>>(), py::arg("ctx_ops") = 0,
            py::arg("pool_ops") = 0)
+      .def_property_readonly("pool_subset_topk_fused", &Engine::pool_subset_topk_fused)
+      .def("pool_subset_topk",
+           [](Engine& e, uintptr_t ctx, int64_t R, uintptr_t pool, int64_t N, uintptr_t index,
+              uintptr_t req_ptr, int64_t M, int k, uintptr_t idx, uintptr_t score) {
+             e.pool_subset_topk(P<const float>(ctx), R, P<const float>(pool), N,
+                                P<const int32_t>(index), P<const int32_t>(req_ptr), M, k,
+                                P<int32_t>(idx), P<float>(score));
+           },
+           py::call_guard<py::gil_scoped_release>())
       .def("slices_of", &Engine::slices_of)
       .def_static("slice_groups", &Engine::slice_groups)
       .def_static("group_slices", &Engine::group_slices)

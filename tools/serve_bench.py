@@ -47,7 +47,10 @@ serve the shape, ``rank_step`` on the pool's rows repeated once per request
 (where those R x N rows stay under --pool-expand-rows).  --pool --pool-subset
 L[,L..] measures ``pool_subset`` instead: R requests with L random pool indices
 each, against ``rank_step`` on the gathered rows, ``pool_score`` over the whole
-pool, and itself with the staged gather off.
+pool, and itself with the staged gather off.  With --top-k K[,K..] a second
+table follows (--topk-ab-only: it alone): ``pool_subset_topk`` at every K, the
+fused kernel / the composed path of an engine pair that differs in
+``pool_subset_topk_fused`` alone, and the composition with torch ops it replaced.
 
     python tools/serve_bench.py [--model fm --v-dim 8] [--out profiles/serve.txt]
     python tools/serve_bench.py --pool [--model fm --v-dim 32 --fm-math standard]
@@ -501,6 +504,62 @@ def pool_subset_section(a, dev, snap_dir, synth, say):
                                    R * L * e.pool_width * 4 / m[1] / 1e6))
 
 
+def pool_subset_topk_section(a, dev, snap_dir, synth, say):
+    """The best K of every request's own --pool-subset candidates: the fused
+    pool_subset_topk kernel against the composed path of the same build, an
+    engine pair that differs in EngineConfig.pool_subset_topk_fused alone."""
+    p, _, _ = loaded(snap_dir, dev, a)
+    e, C, F = p.engine, a.rank_ctx, a.fields
+    assert e.pools and 0 < C < F
+    # (neither path reads the table: empty engines serve the two settings)
+    f, c = (Engine(p.model, p.optim, EngineConfig(table_log2_cap=16, max_rows=16, max_nnz=1024,
+                                                  pool_subset_topk_fused=on,
+                                                  pool_subset_topk_fused_max=0), device=dev)
+            for on in (True, False))
+    assert f.pool_subset_topk_fused and not c.pool_subset_topk_fused
+    say("# ms per call of Engine.pool_subset_topk alone (the vectors resident), medians of %d "
+        "alternating blocks of device-event time; every request has its own L random pool "
+        "indices.  fused: one kernel scores a tile of the list into the registers it sorts.  "
+        "composed: pool_subset into a score array, topk_step, positions -> pool indices by one "
+        "kernel (pool_subset_topk_fused=False).  torch_map: pool_subset, topk_step and the "
+        "positions mapped by torch ops, the path before the fused kernel" % a.blocks)
+    say("candidates L requests K fused composed torch_map composed/fused torch_map/fused")
+    gen = SyntheticCriteo(e, a.batch, synth)
+    b = gen.alloc_batch()
+    keys = []
+    while sum(len(x) for x in keys) < 65536 + 256:
+        gen.next(out=b)
+        keys.append((b.keys.view(F, a.batch).t() if b.field_major else b.keys.view(a.batch, F)).clone())
+    keys = torch.cat(keys)
+    N = 65536
+    cand = keys[:N, C:].contiguous()
+    pv = e.pool_rows(Batch(keys=cand.t().contiguous().view(-1), labels=torch.zeros(N, device=dev),
+                           nnz_per_row=F - C, field_major=True))
+    for L in a.pool_subset:
+        for R in (1, 32, 256):
+            cv = e.pool_rows(Batch(keys=keys[N:N + R, :C].contiguous().view(-1),
+                                   labels=torch.zeros(R, device=dev), nnz_per_row=C))
+            index = torch.randint(0, N, (R * L,), device=dev, dtype=torch.int32)
+            rptr = (torch.arange(R + 1, device=dev) * L).to(torch.int32)
+            for K in a.top_k:
+                def torch_map():
+                    pos, sc = c.topk_step(c.pool_subset(cv, pv, index, rptr), rptr, K)
+                    at = (pos.clamp(min=0).long() + rptr[:-1, None].long()).clamp(max=R * L - 1)
+                    return index[at], sc
+
+                calls = [lambda: f.pool_subset_topk(cv, pv, index, rptr, K),
+                         lambda: c.pool_subset_topk(cv, pv, index, rptr, K), torch_map]
+                got = [x() for x in calls]
+                n = min(K, L)  # (past a request's entries torch_map holds no padding)
+                assert all(torch.equal(g[0][:, :n], got[0][0][:, :n]) and
+                           torch.equal(g[1].view(torch.int32), got[0][1].view(torch.int32))
+                           for g in got[1:])
+                reps = 200 if R * L <= 1 << 16 else 50
+                m = [median(t) for t in timed_blocks(calls, reps, a.blocks, dev)]
+                say("%d %d %d %d %.4f %.4f %.4f %.2f %.2f"
+                    % (N, L, R, K, m[0], m[1], m[2], m[1] / m[0], m[2] / m[0]))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -533,6 +592,8 @@ def main() -> int:
     ap.add_argument("--pool-subset", type=lambda s: [int(x) for x in s.split(",")], default=[],
                     metavar="L[,L..]", help="with --pool: every request scores its own L random "
                                             "pool indices (pool_subset) instead")
+    ap.add_argument("--topk-ab-only", action="store_true",
+                    help="with --pool --pool-subset --top-k: only the fused / composed table")
     ap.add_argument("--tmp", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
@@ -570,7 +631,10 @@ def main() -> int:
         del eng
         torch.cuda.empty_cache()
         if a.pool:
-            (pool_subset_section if a.pool_subset else pool_section)(a, dev, snap_dir, synth, say)
+            if not (a.pool_subset and a.top_k and a.topk_ab_only):
+                (pool_subset_section if a.pool_subset else pool_section)(a, dev, snap_dir, synth, say)
+            if a.pool_subset and a.top_k:
+                pool_subset_topk_section(a, dev, snap_dir, synth, say)
             return done()
         if a.rank:
             section = rank_cross_section if a.cross else (topk_section if a.top_k else rank_section)

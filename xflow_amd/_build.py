@@ -55,6 +55,7 @@ HIP_FILE_FLAGS = {"kernels_rank.hip": _NO_PACKED_FP32, "kernels_rank_cross.hip":
                   "kernels_topk.hip": _NO_PACKED_FP32, "kernels_pool.hip": _NO_PACKED_FP32,
                   "kernels_pool_topk.hip": _NO_PACKED_FP32,
                   "kernels_pool_subset.hip": _NO_PACKED_FP32,
+                  "kernels_pool_subset_topk.hip": _NO_PACKED_FP32,
                   "kernels_pool_cross.hip": _NO_PACKED_FP32}
 
 HOST_SOURCES = ["io/reader.cpp", "cpu/cpu_backend.cpp", "engine/engine.cpp", "engine/engine_step.cpp",

@@ -235,6 +235,19 @@ class EngineConfig:
     # direct loads at 8 and 12 floats, where it measured 5 to 7 % behind and
     # even (profiles/rank_pool_subset.txt)
     pool_subset_stage: bool | None = None
+    # Engine.pool_subset_topk on HIP computes a tile's scores straight into the
+    # registers its top-k network sorts: no score array, no second pass, pool
+    # indices written directly (docs/DESIGN.md §2); False: pool_subset, then
+    # topk_step, then the map of positions to pool indices (the A/B switch).
+    # Engine.pool_subset_topk_fused reports the path taken
+    pool_subset_topk_fused: bool = True
+    # ... for calls of at most this many list entries; larger calls take the
+    # composed path.  A workgroup walks its tile's 16 rounds one after another,
+    # and measured the kernel is ahead only while a call is one short tile
+    # (profiles/rank_pool_subset_topk.txt: 1.04x to 1.17x ahead at 64 and 512
+    # entries, 0.51x to 0.98x, behind, from 2048 entries on, LR, FM-8 and FM-32);
+    # 0: the fused kernel at every size
+    pool_subset_topk_fused_max: int = 1024
 
 
 @dataclass

@@ -219,7 +219,9 @@ class Engine:
                            pool_topk_fused=self.cfg.pool_topk_fused,
                            pool_topk_strip=int(self.cfg.pool_topk_strip),
                            pool_subset_stage=-1 if self.cfg.pool_subset_stage is None
-                           else int(bool(self.cfg.pool_subset_stage)))
+                           else int(bool(self.cfg.pool_subset_stage)),
+                           pool_subset_topk_fused=bool(self.cfg.pool_subset_topk_fused),
+                           pool_subset_topk_fused_max=int(self.cfg.pool_subset_topk_fused_max))
         if self.is_gpu != (self.device.type == "cuda"):
             raise RuntimeError("native engine backend does not match the requested device")
         # delta_clear() calls so far: a serving or checkpoint delta is only
@@ -520,6 +522,55 @@ class Engine:
         self._e.pool_subset(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(), int(pool_vecs.shape[0]),
                             index.data_ptr(), req_ptr.data_ptr(), M, out.data_ptr(), *xargs)
         return out
+
+    @property
+    def pool_subset_topk_fused(self) -> bool:
+        """pool_subset_topk (without crosses) takes the fused kernel: a HIP
+        engine with EngineConfig.pool_subset_topk_fused."""
+        return bool(self._e.pool_subset_topk_fused)
+
+    def pool_subset_topk(self, ctx_vecs: torch.Tensor, pool_vecs: torch.Tensor,
+                         index: torch.Tensor, req_ptr: torch.Tensor, k: int, crosses=None,
+                         ctx_ops: torch.Tensor | None = None,
+                         pool_ops: torch.Tensor | None = None
+                         ) -> tuple[torch.Tensor, torch.Tensor]:
+        """The best ``k`` (1 .. 1024) entries of every request's own list:
+        pool_subset's arguments, topk_step's answer -- (idx int32 [R, k], score
+        float32 [R, k]), best first in topk_step's order, padded with -1 / 0.0
+        -- but ``idx`` holds pool indices (index[e]), not positions in the list.
+        With ``pool_subset_topk_fused``, up to
+        EngineConfig.pool_subset_topk_fused_max entries, one kernel scores a tile of the list
+        into the registers it sorts and no score array exists; the scores have
+        pool_subset's bits, except that a score of the last tie class (NaN, zero
+        or negative) comes back as +0.0.  Otherwise pool_subset, topk_step and
+        the map of positions, in the same stream.  With ``crosses`` always the
+        latter, on the crossed pool_subset."""
+        if not 1 <= int(k) <= 1024:
+            raise ValueError("k must be 1 .. 1024")
+        if crosses:
+            p = self.pool_subset(ctx_vecs, pool_vecs, index, req_ptr, crosses=crosses,
+                                 ctx_ops=ctx_ops, pool_ops=pool_ops)
+            pos, score = self.topk_step(p, req_ptr, k)
+            if index.numel() == 0:
+                return pos, score
+            at = (pos.clamp(min=0).long() + req_ptr[:-1, None].long()).clamp(max=index.numel() - 1)
+            return torch.where(pos >= 0, index[at], pos), score
+        self._pool_vecs("ctx_vecs", ctx_vecs)
+        self._pool_vecs("pool_vecs", pool_vecs)
+        for name, t in (("index", index), ("req_ptr", req_ptr)):
+            if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or \
+                    t.dim() != 1:
+                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on {self.device}")
+        R, M = int(ctx_vecs.shape[0]), int(index.numel())
+        if req_ptr.numel() != R + 1:
+            raise ValueError("req_ptr must hold one offset per context, plus one")
+        idx = torch.empty((R, int(k)), dtype=torch.int32, device=self.device)
+        score = torch.empty((R, int(k)), dtype=torch.float32, device=self.device)
+        self._sync_stream()
+        self._e.pool_subset_topk(ctx_vecs.data_ptr(), R, pool_vecs.data_ptr(),
+                                 int(pool_vecs.shape[0]), index.data_ptr(), req_ptr.data_ptr(), M,
+                                 int(k), idx.data_ptr(), score.data_ptr())
+        return idx, score
 
     def train_view(self, view) -> None:
         """Train on a native BatchView (e.g. engine-staged synthetic batch)."""

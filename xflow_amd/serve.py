@@ -637,17 +637,15 @@ class Predictor:
                 rp = ptr[q:q1 + 1] - m0
                 up = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.int32)).to(self.device)
                 idx_d, rp_d = up(index[m0:m1]), up(rp)
-                p = self.engine.pool_subset(cv, vecs, idx_d, rp_d, **xkw)
                 if top_k is None:
-                    p = p.cpu().numpy()
+                    p = self.engine.pool_subset(cv, vecs, idx_d, rp_d, **xkw).cpu().numpy()
                     out += [p[rp[j]:rp[j + 1]] for j in range(q1 - q)]
                 elif m1 == m0:
                     out += [(np.zeros(0, np.int32), np.zeros(0, np.float32))] * (q1 - q)
                 else:
-                    pos, sc = self.engine.topk_step(p, rp_d, int(top_k))
-                    # positions inside a request's list -> pool indices, on the device
-                    at = (pos.clamp(min=0).long() + rp_d[:-1, None].long()).clamp(max=m1 - m0 - 1)
-                    pi, sc = idx_d[at].cpu().numpy(), sc.cpu().numpy()
+                    # scored and selected on the device, as pool indices
+                    pi, sc = (t.cpu().numpy() for t in self.engine.pool_subset_topk(
+                        cv, vecs, idx_d, rp_d, int(top_k), **xkw))
                     n = np.minimum(int(top_k), np.diff(rp))
                     out += [(pi[j, :n[j]], sc[j, :n[j]]) for j in range(q1 - q)]
                 q = q1
